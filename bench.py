@@ -69,7 +69,12 @@ def parse():
     ap.add_argument("--leg", default="", choices=["", "train_fp32", "train_bf16"],
                     help="internal: run ONE leg in this process and print its dict as a JSON line (the fp32 training leg runs in a child process with a clean MIOpen environment)")
     ap.add_argument("--all-legs", action="store_true", help="with --gpus > 1: also run the uniform / H2D-merge / Waymo legs (default: value, roofline, value_train only, so that an 8-rank run stays short)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed loop, write the detections of its last step to DIR/<name>.npy (see dump_outputs); rank r > 0 prefixes rank<r>_")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def free_port():
@@ -181,6 +186,27 @@ def cpu_model():
 
 
 # ------------------------------------------------------------------------------------------------ GPU legs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, det, tokens, prefix=""):
+    """What a caller of the serving loop receives for one step, frames in batch order: box3d_lidar (n, 9) float32, scores (n,) float32,
+    label_preds (n,) float64 and frame_counts (B,) float64 (the rows of each frame).  NMS keeps at most post_max_size boxes per task and
+    frame, so this is well under DUMP_LIMIT_BYTES at any batch that fits the device."""
+    import numpy as np
+    import torch
+
+    rows = [det[t] for t in tokens]
+    arrs = {"box3d_lidar": torch.cat([r["box3d_lidar"].reshape(-1, 9) for r in rows]).float().numpy(),
+            "scores": torch.cat([r["scores"] for r in rows]).float().numpy(),
+            "label_preds": torch.cat([r["label_preds"] for r in rows]).numpy().astype(np.float64),
+            "frame_counts": np.asarray([len(r["scores"]) for r in rows], np.float64)}
+    assert sum(v.nbytes for v in arrs.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, prefix + k + ".npy"), v)
+
+
 def serving_loop(model, examples, steps, upload=None):
     """`steps` frame batches through the fused graph; batch i+1 is enqueued before the host blocks on (and unpacks) the detections of
     batch i, and every batch's detections are on the host, as dicts, before this returns."""
@@ -555,6 +581,8 @@ def main():
         host_ms = serving_loop.host_enqueue_ms
         r_us, c_us, ns = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_int32(0)
         _lib.check(L.pnx_profile_end(ctypes.byref(r_us), ctypes.byref(c_us), ctypes.byref(ns)), "pnx_profile_end")
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out, examples[(a.steps - 1) % ROTATE]["token"], f"rank{rank}_" if rank else "")
         pfn_us, vox_us = float(L.pnx_profile_last_pfn_us()), float(L.pnx_profile_last_voxelize_us())
         # the same reader calls back to back, nothing else on the GPU between them: the convolutions of the detector leave the chip in a
         # power / cache state in which the reader's kernels run 12-20 % slower (profiles/r04_reader_between.txt); `roofline` is the in-loop figure

@@ -275,6 +275,22 @@ def gen_iou_nms():
     np.savez_compressed(os.path.join(OUT, "nms_rotated.npz"), **cases)
 
 
+def gen_ref_random():
+    """The compiled reference on the random box sets of test_oracle_golden.py / test_gpu_iou_nms.py, so that those tests compare
+    against the reference where oracle/_ref cannot be built."""
+    a, _ = synth.clustered_boxes(300, 101, spread=10.0)
+    b, _ = synth.clustered_boxes(200, 102, spread=10.0)
+    out = dict(cpu_a=a, cpu_b=b, cpu_iou_ab=O.ref_boxes_iou_bev(a, b), cpu_keep_a_t020=O.ref_nms_rotated(a, 0.2))
+    a, _ = synth.clustered_boxes(600, 911, spread=10.0)
+    b, _ = synth.clustered_boxes(400, 912, spread=10.0)
+    boxes, scores = synth.clustered_boxes(1000, 920, spread=12.0)
+    sb = np.ascontiguousarray(boxes[np.argsort(-scores, kind="stable")])
+    out.update(gpu_a=a, gpu_b=b, gpu_iou_ab=O.ref_boxes_iou_bev(a, b), gpu_sorted_boxes=sb, gpu_keep_t020=O.ref_nms_rotated(sb, 0.2),
+               gpu_sorted_margin_t020=np.float64(np.abs(O.ref_boxes_iou_bev(sb, sb) - 0.2).min()))
+    np.savez_compressed(os.path.join(OUT, "ref_iou_random.npz"), **out)
+    print("[golden] ref_iou_random:", {k: v.shape for k, v in out.items()})
+
+
 # --------------------------------------------------------------------------- decode fixture
 def ns(**k):
     return types.SimpleNamespace(**k)
@@ -597,7 +613,7 @@ def main():
     install_numba_identity()
     install_iou3d_nms()
     sys.path.insert(0, REF)
-    what = sys.argv[1:] or ["reader", "train", "iou", "decode", "decode_lazy", "loss", "voxel", "mvf", "merge"]
+    what = sys.argv[1:] or ["reader", "train", "iou", "decode", "decode_lazy", "loss", "voxel", "mvf", "merge", "ref_random"]
     if "reader" in what:
         gen_reader()
     if "train" in what:
@@ -616,6 +632,8 @@ def main():
         gen_mvf_parts()
     if "merge" in what:
         gen_merge()
+    if "ref_random" in what:
+        gen_ref_random()
 
 
 if __name__ == "__main__":

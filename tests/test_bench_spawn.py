@@ -54,6 +54,24 @@ def test_gpus_2_with_real_kernels_on_one_gpu():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the detections of the timed loop's last step as .npy files (float32 / float64), whose rows add up to the line's count."""
+    import numpy as np
+
+    r = run(["--batch", "2", "--steps", "3", "--warmup", "1", "--no-extras", "--no-back-to-back", "--dump-outputs", str(tmp_path)],
+            {"PNX_NO_MIOPEN_BENCH": "1"}, timeout=900)
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    names = ("box3d_lidar", "scores", "label_preds", "frame_counts")
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in names)
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in names}
+    n = int(d["frame_counts"].sum())
+    assert d["frame_counts"].shape == (2,) and d["frame_counts"].dtype == np.float64 and n == r["detections_last_step"] > 0
+    assert d["box3d_lidar"].shape == (n, 9) and d["box3d_lidar"].dtype == np.float32 and np.isfinite(d["box3d_lidar"]).all()
+    assert d["scores"].shape == (n,) and d["scores"].dtype == np.float32 and np.isfinite(d["scores"]).all()
+    assert d["label_preds"].shape == (n,) and d["label_preds"].dtype == np.float64 and np.array_equal(d["label_preds"], np.round(d["label_preds"]))
+
+
+@pytest.mark.gpu
 def test_gpus_2_over_rccl_when_two_devices_are_visible():
     """The same line over RCCL (backend nccl, one rank per GPU): runs wherever >= 2 devices are visible -- the boxes this repository is developed on have
     one, so there it skips and the gloo form above is what exercises the N-rank path."""

@@ -173,24 +173,29 @@ def test_nms_pair_list_overflow_path_is_bit_identical(oracle, monkeypatch):
 
 
 def test_hip_against_the_compiled_reference(oracle):
-    """HIP kernels vs the reference's own iou3d_cpu.cpp compiled in place (oracle/_ref, prebuilt in the build container and shipped with the snapshot):
-    IoU-BEV within 1e-5 (libm vs det-math transcendentals), NMS keep indices identical.  Skips where the library is absent."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref/libref_iou3d.so not present")
+    """HIP kernels vs the reference's own iou3d_cpu.cpp: its outputs stored in tests/golden/ref_iou_random.npz (oracle/gen_golden.py
+    ref_random), checked against the compiled reference itself where oracle/_ref exists.  IoU-BEV within 1e-5 (libm vs det-math
+    transcendentals), NMS keep indices identical."""
     from pillarnext_amd import ops, synth
 
-    a, _ = synth.clustered_boxes(600, 911, spread=10.0)
-    b, _ = synth.clustered_boxes(400, 912, spread=10.0)
+    g = load_golden("ref_iou_random")
+    a, b, ref = g["gpu_a"], g["gpu_b"], g["gpu_iou_ab"]
+    assert np.array_equal(a, synth.clustered_boxes(600, 911, spread=10.0)[0])
+    assert np.array_equal(b, synth.clustered_boxes(400, 912, spread=10.0)[0])
+    if oracle.have_ref():
+        assert np.array_equal(oracle.ref_boxes_iou_bev(a, b).view(np.uint32), ref.view(np.uint32))
     out = torch.zeros((600, 400), device="cuda")
     ops.boxes_iou_bev(cu(a), cu(b), out)
-    ref = oracle.ref_boxes_iou_bev(a, b)
     assert (ref > 0).mean() > 0.01
     np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=0, atol=1e-5)
     boxes, scores = synth.clustered_boxes(1000, 920, spread=12.0)   # seed 920: no pair within 7e-5 of the threshold (libm vs det-math differ by <= 1e-5)
     order = np.argsort(-scores, kind="stable")
     sb = np.ascontiguousarray(boxes[order])
-    keep_ref = oracle.ref_nms_rotated(sb, 0.2)
-    iou = oracle.ref_boxes_iou_bev(sb, sb)
-    assert np.abs(iou - 0.2).min() > 2e-5, "a pair sits on the threshold: pick another seed"
+    assert np.array_equal(sb, g["gpu_sorted_boxes"])
+    keep_ref = g["gpu_keep_t020"]
+    if oracle.have_ref():
+        assert np.array_equal(oracle.ref_nms_rotated(sb, 0.2), keep_ref)
+        assert np.abs(oracle.ref_boxes_iou_bev(sb, sb) - 0.2).min() == g["gpu_sorted_margin_t020"]
+    assert g["gpu_sorted_margin_t020"] > 2e-5, "a pair sits on the threshold: pick another seed"
     k, num = ops.nms_single(cu(sb), 0.2)
     assert np.array_equal(np.asarray(keep_ref, np.int64), k[:num].cpu().numpy().astype(np.int64))

@@ -72,19 +72,22 @@ def test_nms_golden_keep_indices(oracle, name):
 
 
 def test_oracle_vs_compiled_reference_random(oracle):
-    """oracle(libm) == reference iou3d_cpu.cpp bit-for-bit on fresh random boxes (needs oracle/_ref)."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent and no prebuilt library)")
+    """oracle(libm) == reference iou3d_cpu.cpp bit-for-bit on random boxes: the reference's outputs stored in
+    tests/golden/ref_iou_random.npz (oracle/gen_golden.py ref_random), and the compiled reference itself where oracle/_ref exists."""
     from pillarnext_amd import synth
 
-    a, _ = synth.clustered_boxes(300, 101, spread=10.0)
-    b, _ = synth.clustered_boxes(200, 102, spread=10.0)
-    r = oracle.ref_boxes_iou_bev(a, b)
+    g = load_golden("ref_iou_random")
+    a, b, r = g["cpu_a"], g["cpu_b"], g["cpu_iou_ab"]
+    assert np.array_equal(a, synth.clustered_boxes(300, 101, spread=10.0)[0])
+    assert np.array_equal(b, synth.clustered_boxes(200, 102, spread=10.0)[0])
+    if oracle.have_ref():
+        assert np.array_equal(oracle.ref_boxes_iou_bev(a, b).view(np.uint32), r.view(np.uint32))
+        assert np.array_equal(oracle.ref_nms_rotated(a, 0.2), g["cpu_keep_a_t020"])
     o = oracle.boxes_iou_bev(a, b, "libm")
     assert np.array_equal(r.view(np.uint32), o.view(np.uint32))
     assert (r > 0).mean() > 0.02
     np.testing.assert_allclose(oracle.boxes_iou_bev(a, b, "det"), r, rtol=0, atol=1e-5)
-    assert np.array_equal(oracle.ref_nms_rotated(a, 0.2), oracle.nms_rotated(a, 0.2, "libm"))
+    assert np.array_equal(g["cpu_keep_a_t020"], oracle.nms_rotated(a, 0.2, "libm"))
 
 
 def test_nms_edge_cases(oracle):
