@@ -277,6 +277,12 @@ int pnx_conv3x3_wgrad_bf16(const void* x, const void* dy, const uint8_t* mask, f
  * tiles staged for the three products, fp32 accumulation, deterministic; shapes, mask and workspace as pnx_conv3x3_wgrad_bf16. */
 int pnx_conv3x3_wgrad_x3(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, const uint8_t* mask, float* dw, int32_t batch, int32_t h,
                          int32_t w, int32_t cin, int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+/* The same from three bf16 pieces of both operands (pnx_split3_f32): the six products of piece orders 0..2 (x_hi dY_hi, x_hi dY_mid, x_mid dY_hi,
+ * x_mid dY_mid, x_hi dY_lo, x_lo dY_hi) in one pass, seven operand tiles staged for the six, hi x hi last, fp32 accumulation, deterministic; shapes, mask
+ * and workspace as pnx_conv3x3_wgrad_bf16. */
+int pnx_conv3x3_wgrad_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* dy_hi, const void* dy_mid, const void* dy_lo, const uint8_t* mask,
+                         float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes,
+                         pnx_stream_t stream);
 /* (cout, cin, 3, 3) fp32 / bf16 weights -> wfrag of pnx_conv3x3_bf16 (9*cout*cin bf16) in one launch; transposed != 0: the weights of the data
  * gradient of a stride-1 layer, wt[ci][co][ky][kx] = w[co][ci][2-ky][2-kx], i.e. the wfrag of a cout -> cin convolution. */
 int pnx_conv3x3_pack_weights(const void* w, int32_t dtype, int32_t cout, int32_t cin, int32_t transposed, void* wfrag, pnx_stream_t stream);
@@ -330,6 +336,13 @@ int pnx_sephead_lazy_f16(const PnxLazyTask* tasks, int32_t n_tasks, const int32_
 int pnx_split_f32(const float* x, void* hi, void* lo, int64_t n, const uint8_t* mask, int32_t channels, pnx_stream_t stream);
 int pnx_conv3x3_x3(const void* x_hi, const void* x_lo, const void* wfrag_hi, const void* wfrag_lo, const float* bias, const uint8_t* mask, float* y,
                    int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream);
+/* Three bf16 pieces per operand for the fp32 graph's reference-precision form (PNX_TRAIN_F32_PIECES=3): pnx_split3_f32 writes hi = RNE(x),
+ * mid = RNE(x - hi), lo = RNE(x - hi - mid) (exact: hi + mid + lo == x for every finite |x| >= 2^-100; n, mask, alignment and the non-finite convention as
+ * pnx_split_f32), and pnx_conv3x3_x6 accumulates the six products of piece orders 0..2 (hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi; what is dropped is
+ * ~2^-23 of sum |x||W|) in fp32 inside one launch, low-order products first.  Shapes, mask, bias and output as pnx_conv3x3_x3. */
+int pnx_split3_f32(const float* x, void* hi, void* mid, void* lo, int64_t n, const uint8_t* mask, int32_t channels, pnx_stream_t stream);
+int pnx_conv3x3_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* wfrag_hi, const void* wfrag_mid, const void* wfrag_lo, const float* bias,
+                   const uint8_t* mask, float* y, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream);
 /* Data gradient of the backbone's stride-2 SparseConv2d layers in training (csrc/conv_dgrad_s2.h; reference: det3d/models/utils/sparse_conv.py:16-39 under
  * autograd): the four parity planes of dx as four small convolutions of the upstream gradient (1, 2, 2, 4 taps).  g: NHWC (batch, ho, wo, cout) bf16 with
  * ho = (h - 1) / 2 + 1; wfrag_t: pnx_conv3x3_pack_weights(transposed = 1) of the (cout, cin, 3, 3) weights; mask_in: uint8 (batch, h, w), the layer's INPUT active
@@ -339,6 +352,9 @@ int pnx_conv3x3_dgrad_s2_bf16(const void* g, const void* wfrag_t, const uint8_t*
                               int32_t cout, pnx_stream_t stream);
 int pnx_conv3x3_dgrad_s2_x3(const void* g_hi, const void* g_lo, const void* wfrag_t_hi, const void* wfrag_t_lo, const uint8_t* mask_in, float* dx, int32_t batch,
                             int32_t h, int32_t w, int32_t cin, int32_t cout, pnx_stream_t stream);
+/* _x6: the three-piece form (pnx_split3_f32 pieces of g and of the weights, six products, fp32 dx); shapes and mask as above. */
+int pnx_conv3x3_dgrad_s2_x6(const void* g_hi, const void* g_mid, const void* g_lo, const void* wfrag_t_hi, const void* wfrag_t_mid, const void* wfrag_t_lo,
+                            const uint8_t* mask_in, float* dx, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, pnx_stream_t stream);
 /* The SepHead's output convolutions in training (csrc/head_train.hip; reference: det3d/models/heads/centerhead.py:31-41, nn.Conv2d(64, k, 3, padding 1,
  * bias=True) with k = classes / 2 / 1 / 3 / 2 / 2, under autograd): bandwidth-bound layers MIOpen runs at 1/7 of the HBM rate.
  *   pnx_conv3x3_smallk        y = conv3x3(x, weight) + bias: x NHWC (batch, h, w, 64), y NHWC (batch, h, w, k), both `dtype` (PNX_F32 or PNX_BF16);

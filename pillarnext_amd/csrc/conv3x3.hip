@@ -1142,18 +1142,21 @@ __device__ __forceinline__ void stage_tile64_s2(uint4* __restrict__ s_in, const 
   }
 }
 
-template <int NR, int CIN, int COUT, int MB, bool X3 = false>
+// NP = bf16 pieces per operand, as in conv_pc.h::pc_rows: x / x2 / x3 and wfrag / wfrag2 / wfrag3 = hi / lo (NP 2) or hi / mid / lo (NP 3).
+template <int NR, int CIN, int COUT, int MB, int NP = 1>
 __device__ __forceinline__ void conv_rows_s2(uint4* __restrict__ s_in, const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2,
-                                             const uint4* __restrict__ wfrag, const uint4* __restrict__ wfrag2, const float* __restrict__ bias, const int (&rbase)[4], const uint32_t (&rmask)[4],
+                                             const uint16_t* __restrict__ x3, const uint4* __restrict__ wfrag, const uint4* __restrict__ wfrag2,
+                                             const uint4* __restrict__ wfrag3, const float* __restrict__ bias, const int (&rbase)[4], const uint32_t (&rmask)[4],
                                              uint16_t* const (&yrow)[4], int b, int H, int W, int iy0, int ix0, int n_valid, uint32_t need, int mg,
                                              int relu, int px, int kb, int lane) {
   constexpr int NS = CIN / 64, NRA = NR > 0 ? NR : 1;
+  constexpr bool X3 = NP == 2, F32 = NP > 1;
   v16f acc[NRA][MB];
   if (NR > 0) {
 #pragma unroll
     for (int m = 0; m < MB; m++) {
       v16f bq;
-      if (X3 && bias == nullptr) {
+      if (F32 && bias == nullptr) {
 #pragma unroll
         for (int i = 0; i < 16; i++) bq[i] = 0.f;
       } else {
@@ -1163,19 +1166,29 @@ __device__ __forceinline__ void conv_rows_s2(uint4* __restrict__ s_in, const uin
       for (int j = 0; j < NR; j++) acc[j][m] = bq;
     }
   }
-  // X3 (fp32 product of bf16 pairs, see conv_pc.h): the NS slabs of the high halves (taps with W_hi and with W_lo), then those of the low halves (W_hi)
+  // X3 (fp32 product of bf16 pairs, see conv_pc.h): the NS slabs of the high halves (taps with W_hi and with W_lo), then those of the low halves (W_hi).
+  // NP 3: the NS slabs of x_lo (W_hi), of x_mid (W_mid, W_hi), of x_hi (W_lo, W_mid, W_hi) -- the caller staged slab 0 of x_lo.
 #pragma unroll 1
-  for (int sq = 0; sq < NS * (X3 ? 2 : 1); sq++) {
-    const int sl = X3 ? sq % NS : sq;
+  for (int sq = 0; sq < NS * NP; sq++) {
+    const int sl = F32 ? sq % NS : sq;
     if (sq) {
       __syncthreads();  // previous slab consumed
-      stage_tile64_s2<CIN>(s_in, X3 && sq >= NS ? x2 : x, b, H, W, 64 * sl, iy0, ix0, need);
+      const uint16_t* xs = X3 && sq >= NS ? x2 : x;
+      if constexpr (NP == 3) xs = sq < NS ? x3 : sq < 2 * NS ? x2 : x;
+      stage_tile64_s2<CIN>(s_in, xs, b, H, W, 64 * sl, iy0, ix0, need);
       __syncthreads();
     }
     if (NR > 0) {
-      conv_taps<NRA, COUT / 32, CIN / 16, 2, MB>(acc, s_in, wfrag, rbase, mg, px, kb, lane, 4 * sl);
-      if constexpr (X3) {
-        if (sq < NS) conv_taps<NRA, COUT / 32, CIN / 16, 2, MB>(acc, s_in, wfrag2, rbase, mg, px, kb, lane, 4 * sl);
+      if constexpr (NP == 3) {
+        const int q = sq / NS;  // piece 2 - q of x: W pieces q .. 0
+#pragma unroll 1
+        for (int k = q; k >= 0; k--)
+          conv_taps<NRA, COUT / 32, CIN / 16, 2, MB>(acc, s_in, k == 0 ? wfrag : k == 1 ? wfrag2 : wfrag3, rbase, mg, px, kb, lane, 4 * sl);
+      } else {
+        conv_taps<NRA, COUT / 32, CIN / 16, 2, MB>(acc, s_in, wfrag, rbase, mg, px, kb, lane, 4 * sl);
+        if constexpr (X3) {
+          if (sq < NS) conv_taps<NRA, COUT / 32, CIN / 16, 2, MB>(acc, s_in, wfrag2, rbase, mg, px, kb, lane, 4 * sl);
+        }
       }
     }
   }
@@ -1183,7 +1196,7 @@ __device__ __forceinline__ void conv_rows_s2(uint4* __restrict__ s_in, const uin
 #pragma unroll
     for (int j = 0; j < NR; j++) {
       const bool act = (rmask[j] >> px) & 1u;
-      if constexpr (X3) {
+      if constexpr (F32) {
 #pragma unroll
         for (int m = 0; m < MB; m++) store_tile_f32<COUT>(acc[j][m], act, reinterpret_cast<float*>(yrow[j]) + (mg + m) * 32, n_valid, px, kb);
       } else if constexpr (MB == 2) {
@@ -1207,17 +1220,18 @@ __device__ __forceinline__ void conv_rows_s2(uint4* __restrict__ s_in, const uin
 }
 
 // H, W: input; Ho, Wo: output.  The 4 waves are COUT/64 groups of 64 output channels x 4/(COUT/64) row groups.
-template <int CIN, int COUT, bool X3 = false>
+template <int CIN, int COUT, int NP = 1>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, const uint4* __restrict__ wfrag,
                                                     const uint4* __restrict__ wfrag2, const float* __restrict__ bias,
                                                     const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W, int Ho, int Wo,
-                                                    int relu, uint8_t* __restrict__ row_dirty, int slot) {
+                                                    int relu, uint8_t* __restrict__ row_dirty, int slot, const uint16_t* __restrict__ x3 = nullptr,
+                                                    const uint4* __restrict__ wfrag3 = nullptr) {
   static_assert(CIN % 64 == 0 && (COUT == 128 || COUT == 256), "64-channel input slabs; 4 groups of 32 or of 64 output channels");
   // Round 6: with 128 output channels the waves were 2 row groups x 2 groups of 64 channels, i.e. at most TWO rows per wave -- one 1 KiB weight fragment from
   // L1 per two MFMAs, which is all of the L1's bandwidth at full MFMA rate (the 759 us outlier of profiles/r06_bench_steady_trace.md).  Now every shape has one
   // row group: four rows per wave, four channel groups of COUT / 4.
   constexpr int TH = S2_TH, MB = COUT / 128, NCG = 4, NRG = 1, NRMAX = TH / NRG;
-  constexpr int YS = X3 ? 2 : 1;  // output element in units of uint16_t (X3: fp32)
+  constexpr int YS = NP > 1 ? 2 : 1;  // output element in units of uint16_t (NP > 1: fp32)
   extern __shared__ uint4 s_in[];  // S2_NSTAGE
   __shared__ uint32_t s_rowmask2[2 * TH];
   __shared__ unsigned int s_next[2];
@@ -1288,9 +1302,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restric
     for (int r = 0; r < TH; r++)
       if ((am >> r) & 1u) need |= 7u << (2 * r);
     const int iy0 = 2 * y0 - 1, ix0 = 2 * x0 - 1;
-    stage_tile64_s2<CIN>(s_in, x, b, H, W, 0, iy0, ix0, need);
+    stage_tile64_s2<CIN>(s_in, NP == 3 ? x3 : x, b, H, W, 0, iy0, ix0, need);  // NP 3: the low pieces come first
     __syncthreads();
-#define PNX_ROWS_S2(N_) conv_rows_s2<(N_ <= NRMAX ? N_ : NRMAX), CIN, COUT, MB, X3>(s_in, x, x2, wfrag, wfrag2, bias, rbase, rmask, yrow, b, H, W, iy0, ix0, Wo - x0, need, mg, relu, px, kb, lane)
+#define PNX_ROWS_S2(N_) conv_rows_s2<(N_ <= NRMAX ? N_ : NRMAX), CIN, COUT, MB, NP>(s_in, x, x2, x3, wfrag, wfrag2, wfrag3, bias, rbase, rmask, yrow, b, H, W, iy0, ix0, Wo - x0, need, mg, relu, px, kb, lane)
     switch (nr) {  // wave-uniform; every case runs the same barriers
       case 0: PNX_ROWS_S2(0); break;
       case 1: PNX_ROWS_S2(1); break;
@@ -1303,13 +1317,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restric
   sched_done(slot);
 }
 
-template <int CIN, int COUT, bool X3 = false>
+template <int CIN, int COUT, int NP = 1>
 int launch_s2(const void* x, const void* wfrag, const float* bias, const uint8_t* mask, void* y, int B, int H, int W, int Ho, int Wo, int relu,
-              uint8_t* row_dirty, hipStream_t st, const void* x2 = nullptr, const void* wfrag2 = nullptr) {
+              uint8_t* row_dirty, hipStream_t st, const void* x2 = nullptr, const void* wfrag2 = nullptr, const void* x3 = nullptr, const void* wfrag3 = nullptr) {
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   int64_t nb = (int64_t)B * ((Ho + S2_TH - 1) / S2_TH) * ((Wo + 31) / 32);
   if (nb > 512) nb = 512;  // resident workgroups: 2 per CU (LDS and registers)
-  auto kern = k_conv3x3_s2<CIN, COUT, X3>;
+  auto kern = k_conv3x3_s2<CIN, COUT, NP>;
   constexpr int lds = S2_NSTAGE * 16;
   static bool attr_done = false;
   if (!attr_done) {
@@ -1317,7 +1331,7 @@ int launch_s2(const void* x, const void* wfrag, const float* bias, const uint8_t
     attr_done = true;
   }
   kern<<<(unsigned)nb, 256, lds, st>>>((const uint16_t*)x, (const uint16_t*)x2, (const uint4*)wfrag, (const uint4*)wfrag2, bias, mask, (uint16_t*)y, B, H, W, Ho,
-                                       Wo, relu, row_dirty, slot);
+                                       Wo, relu, row_dirty, slot, (const uint16_t*)x3, (const uint4*)wfrag3);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
@@ -1717,9 +1731,9 @@ int pnx_conv3x3_dgrad_s2_bf16(const void* g, const void* wfrag_t, const uint8_t*
   PNX_REQUIRE(g && wfrag_t && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_dgrad_s2_bf16: bad arguments");
   PNX_REQUIRE((((uintptr_t)g | (uintptr_t)wfrag_t | (uintptr_t)dx) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
   hipStream_t st = (hipStream_t)stream;
-  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, false>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
-  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, false>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
-  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, false>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
+  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
+  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
+  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
   pnx_set_error("pnx_conv3x3_dgrad_s2_bf16: no kernel for %d -> %d channels", cin, cout);
   return PNX_ERR_UNSUPPORTED;
 }
@@ -1731,10 +1745,25 @@ int pnx_conv3x3_dgrad_s2_x3(const void* g_hi, const void* g_lo, const void* wfra
   PNX_REQUIRE((((uintptr_t)g_hi | (uintptr_t)g_lo | (uintptr_t)wfrag_t_hi | (uintptr_t)wfrag_t_lo | (uintptr_t)dx) & 15) == 0, PNX_ERR_INVALID,
               "16-byte alignment required");
   hipStream_t st = (hipStream_t)stream;
-  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, true>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
-  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, true>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
-  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, true>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
+  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
+  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
+  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
   pnx_set_error("pnx_conv3x3_dgrad_s2_x3: no kernel for %d -> %d channels", cin, cout);
+  return PNX_ERR_UNSUPPORTED;
+}
+
+// Three bf16 pieces of g and of the weights (pnx_split3_f32), six products, fp32 out: the stride-2 companion of pnx_conv3x3_x6.
+int pnx_conv3x3_dgrad_s2_x6(const void* g_hi, const void* g_mid, const void* g_lo, const void* wfrag_t_hi, const void* wfrag_t_mid, const void* wfrag_t_lo,
+                            const uint8_t* mask_in, float* dx, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, pnx_stream_t stream) {
+  PNX_REQUIRE(g_hi && g_mid && g_lo && wfrag_t_hi && wfrag_t_mid && wfrag_t_lo && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID,
+              "pnx_conv3x3_dgrad_s2_x6: bad arguments");
+  PNX_REQUIRE((((uintptr_t)g_hi | (uintptr_t)g_mid | (uintptr_t)g_lo | (uintptr_t)wfrag_t_hi | (uintptr_t)wfrag_t_mid | (uintptr_t)wfrag_t_lo | (uintptr_t)dx) & 15) == 0,
+              PNX_ERR_INVALID, "16-byte alignment required");
+  hipStream_t st = (hipStream_t)stream;
+  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
+  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
+  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
+  pnx_set_error("pnx_conv3x3_dgrad_s2_x6: no kernel for %d -> %d channels", cin, cout);
   return PNX_ERR_UNSUPPORTED;
 }
 
@@ -1756,11 +1785,39 @@ int pnx_conv3x3_x3(const void* x_hi, const void* x_lo, const void* wfrag_hi, con
     if (cin == 256 && cout == 256) return launch_pc_x3<256, 256>(x_hi, x_lo, wfrag_hi, wfrag_lo, bias, mask, y, batch, h, w, st);
   } else {
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    if (cin == 64 && cout == 128) return launch_s2<64, 128, true>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
-    if (cin == 128 && cout == 256) return launch_s2<128, 256, true>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
-    if (cin == 256 && cout == 256) return launch_s2<256, 256, true>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
+    if (cin == 64 && cout == 128) return launch_s2<64, 128, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
+    if (cin == 128 && cout == 256) return launch_s2<128, 256, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
+    if (cin == 256 && cout == 256) return launch_s2<256, 256, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
   }
   pnx_set_error("pnx_conv3x3_x3: no kernel for %d -> %d channels, stride %d", cin, cout, stride);
+  return PNX_ERR_UNSUPPORTED;
+}
+
+// fp32 convolution out of six bf16 products: x = x_hi + x_mid + x_lo and W = W_hi + W_mid + W_lo (pnx_split3_f32, exact for |x| >= 2^-100), y = the
+// products of piece orders 0..2 (hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi; the dropped mid.lo, lo.mid, lo.lo are ~2^-23 of sum |x||W|, fp32's own
+// rounding) accumulated in fp32 inside ONE launch, low-order products first and hi.hi last.  Otherwise exactly pnx_conv3x3_x3: shapes, mask, bias, output.
+int pnx_conv3x3_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* wfrag_hi, const void* wfrag_mid, const void* wfrag_lo, const float* bias,
+                   const uint8_t* mask, float* y, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream) {
+  PNX_REQUIRE(x_hi && x_mid && x_lo && wfrag_hi && wfrag_mid && wfrag_lo && y, PNX_ERR_INVALID, "null pointer");
+  PNX_REQUIRE(batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "bad shape");
+  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
+  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_mid | (uintptr_t)x_lo | (uintptr_t)y | (uintptr_t)wfrag_hi | (uintptr_t)wfrag_mid | (uintptr_t)wfrag_lo |
+                (uintptr_t)bias) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  hipStream_t st = (hipStream_t)stream;
+  if (stride == 1) {
+    if (cin == 64 && cout == 64) return launch_pc_x6<64, 64>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
+    if (cin == 128 && cout == 128) return launch_pc_x6<128, 128>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
+    if (cin == 256 && cout == 256) return launch_pc_x6<256, 256>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
+  } else {
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    if (cin == 64 && cout == 128)
+      return launch_s2<64, 128, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
+    if (cin == 128 && cout == 256)
+      return launch_s2<128, 256, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
+    if (cin == 256 && cout == 256)
+      return launch_s2<256, 256, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
+  }
+  pnx_set_error("pnx_conv3x3_x6: no kernel for %d -> %d channels, stride %d", cin, cout, stride);
   return PNX_ERR_UNSUPPORTED;
 }
 #endif

@@ -11,10 +11,11 @@
 //             (3 rows x 2 column offsets), 9 weight fragments (one per tap, from the TRANSPOSED pack pnx_conv3x3_pack_weights(transposed=1): M = ci, K = co,
 //             tap index (2 - ky) * 3 + (2 - kx)) and 18 MFMAs; 8 waves = (TG / 2) row pairs x (8 / (TG / 2)) channel tiles = all of CI
 //   epilogue  pack_tile (8 consecutive channels per lane), zeros at inactive input sites, 16-byte stores (fp32 out for the three-product form)
-// X3: the fp32 graph's form (pnx_conv3x3_x3's companion): g = g_hi + g_lo, W = W_hi + W_lo; the tile of g_hi runs with both weight halves, then the tile of
-// g_lo with W_hi, the accumulators running through; fp32 output.
+// NP = bf16 pieces per operand.  2 (X3): the fp32 graph's form (pnx_conv3x3_x3's companion): g = g_hi + g_lo, W = W_hi + W_lo; the tile of g_hi runs with
+// both weight halves, then the tile of g_lo with W_hi, the accumulators running through; fp32 output.  3 (pnx_conv3x3_x6's companion): the tiles of g_lo
+// (with W_hi), g_mid (W_mid, W_hi) and g_hi (W_lo, W_mid, W_hi) in that order, hi x hi last; fp32 output.
 
-template <int CO, int CI, bool X3>
+template <int CO, int CI, int NP>
 struct Dg2Geo {
   static constexpr int MT = CI / 32;             // 32-channel tiles of dx
   static constexpr int NRP = 8 / MT;             // row pairs per tile (8 waves)
@@ -26,11 +27,12 @@ struct Dg2Geo {
   static_assert(MT == 2 || MT == 4 || MT == 8, "CI = 64, 128 or 256");
 };
 
-template <int CO, int CI, bool X3>
+template <int CO, int CI, int NP>
 __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict__ g, const uint16_t* __restrict__ g2, const uint4* __restrict__ wt,
                                                      const uint4* __restrict__ wt2, const uint8_t* __restrict__ mask_in, void* __restrict__ dx, int B, int H, int W,
-                                                     int Ho, int Wo, int slot) {
-  using G = Dg2Geo<CO, CI, X3>;
+                                                     int Ho, int Wo, int slot, const uint16_t* __restrict__ g3 = nullptr, const uint4* __restrict__ wt3 = nullptr) {
+  using G = Dg2Geo<CO, CI, NP>;
+  constexpr bool X3 = NP == 2, F32 = NP > 1;
   constexpr int MT = G::MT, NRP = G::NRP, TG = G::TG, NSLAB = G::NSLAB, CB = CO / 16;
   extern __shared__ uint4 s_g[];  // [slab][row 0..TG][col 0..33][8 chunks]
   __shared__ unsigned int s_next[2];
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
     next = sched_next(s_next, it, slot, tile);
     const bool live = s_any != 0u;
     if (!live) {  // no active input site: the gradient is not needed here -- zeros (every site of dx is written)
-      constexpr int ESZ = X3 ? 4 : 2;
+      constexpr int ESZ = F32 ? 4 : 2;
       const int rows = min(2 * TG, H - 2 * a0), cols = min(64, W - 2 * b0);
       const int row_bytes = cols * CI * ESZ;
       for (int r = wv; r < rows; r += 8) {
@@ -86,8 +88,9 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
         for (int i = 0; i < 16; i++) acc[j][p][i] = 0.f;
 
 #pragma unroll 1
-    for (int src = 0; src < (X3 ? 2 : 1); src++) {
+    for (int src = 0; src < NP; src++) {
       const uint16_t* gs = src == 0 ? g : g2;
+      if constexpr (NP == 3) gs = src == 0 ? g3 : src == 1 ? g2 : g;  // g_lo, g_mid, g_hi
       if (src) __syncthreads();  // the first image has been consumed
       // ---- stage the g halo tile: rows a0 .. a0 + TG, columns b0 .. b0 + 32, all CO channels; zeros outside the map
       constexpr int NCH = (TG + 1) * 33 * (CO / 8);
@@ -113,9 +116,12 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
             q[r][d] = __builtin_bit_cast(el8, sb[r * G::ROW_N + c * 8 + ((2 * cbl + kb) ^ lds_swz(c))]);
           }
 #pragma unroll
-        for (int half = 0; half < (X3 ? 2 : 1); half++) {
+        for (int half = 0; half < NP; half++) {
           if (X3 && half == 1 && src == 1) break;  // g_lo runs with W_hi only
-          const uint4* wp = (half == 0 ? wt : wt2) + ((int64_t)ks * MT + mt) * 64 + lane;
+          if (NP == 3 && half > src) break;        // piece 2 - src of g with W pieces src .. 0
+          const uint4* wsel = half == 0 ? wt : wt2;
+          if constexpr (NP == 3) wsel = src - half == 0 ? wt : src - half == 1 ? wt2 : wt3;
+          const uint4* wp = wsel + ((int64_t)ks * MT + mt) * 64 + lane;
           el8 w[9];  // by (ky, kx): fragment of tap (2 - ky) * 3 + (2 - kx) of the transposed pack
 #pragma unroll
           for (int k = 0; k < 9; k++) w[k] = __builtin_bit_cast(el8, wp[(int64_t)(8 - k) * CB * MT * 64]);
@@ -147,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
         const int iy = 2 * a + (p >> 1), ix = 2 * (b0 + px) + (p & 1);
         const bool inb = iy < H && ix < W;
         const bool act = inb && mask_in[((int64_t)b * H + iy) * W + ix] != 0;
-        if constexpr (X3) {
+        if constexpr (F32) {
           float* row = reinterpret_cast<float*>(dx) + (((int64_t)b * H + iy) * W + ix) * CI + mt * 32 + 4 * kb;
           if (inb) {
 #pragma unroll
@@ -172,21 +178,23 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
   sched_done(slot);
 }
 
-template <int CO, int CI, bool X3>
-int launch_dgrad_s2(const void* g, const void* g2, const void* wt, const void* wt2, const uint8_t* mask_in, void* dx, int B, int H, int W, hipStream_t st) {
-  using G = Dg2Geo<CO, CI, X3>;
+template <int CO, int CI, int NP>
+int launch_dgrad_s2(const void* g, const void* g2, const void* wt, const void* wt2, const uint8_t* mask_in, void* dx, int B, int H, int W, hipStream_t st,
+                    const void* g3 = nullptr, const void* wt3 = nullptr) {
+  using G = Dg2Geo<CO, CI, NP>;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   int64_t nb = (int64_t)B * ((Ho + G::TG - 1) / G::TG) * ((Wo + 31) / 32);
   const int per_cu = G::LDS_BYTES <= 75 * 1024 ? 2 : 1;
   if (nb > 256 * per_cu) nb = 256 * per_cu;
-  auto kern = k_dgrad_s2<CO, CI, X3>;
+  auto kern = k_dgrad_s2<CO, CI, NP>;
   static bool attr_done = false;
   if (!attr_done) {
     PNX_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
     attr_done = true;
   }
   const int slot = next_sched_slot();
-  kern<<<(unsigned)nb, 512, G::LDS_BYTES, st>>>((const uint16_t*)g, (const uint16_t*)g2, (const uint4*)wt, (const uint4*)wt2, mask_in, dx, B, H, W, Ho, Wo, slot);
+  kern<<<(unsigned)nb, 512, G::LDS_BYTES, st>>>((const uint16_t*)g, (const uint16_t*)g2, (const uint4*)wt, (const uint4*)wt2, mask_in, dx, B, H, W, Ho, Wo, slot,
+                                                (const uint16_t*)g3, (const uint4*)wt3);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -46,11 +46,13 @@ __device__ __forceinline__ void pc_barrier_all() { asm volatile("s_waitcnt vmcnt
 
 // Everything a consumer wave does for one tile: NPASS passes (CIN = 64: over the one fill; otherwise over NSLAB fills each), every fill closed
 // by pc_barrier_lds().  NR = 0: the wave has no row in this tile and only keeps the barrier count.
-// X3: the fp32 product from bf16 pairs (pnx_conv3x3_x3): the fills alternate between the tensor of high halves (taps with W_hi, then with W_lo) and the
-// tensor of low halves (taps with W_hi); no bias, no ReLU, and the accumulators go out as fp32.
-template <int NR, int CIN, int COUT, bool HAS_RES, int NRG, int NSLOT, int SLOT_N, bool X3 = false>
+// NP = bf16 pieces per operand.  1: the bf16 convolution.  2 (pnx_conv3x3_x3, the fp32 product from bf16 pairs): the fills alternate between the tensor of
+// high halves (taps with W_hi, then with W_lo) and the tensor of low halves (taps with W_hi).  3 (pnx_conv3x3_x6, three pieces): the fills of a pass run
+// x_lo (taps with W_hi), x_mid (W_mid, then W_hi), x_hi (W_lo, W_mid, then W_hi) -- six products, the low-order ones first and hi x hi last in the
+// accumulators' life.  NP > 1: wfrag / wfrag2 / wfrag3 = W_hi / W_lo (NP 2) or W_hi / W_mid / W_lo (NP 3); no bias, no ReLU, fp32 accumulators out.
+template <int NR, int CIN, int COUT, bool HAS_RES, int NRG, int NSLOT, int SLOT_N, int NP = 1>
 __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g, const uint4* __restrict__ wfrag, const uint4* __restrict__ wfrag2,
-                                        const float* __restrict__ bias,
+                                        const uint4* __restrict__ wfrag3, const float* __restrict__ bias,
                                         const uint16_t* __restrict__ res_t, uint16_t* __restrict__ y_t, const int (&rrow)[4], const uint32_t (&rmask)[4],
                                         int W, int n_valid, int cg, int relu, int px, int kb, int lane
 #ifdef PNX_CONV_TIMERS
@@ -59,6 +61,7 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
 ) {
   constexpr int NCG = 8 / NRG, PASS_C = NCG * 32, NPASS = COUT / PASS_C, NSLAB = CIN / 64, NRA = NR > 0 ? NR : 1;
   constexpr int MTALL = COUT / 32, CB = CIN / 16;
+  constexpr bool X3 = NP == 2, F32 = NP > 1;
   int rbase[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) rbase[j] = rrow[j] * LDS_HW * 8;
@@ -69,7 +72,7 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
     v16f acc[NRA][1];
     if (NR > 0) {
       v16f bq;
-      if (X3 && bias == nullptr) {
+      if (F32 && bias == nullptr) {
 #pragma unroll
         for (int i = 0; i < 16; i++) bq[i] = 0.f;
       } else {
@@ -80,8 +83,8 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
     }
     uint4 rq[2];
 #pragma unroll 1
-    for (int sq = 0; sq < NSLAB * (X3 ? 2 : 1); sq++) {
-      const int sl = X3 ? sq % NSLAB : sq;
+    for (int sq = 0; sq < NSLAB * NP; sq++) {
+      const int sl = F32 ? sq % NSLAB : sq;
       if (NR > 0) {
         if (HAS_RES && sl == NSLAB - 1) {  // residual lines of row 0: requested before the last slab's taps, arrive under them
           const bool a0 = (rmask[0] >> px) & 1u;
@@ -92,13 +95,21 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
             if (a0) rq[t] = *reinterpret_cast<const uint4*>(rp + 32 * t);
           }
         }
-        conv_taps<NRA, MTALL, CB, 1, 1>(acc, s_ring + (g % NSLOT) * SLOT_N, wfrag, rbase, mt, px, kb, lane, 4 * sl);
-        if constexpr (X3) {
-          if (sq < NSLAB) conv_taps<NRA, MTALL, CB, 1, 1>(acc, s_ring + (g % NSLOT) * SLOT_N, wfrag2, rbase, mt, px, kb, lane, 4 * sl);
+        if constexpr (NP == 3) {
+          // fill q of the pass holds piece 2 - q of x (lo, mid, hi): taps with W pieces q .. 0 (rolled: one inlined tap loop)
+          const int q = sq / NSLAB;
+#pragma unroll 1
+          for (int k = q; k >= 0; k--)
+            conv_taps<NRA, MTALL, CB, 1, 1>(acc, s_ring + (g % NSLOT) * SLOT_N, k == 0 ? wfrag : k == 1 ? wfrag2 : wfrag3, rbase, mt, px, kb, lane, 4 * sl);
+        } else {
+          conv_taps<NRA, MTALL, CB, 1, 1>(acc, s_ring + (g % NSLOT) * SLOT_N, wfrag, rbase, mt, px, kb, lane, 4 * sl);
+          if constexpr (X3) {
+            if (sq < NSLAB) conv_taps<NRA, MTALL, CB, 1, 1>(acc, s_ring + (g % NSLOT) * SLOT_N, wfrag2, rbase, mt, px, kb, lane, 4 * sl);
+          }
         }
       }
       PC_TOCK(1)
-      if (X3 || NSLAB > 1 || pass == NPASS - 1) {
+      if (F32 || NSLAB > 1 || pass == NPASS - 1) {
         pc_barrier_lds();
         g++;
       }
@@ -108,7 +119,7 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
 #pragma unroll
       for (int j = 0; j < NR; j++) {
         const bool act = (rmask[j] >> px) & 1u;
-        if constexpr (X3) {
+        if constexpr (F32) {
           store_tile_f32<COUT>(acc[j][0], act, reinterpret_cast<float*>(y_t) + ((int64_t)rrow[j] * W) * COUT + mt * 32, n_valid, px, kb);
           continue;
         }
@@ -137,18 +148,21 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
   }
 }
 
-template <int CIN, int COUT, bool HAS_RES, bool X3 = false>
+// NP > 1 (see pc_rows): x / x2 / x3 = x_hi / x_lo (NP 2) or x_hi / x_mid / x_lo (NP 3), wfrag* likewise; y is fp32.
+template <int CIN, int COUT, bool HAS_RES, int NP = 1>
 __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, const uint4* __restrict__ wfrag,
                                                        const uint4* __restrict__ wfrag2, const float* __restrict__ bias,
                                                        const uint16_t* __restrict__ res, const uint8_t* __restrict__ mask, uint16_t* __restrict__ y,
                                                        int B, int H, int W, int relu, uint8_t* __restrict__ row_dirty, int slot,
-                                                       const int32_t* __restrict__ tlist, const int32_t* __restrict__ tcount) {
+                                                       const int32_t* __restrict__ tlist, const int32_t* __restrict__ tcount,
+                                                       const uint16_t* __restrict__ x3 = nullptr, const uint4* __restrict__ wfrag3 = nullptr) {
+  constexpr bool X3 = NP == 2, F32 = NP > 1;
   constexpr int TH = CIN == 64 ? 16 : 8;
   constexpr int NRG = TH / 4, NCG = 8 / NRG, PASS_C = NCG * 32, NPASS = COUT / PASS_C, NSLAB = CIN / 64;
   constexpr int NSLOT = CIN == 64 ? 2 : 3, DEPTH = NSLOT - 1;
-  constexpr int NFILL = X3 ? NPASS * NSLAB * 2 : CIN == 64 ? 1 : NPASS * NSLAB;  // fills per tile with an active site
-  constexpr int YS = X3 ? 2 : 1;                                                 // output element in units of uint16_t
-  static_assert(!X3 || (!HAS_RES && (CIN > 64 || NPASS == 1)), "fp32 product: no residual; one pass when the tile is filled once per source");
+  constexpr int NFILL = F32 ? NPASS * NSLAB * NP : CIN == 64 ? 1 : NPASS * NSLAB;  // fills per tile with an active site
+  constexpr int YS = F32 ? 2 : 1;                                                  // output element in units of uint16_t
+  static_assert(!F32 || (!HAS_RES && (CIN > 64 || NPASS == 1)), "fp32 product: no residual; one pass when the tile is filled once per source");
   constexpr int SLOT_N = (TH + 2) * LDS_HW * 8;
   static_assert(COUT % PASS_C == 0 && CIN % 64 == 0, "passes of NCG x 32 output channels over 64-channel input slabs");
   __shared__ uint4 s_ring[NSLOT * SLOT_N];
@@ -275,7 +289,12 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       if (am != 0) {
         const int sl = f % NSLAB;
         uint4* dstslot = s_ring + (g % NSLOT) * SLOT_N;
-        const uint16_t* xs = X3 && (f / NSLAB) % 2 == 1 ? x2 : x;  // fp32 product: per pass the NSLAB slabs of the high halves, then those of the low halves
+        // fp32 product: per pass the NSLAB slabs of the high halves, then those of the low halves (NP 2); of x_lo, x_mid, then x_hi (NP 3)
+        const uint16_t* xs = X3 && (f / NSLAB) % 2 == 1 ? x2 : x;
+        if constexpr (NP == 3) {
+          const int q = (f / NSLAB) % 3;
+          xs = q == 0 ? x3 : q == 1 ? x2 : x;
+        }
         const uint16_t* xt = xs + (((int64_t)cb * H + (cy0 - 1)) * W + (cx0 - 1)) * CIN + 64 * sl;  // element (0, 0) of the halo tile
         bool col_ok[5];
 #pragma unroll
@@ -355,9 +374,9 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
     const int n_valid = W - x0;
     PC_TOCK(0)
 #ifdef PNX_CONV_TIMERS
-#define PC_ROWS(N_) pc_rows<N_, CIN, COUT, HAS_RES, NRG, NSLOT, SLOT_N, X3>(s_ring, g, wfrag, wfrag2, bias, res_t, y_t, rrow, rmask, W, n_valid, cg, relu, px, kb, lane, pc_T, pc_tk)
+#define PC_ROWS(N_) pc_rows<N_, CIN, COUT, HAS_RES, NRG, NSLOT, SLOT_N, NP>(s_ring, g, wfrag, wfrag2, wfrag3, bias, res_t, y_t, rrow, rmask, W, n_valid, cg, relu, px, kb, lane, pc_T, pc_tk)
 #else
-#define PC_ROWS(N_) pc_rows<N_, CIN, COUT, HAS_RES, NRG, NSLOT, SLOT_N, X3>(s_ring, g, wfrag, wfrag2, bias, res_t, y_t, rrow, rmask, W, n_valid, cg, relu, px, kb, lane)
+#define PC_ROWS(N_) pc_rows<N_, CIN, COUT, HAS_RES, NRG, NSLOT, SLOT_N, NP>(s_ring, g, wfrag, wfrag2, wfrag3, bias, res_t, y_t, rrow, rmask, W, n_valid, cg, relu, px, kb, lane)
 #endif
     switch (nr) {  // wave-uniform; every case runs the same barriers
       case 0: PC_ROWS(0); break;
@@ -397,8 +416,24 @@ int launch_pc_x3(const void* x_hi, const void* x_lo, const void* w_hi, const voi
   int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
   if (nb > 256) nb = 256;
   const int slot = mask != nullptr ? next_sched_slot() : -1;
-  k_conv3x3_pc<CIN, COUT, false, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x_hi, (const uint16_t*)x_lo, (const uint4*)w_hi, (const uint4*)w_lo,
-                                                                     bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr);
+  k_conv3x3_pc<CIN, COUT, false, 2><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x_hi, (const uint16_t*)x_lo, (const uint4*)w_hi, (const uint4*)w_lo,
+                                                                  bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+// Three pieces per operand (pnx_conv3x3_x6): x = x_hi + x_mid + x_lo, W likewise, y = hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi (x.W) in one
+// launch, hi.hi last, fp32 out.  Same launch shape as launch_pc_x3; 1.5 x its fills, 2 x its MFMAs.
+template <int CIN, int COUT>
+int launch_pc_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* w_hi, const void* w_mid, const void* w_lo, const float* bias,
+                 const uint8_t* mask, float* y, int B, int H, int W, hipStream_t st) {
+  constexpr int TH = CIN == 64 ? 16 : 8;
+  int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
+  if (nb > 256) nb = 256;
+  const int slot = mask != nullptr ? next_sched_slot() : -1;
+  k_conv3x3_pc<CIN, COUT, false, 3><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x_hi, (const uint16_t*)x_mid, (const uint4*)w_hi, (const uint4*)w_mid,
+                                                                  bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr,
+                                                                  (const uint16_t*)x_lo, (const uint4*)w_lo);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

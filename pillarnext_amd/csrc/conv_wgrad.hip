@@ -104,12 +104,27 @@ __device__ __forceinline__ void tile_store(const TileRegs<S>& R, uint8_t* sx, ui
   }
 }
 
-// X3 (pnx_conv3x3_wgrad_x3: the fp32 weight gradient from the operands' bf16 halves): every listed tile is visited three times, the accumulators running
-// through -- X = x_lo, Y = dy_hi;  then X = x_hi (Y stays in LDS);  then Y = dy_lo (X stays) -- four operand tiles from HBM for the three products.
-template <int S, bool X3 = false>
+// Visit v of a tile in the three-piece form (k_wgrad64<S, 3>): phase v % 6 stages (x_lo, dy_hi) (x_mid, -) (-, dy_mid) (x_hi, -) (-, dy_lo) (-, dy_hi).
+template <int S>
+__device__ __forceinline__ void wg_load6(TileRegs<S>& R, int v, int tile, const uint16_t* x_hi, const uint16_t* x_mid, const uint16_t* x_lo, const uint16_t* dy_hi,
+                                         const uint16_t* dy_mid, const uint16_t* dy_lo, const uint8_t* mask, int tiles_x, int tiles_y, int H, int W, int Ho, int Wo,
+                                         int cin, int cout, int cb, int ib, int t) {
+  const int ph = v % 6;
+  const uint16_t* xs = ph == 0 ? x_lo : ph < 3 ? x_mid : x_hi;
+  const uint16_t* ys = ph < 2 || ph == 5 ? dy_hi : ph < 4 ? dy_mid : dy_lo;
+  tile_load<S>(R, xs, ys, mask, tile, tiles_x, tiles_y, H, W, Ho, Wo, cin, cout, cb, ib, t, ph == 0 || ph == 1 || ph == 3, ph != 1 && ph != 3);
+}
+
+// NP = bf16 pieces per operand.  2 (X3, pnx_conv3x3_wgrad_x3: the fp32 weight gradient from the operands' bf16 halves): every listed tile is visited three
+// times, the accumulators running through -- X = x_lo, Y = dy_hi;  then X = x_hi (Y stays in LDS);  then Y = dy_lo (X stays) -- four operand tiles from
+// HBM for the three products.  3 (pnx_conv3x3_wgrad_x6, three pieces): six visits, one LDS tile changing per visit and hi x hi last --
+// (x_lo, dy_hi) (x_mid, dy_hi) (x_mid, dy_mid) (x_hi, dy_mid) (x_hi, dy_lo) (x_hi, dy_hi) -- seven operand tiles for the six products.
+template <int S, int NP = 1>
 __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint8_t* __restrict__ mask,
                                                     float* __restrict__ part, int B, int H, int W, int Ho, int Wo, int cin, int cout, int G,
-                                                    const uint16_t* __restrict__ x_lo = nullptr, const uint16_t* __restrict__ dy_lo = nullptr) {
+                                                    const uint16_t* __restrict__ x_lo = nullptr, const uint16_t* __restrict__ dy_lo = nullptr,
+                                                    const uint16_t* __restrict__ x_mid = nullptr, const uint16_t* __restrict__ dy_mid = nullptr) {
+  constexpr bool X3 = NP == 2;
   using Geo = WgGeo<S>;
   constexpr int TH = Geo::TH, XW = Geo::XW;
   extern __shared__ __align__(16) uint8_t s_tile[];  // X halo tile, the dY tile, the workgroup's list of non-empty tiles (no static LDS in front: the base stays 16-byte aligned)
@@ -175,20 +190,27 @@ __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__
   const int n_mine = min(s_list[0], WG_LIST_MAX);
   // ---- software pipeline over the non-empty tiles: the operands of tile k + 1 travel HBM -> registers while the K steps of tile k run
   TileRegs<S> R;
-  constexpr int NV = X3 ? 3 : 1;  // visits per tile
+  constexpr int NV = NP == 3 ? 6 : X3 ? 3 : 1;  // visits per tile
+  // which visits stage a new X tile and which a new dY tile (NP 3: X at 0, 1, 3; dY at 0, 2, 4, 5 -- wg_load6)
+  auto new_x = [&](int ph) { return NP == 3 ? ph == 0 || ph == 1 || ph == 3 : !X3 || ph != 2; };
+  auto new_y = [&](int ph) { return NP == 3 ? ph != 1 && ph != 3 : !X3 || ph != 1; };
   auto visit_load = [&](int v) {
     const int ph = X3 ? v % 3 : 0;
     tile_load<S>(R, X3 && ph == 0 ? x_lo : x, X3 && ph == 2 ? dy_lo : dy, mask, s_list[1 + v / NV], tiles_x, tiles_y, H, W, Ho, Wo, cin, cout, cb, ib, t,
-                 !X3 || ph != 2, !X3 || ph != 1);
+                 new_x(ph), new_y(ph));
   };
-  if (n_mine > 0) visit_load(0);
+  // NP 3: wg_load6 (the six operand pointers captured by the lambda kept it, and R, in scratch)
+#define PNX_WG_LOAD(V_) \
+  if constexpr (NP == 3) wg_load6<S>(R, V_, s_list[1 + (V_) / NV], x, x_mid, x_lo, dy, dy_mid, dy_lo, mask, tiles_x, tiles_y, H, W, Ho, Wo, cin, cout, cb, ib, t); \
+  else visit_load(V_);
+  if (n_mine > 0) { PNX_WG_LOAD(0) }
   for (int v = 0; v < NV * n_mine; v++) {
-    const int k = v / NV, ph = X3 ? v % 3 : 0;
+    const int k = v / NV, ph = NV > 1 ? v % NV : 0;
     uint32_t* rm = s_rm + 4 * (k & 1);  // the tile's row masks: set by the visits that stage dY (the same bits each time)
-    tile_store<S>(R, sx, sy, rm, t, !X3 || ph != 2, !X3 || ph != 1);
+    tile_store<S>(R, sx, sy, rm, t, new_x(ph), new_y(ph));
     __syncthreads();
     if (t < 4 && ph == NV - 1) s_rm[4 * ((k + 1) & 1) + t] = 0u;  // the next tile's set: its writers come behind this iteration's last barrier
-    if (v + 1 < NV * n_mine) visit_load(v + 1);
+    if (v + 1 < NV * n_mine) { PNX_WG_LOAD(v + 1) }
 #pragma unroll 1
     for (int ks = 0; ks < 2 * TH; ks++) {  // rolled: unrolled, the steps' reads are hoisted and the accumulators spill
       const int r = ks >> 1, hs = ks & 1;
@@ -201,6 +223,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__
     }
     __syncthreads();  // the next tile overwrites the LDS image
   }
+#undef PNX_WG_LOAD
   // ---- the workgroup's partial: [pair][group][tap][64 co][64 ci] fp32; D[m][n]: m = (i & 3) + 8 (i >> 2) + 4 (l >> 5), n = l & 31
   float* out = part + ((int64_t)pair * G + blockIdx.x) * 9 * 4096;
 #pragma unroll
@@ -275,9 +298,9 @@ extern "C" size_t pnx_conv3x3_wgrad_workspace_bytes(int32_t cin, int32_t cout) {
   return (size_t)(cin >> 6) * (cout >> 6) * groups_per_pair(cin, cout) * 9 * 4096 * sizeof(float) + 256;
 }
 
-template <int S, bool X3 = false>
+template <int S, int NP = 1>
 int launch_wgrad(const void* x, const void* dy, const uint8_t* mask, float* dw, int batch, int h, int w, int cin, int cout, void* workspace, hipStream_t st,
-                 const void* x_lo = nullptr, const void* dy_lo = nullptr) {
+                 const void* x_lo = nullptr, const void* dy_lo = nullptr, const void* x_mid = nullptr, const void* dy_mid = nullptr) {
   using Geo = WgGeo<S>;
   const int ho = (h - 1) / S + 1, wo = (w - 1) / S + 1;
   const int G = groups_per_pair(cin, cout), n_pairs = (cin >> 6) * (cout >> 6);
@@ -286,11 +309,12 @@ int launch_wgrad(const void* x, const void* dy, const uint8_t* mask, float* dw, 
               (long long)n_tiles, G, WG_LIST_MAX);
   static bool attr_done = false;
   if (!attr_done) {
-    PNX_CHECK_HIP(hipFuncSetAttribute((const void*)k_wgrad64<S, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS));
+    PNX_CHECK_HIP(hipFuncSetAttribute((const void*)k_wgrad64<S, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS));
     attr_done = true;
   }
-  k_wgrad64<S, X3><<<dim3((unsigned)G, (unsigned)n_pairs), 256, Geo::LDS, st>>>((const uint16_t*)x, (const uint16_t*)dy, mask, (float*)workspace, batch, h, w, ho,
-                                                                                 wo, cin, cout, G, (const uint16_t*)x_lo, (const uint16_t*)dy_lo);
+  k_wgrad64<S, NP><<<dim3((unsigned)G, (unsigned)n_pairs), 256, Geo::LDS, st>>>((const uint16_t*)x, (const uint16_t*)dy, mask, (float*)workspace, batch, h, w, ho,
+                                                                                 wo, cin, cout, G, (const uint16_t*)x_lo, (const uint16_t*)dy_lo,
+                                                                                 (const uint16_t*)x_mid, (const uint16_t*)dy_mid);
   PNX_LAUNCH_CHECK();
   k_wgrad_reduce<<<(unsigned)((n_pairs * 9 * 4096 + 31) / 32), 256, 0, st>>>((const float*)workspace, dw, cin, cout, G);
   PNX_LAUNCH_CHECK();
@@ -335,6 +359,24 @@ extern "C" int pnx_conv3x3_wgrad_x3(const void* x_hi, const void* x_lo, const vo
               "16-byte alignment required");
   PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) return launch_wgrad<1, true>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
-  return launch_wgrad<2, true>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
+  if (stride == 1) return launch_wgrad<1, 2>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
+  return launch_wgrad<2, 2>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
+}
+
+// fp32 weight gradient from three bf16 pieces of x and of the upstream gradient (pnx_split3_f32): the six products of piece orders 0..2 in ONE pass over the
+// tiles (k_wgrad64<S, 3>: six visits per tile, hi x hi last), fp32 accumulation, deterministic.  Same shapes, mask and workspace as pnx_conv3x3_wgrad_bf16.
+extern "C" int pnx_conv3x3_wgrad_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* dy_hi, const void* dy_mid, const void* dy_lo,
+                                    const uint8_t* mask, float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride,
+                                    void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
+  PNX_REQUIRE(x_hi && x_mid && x_lo && dy_hi && dy_mid && dy_lo && mask && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID,
+              "pnx_conv3x3_wgrad_x6: bad arguments");
+  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
+  PNX_REQUIRE(cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0 && cin <= 512 && cout <= 512, PNX_ERR_UNSUPPORTED,
+              "weight gradient for %d -> %d channels (multiples of 64 up to 512)", cin, cout);
+  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_mid | (uintptr_t)x_lo | (uintptr_t)dy_hi | (uintptr_t)dy_mid | (uintptr_t)dy_lo | (uintptr_t)workspace) & 15) == 0,
+              PNX_ERR_INVALID, "16-byte alignment required");
+  PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  if (stride == 1) return launch_wgrad<1, 3>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo, x_mid, dy_mid);
+  return launch_wgrad<2, 3>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo, x_mid, dy_mid);
 }

@@ -243,6 +243,35 @@ __global__ __launch_bounds__(256) void k_split_f32(const float4* __restrict__ x,
   }
 }
 
+// fp32 -> three bf16 pieces: hi = RNE(x), mid = RNE(x - hi), lo = RNE(x - hi - mid); both subtractions are exact in fp32 and 3 x 8 significant bits
+// cover fp32's 24, so hi + mid + lo == x for every finite x with |x| >= 2^-100 (below that lo can fall under bf16's range).  Same mask contract and
+// non-finite convention as k_split_f32 (hi = the bf16 cast; mid and lo of an inf / nan are nan).  8 values per thread: two 16-byte loads, three stores.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void k_split3_f32(const float4* __restrict__ x, uint4* __restrict__ hi, uint4* __restrict__ mid, uint4* __restrict__ lo,
+                                                    int64_t n8, const uint8_t* __restrict__ mask, int c8) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    if (MASKED && mask[i / c8] == 0) {
+      hi[i] = make_uint4(0, 0, 0, 0);
+      mid[i] = make_uint4(0, 0, 0, 0);
+      lo[i] = make_uint4(0, 0, 0, 0);
+      continue;
+    }
+    const float4 a = x[2 * i], b = x[2 * i + 1];
+    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint32_t h[8], m[8], l[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      h[k] = bf16_rne(v[k]);
+      const float r = v[k] - __uint_as_float(h[k] << 16);
+      m[k] = bf16_rne(r);
+      l[k] = bf16_rne(r - __uint_as_float(m[k] << 16));
+    }
+    hi[i] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+    mid[i] = make_uint4(m[0] | m[1] << 16, m[2] | m[3] << 16, m[4] | m[5] << 16, m[6] | m[7] << 16);
+    lo[i] = make_uint4(l[0] | l[1] << 16, l[2] | l[3] << 16, l[4] | l[5] << 16, l[6] | l[7] << 16);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,6 +287,22 @@ int pnx_split_f32(const float* x, void* hi, void* lo, int64_t n, const uint8_t* 
   if (nb > 256 * 16) nb = 256 * 16;
   if (mask != nullptr) k_split_f32<true><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((const float4*)x, (uint4*)hi, (uint4*)lo, n8, mask, channels / 8);
   else k_split_f32<false><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((const float4*)x, (uint4*)hi, (uint4*)lo, n8, nullptr, 1);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_split3_f32(const float* x, void* hi, void* mid, void* lo, int64_t n, const uint8_t* mask, int32_t channels, pnx_stream_t stream) {
+  PNX_REQUIRE(x && hi && mid && lo && n >= 0 && n % 8 == 0, PNX_ERR_INVALID, "pnx_split3_f32: null pointer or a count that is not a multiple of 8");
+  PNX_REQUIRE(mask == nullptr || (channels > 0 && channels % 8 == 0 && n % channels == 0), PNX_ERR_INVALID,
+              "pnx_split3_f32: with a mask, channels must be a multiple of 8 that divides n");
+  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)hi | (uintptr_t)mid | (uintptr_t)lo) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  if (n == 0) return PNX_OK;
+  const int64_t n8 = n / 8;
+  int64_t nb = (n8 + 255) / 256;
+  if (nb > 256 * 16) nb = 256 * 16;
+  if (mask != nullptr)
+    k_split3_f32<true><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((const float4*)x, (uint4*)hi, (uint4*)mid, (uint4*)lo, n8, mask, channels / 8);
+  else k_split3_f32<false><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((const float4*)x, (uint4*)hi, (uint4*)mid, (uint4*)lo, n8, nullptr, 1);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -348,10 +348,26 @@ class _MaskedConv3x3Fn(torch.autograd.Function):
         return dx, dw, None, None, None, db
 
 
-def _split_pack(weight, transposed=False):
-    """fp32 (Cout,Cin,3,3) -> the packed bf16 halves (W_hi, W_lo) pnx_conv3x3_x3 takes."""
-    hi, lo = ops.split_f32(weight.detach().contiguous())
-    return ops.conv3x3_pack_weights(hi, transposed=transposed), ops.conv3x3_pack_weights(lo, transposed=transposed)
+def _split_pack(weight, transposed=False, pieces=2):
+    """fp32 (Cout,Cin,3,3) -> the packed bf16 pieces pnx_conv3x3_x3 ((W_hi, W_lo), pieces=2) or pnx_conv3x3_x6 ((W_hi, W_mid, W_lo), pieces=3) takes."""
+    w = weight.detach().contiguous()
+    parts = ops.split_f32(w) if pieces == 2 else ops.split3_f32(w)
+    return tuple(ops.conv3x3_pack_weights(p, transposed=transposed) for p in parts)
+
+
+def train_f32_pieces():
+    """bf16 pieces per fp32 operand in the fp32 graph's 3x3 layers (PNX_TRAIN_F32_PIECES): 2 (default) = the three-product node, 3 = the six-product
+    form (fp32-accurate; ~2x the MFMA work of those layers).  Anything else is an error."""
+    v = os.environ.get("PNX_TRAIN_F32_PIECES", "2").strip()
+    if v not in ("2", "3"):
+        raise ops.PnxError(f"PNX_TRAIN_F32_PIECES must be 2 or 3, got {v!r}")
+    return int(v)
+
+
+def split_f32_pieces(x, mask=None, pieces=None):
+    """x split into the bf16 pieces the fp32 node uses (train_f32_pieces() unless given): ops.split_f32 (2) or ops.split3_f32 (3)."""
+    n = train_f32_pieces() if pieces is None else pieces
+    return ops.split_f32(x, mask) if n == 2 else ops.split3_f32(x, mask)
 
 
 _ONES_MASK = {}
@@ -366,28 +382,46 @@ def _ones_mask(b, h, w, device):
 
 class _MaskedConv3x3F32Fn(torch.autograd.Function):
     """_MaskedConv3x3Fn for the fp32 training graph (the reference's training precision: tools/train.py runs without autocast): every fp32 operand
-    is split into two bf16 halves (16 mantissa bits together) and the three significant products run on the bf16 matrix cores with fp32 accumulation.
-      forward   pnx_conv3x3_x3 on (x_hi, x_lo) x (W_hi, W_lo) [+ bias]: one launch, fp32 out
-      dgrad     stride 1: the same kernel on the halves of g and of W^T flipped, masked by the INPUT's active set; stride 2: pnx_conv3x3_dgrad_s2_x3
-      wgrad     pnx_conv3x3_wgrad_x3: x_hi g_hi + x_lo g_hi + x_hi g_lo in one pass, accumulated in fp32
-    mask_out = mask_in = None: a dense layer (the neck's and the head's 3x3 convolutions, x3_conv below).  halves: (x_hi, x_lo) when the caller
-    already split x (the six branches of a SepHead share their input).
-    Relative error of every product ~ 4e-6 (the dropped low x low term and the halves' rounding, 2^-17 each), against MIOpen's fp32 kernels' ~ 2e-7:
-    tests/test_gpu_masked_conv_train.py holds the node against an fp64 convolution.  PNX_TRAIN_F32_HIP=0 keeps the fp32 graph on MIOpen."""
+    is split into bf16 pieces and the significant products run on the bf16 matrix cores with fp32 accumulation.  PNX_TRAIN_F32_PIECES (read at
+    forward time, kept in ctx for the backward) picks the form:
+      2 (default)  two halves (16 mantissa bits together), three products x_hi W_hi + x_hi W_lo + x_lo W_hi:
+        forward   pnx_conv3x3_x3 on (x_hi, x_lo) x (W_hi, W_lo) [+ bias]: one launch, fp32 out
+        dgrad     stride 1: the same kernel on the halves of g and of W^T flipped, masked by the INPUT's active set; stride 2: pnx_conv3x3_dgrad_s2_x3
+        wgrad     pnx_conv3x3_wgrad_x3: x_hi g_hi + x_lo g_hi + x_hi g_lo in one pass, accumulated in fp32
+        relative error of every product ~ 4e-6 (the dropped low x low term and the halves' rounding, 2^-17 each)
+      3            three pieces (pnx_split3_f32: exact for |x| >= 2^-100), the six products of piece orders 0..2, hi x hi last: pnx_conv3x3_x6,
+                   pnx_conv3x3_dgrad_s2_x6, pnx_conv3x3_wgrad_x6 in the same places; what is dropped is ~2^-23 of sum |x||W|, i.e. fp32's own rounding
+                   (~2e-7 relative, as MIOpen's fp32 kernels) for about twice the MFMA work of those layers
+    mask_out = mask_in = None: a dense layer (the neck's and the head's 3x3 convolutions, x3_conv below).  pieces: the bf16 pieces of x
+    (split_f32_pieces) when the caller already split it (the six branches of a SepHead share their input); they are what the backward keeps of x.
+    tests/test_gpu_masked_conv_train.py and tests/test_gpu_fp32_six_products.py hold the node against an fp64 convolution.  PNX_TRAIN_F32_HIP=0 keeps
+    the fp32 graph on MIOpen."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, mask_out, mask_in, stride, halves):
-        if halves is None:
-            halves = ops.split_f32(x.contiguous(memory_format=torch.channels_last), mask_in)   # x is zero outside its active set (masked_bn_act, the scatter)
-        xh, xl = halves
+    def forward(ctx, x, weight, bias, mask_out, mask_in, stride, pieces):
+        n = train_f32_pieces()
+        if pieces is None:
+            pieces = split_f32_pieces(x.contiguous(memory_format=torch.channels_last), mask_in, n)   # x is zero outside its active set (masked_bn_act, the scatter)
+        if len(pieces) != n:
+            raise ops.PnxError(f"_MaskedConv3x3F32Fn: {len(pieces)} pieces of x given, PNX_TRAIN_F32_PIECES={n}")
+        ctx.pieces = n
+        b = None if bias is None else bias.detach().contiguous()
+        if n == 3:
+            y = ops.conv3x3_x6(pieces, _split_pack(weight, pieces=3), weight.shape[0], stride, mask_out, bias=b)
+            ctx.save_for_backward(*pieces, weight, mask_in, mask_out)
+            ctx.stride = stride
+            return y
+        xh, xl = pieces
         wh, wl = _split_pack(weight)
-        y = ops.conv3x3_x3(xh, xl, wh, wl, weight.shape[0], stride, mask_out, bias=None if bias is None else bias.detach().contiguous())
+        y = ops.conv3x3_x3(xh, xl, wh, wl, weight.shape[0], stride, mask_out, bias=b)
         ctx.save_for_backward(xh, xl, weight, mask_in, mask_out)
         ctx.stride = stride
         return y
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.pieces == 3:
+            return _MaskedConv3x3F32Fn._backward6(ctx, g)
         xh, xl, weight, mask_in, mask_out = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         g = g.contiguous(memory_format=torch.channels_last)
@@ -407,6 +441,30 @@ class _MaskedConv3x3F32Fn(torch.autograd.Function):
         if need_w:
             m = mask_out if mask_out is not None else _ones_mask(g.shape[0], g.shape[2], g.shape[3], g.device)
             dw = ops.conv3x3_wgrad_x3(xh, xl, gh, gl, m, stride=s)
+        if need_b:
+            db = g.sum(dim=(0, 2, 3))
+        return dx, dw, db, None, None, None, None
+
+    @staticmethod
+    def _backward6(ctx, g):
+        """backward of the three-piece form: the same kernels' six-product twins (the stride-2 data gradient outside their shapes on MIOpen, as above)"""
+        xh, xm, xl, weight, mask_in, mask_out = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g = g.contiguous(memory_format=torch.channels_last)
+        s = ctx.stride
+        dx = dw = db = None
+        if need_w or need_x:
+            gp = ops.split3_f32(g, mask_out)   # zero outside mask_out, as above
+        if need_x:
+            if s == 1:
+                dx = ops.conv3x3_x6(gp, _split_pack(weight, transposed=True, pieces=3), weight.shape[1], 1, mask_in)
+            elif mask_in is not None and _hip_dgrad_s2(weight):
+                dx = ops.conv3x3_dgrad_s2_x6(gp, _split_pack(weight, transposed=True, pieces=3), weight.shape[1], xh.shape[2:], mask_in)
+            else:
+                dx = torch.nn.grad.conv2d_input(xh.shape, weight, g, stride=s, padding=1)
+        if need_w:
+            m = mask_out if mask_out is not None else _ones_mask(g.shape[0], g.shape[2], g.shape[3], g.device)
+            dw = ops.conv3x3_wgrad_x6((xh, xm, xl), gp, m, stride=s)
         if need_b:
             db = g.sum(dim=(0, 2, 3))
         return dx, dw, db, None, None, None, None
@@ -478,12 +536,12 @@ def bf16_dense_ok(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), gro
             and os.environ.get("PNX_TRAIN_HIPCONV", "1") != "0" and os.environ.get("PNX_TRAIN_DENSE_HIP", "1") != "0")
 
 
-def x3_conv(conv, x, halves=None):
-    """conv(x) of a dense nn.Conv2d in training: the fp32 graph on _MaskedConv3x3F32Fn where x3_ok says so, bf16 autocast on _MaskedConv3x3Fn where
-    bf16_dense_ok does, the module itself (MIOpen) otherwise."""
+def x3_conv(conv, x, pieces=None):
+    """conv(x) of a dense nn.Conv2d in training: the fp32 graph on _MaskedConv3x3F32Fn where x3_ok says so (pieces: x already split by
+    split_f32_pieces), bf16 autocast on _MaskedConv3x3Fn where bf16_dense_ok does, the module itself (MIOpen) otherwise."""
     if type(conv) is nn.Conv2d and conv.padding_mode == "zeros":
         if x3_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, conv.training):
-            return _MaskedConv3x3F32Fn.apply(x, conv.weight, conv.bias, None, None, 1, halves)
+            return _MaskedConv3x3F32Fn.apply(x, conv.weight, conv.bias, None, None, 1, pieces)
         if bf16_dense_ok(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, conv.training):
             return _MaskedConv3x3Fn.apply(x, conv.weight, None, None, 1, conv.bias)
     return conv(x)
@@ -734,14 +792,14 @@ class SepHead(nn.Module):
         x = self.deblock(x)
         if not (self.training and x.is_cuda and torch.is_grad_enabled()):
             return {head: getattr(self, head)(x) for head in self.heads}
-        # training: the branches' first 3x3 convolutions on the product's kernels (x3_conv: the fp32 graph on the three-product node, their shared input
-        # split into its bf16 halves once; bf16 autocast on the bf16 kernels), the output convolutions (64 -> k <= 4) on csrc/head_train.hip; anything
-        # else is the module itself
+        # training: the branches' first 3x3 convolutions on the product's kernels (x3_conv: the fp32 graph on the three- or six-product node, their
+        # shared input split into its bf16 pieces once; bf16 autocast on the bf16 kernels), the output convolutions (64 -> k <= 4) on
+        # csrc/head_train.hip; anything else is the module itself
         first = [getattr(self, head)[0] for head in self.heads]
-        halves = None
+        pieces = None
         if any(type(c) is nn.Conv2d and len(getattr(self, h)) > 1 and x3_ok(x, c.weight, c.stride, c.padding, c.dilation, c.groups, c.training)
                for h, c in zip(self.heads, first)):
-            halves = ops.split_f32(x.contiguous(memory_format=torch.channels_last))
+            pieces = split_f32_pieces(x.contiguous(memory_format=torch.channels_last))
         out = {}
         for head in self.heads:
             layers = list(getattr(self, head))
@@ -751,7 +809,7 @@ class SepHead(nn.Module):
                 if i == len(layers) - 1:
                     h = smallk_conv(layer, h)
                 elif i == 0:
-                    h = x3_conv(layer, h, halves)
+                    h = x3_conv(layer, h, pieces)
                 elif type(layer) is nn.BatchNorm2d and type(layers[i + 1]) is nn.ReLU:
                     h = dense_bn_act(layer, h)
                     i += 1

@@ -469,6 +469,24 @@ def split_f32(x, mask=None):
     return hi, lo
 
 
+def split3_f32(x, mask=None):
+    """fp32 tensor -> (hi, mid, lo) bf16 tensors of the same shape and memory layout: hi = RNE(x), mid = RNE(x - hi), lo = RNE(x - hi - mid)
+    (pnx_split3_f32; hi + mid + lo == x exactly for finite |x| >= 2^-100).  mask: as split_f32."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.numel() % 8 == 0):
+        raise PnxError("split3_f32 needs an fp32 CUDA tensor with a multiple of 8 elements")
+    if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))):
+        raise PnxError("split3_f32 needs a dense tensor (contiguous or channels_last)")
+    c = 0
+    if mask is not None:
+        if not (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and mask.dtype == torch.uint8 and mask.is_contiguous()
+                and tuple(mask.shape) == (x.shape[0], x.shape[2], x.shape[3]) and x.shape[1] % 8 == 0):
+            raise PnxError("split3_f32: mask needs a channels_last (B,C,H,W) tensor with C % 8 == 0 and a contiguous uint8 (B,H,W) mask")
+        c = x.shape[1]
+    hi, mid, lo = (torch.empty_like(x, dtype=torch.bfloat16) for _ in range(3))
+    check(lib().pnx_split3_f32(ptr(x), ptr(hi), ptr(mid), ptr(lo), x.numel(), ptr(mask), c, stream_ptr()), "pnx_split3_f32")
+    return hi, mid, lo
+
+
 CONV3X3_X3_SHAPES = {1: {(64, 64), (128, 128), (256, 256)}, 2: {(64, 128), (128, 256), (256, 256)}}   # stride -> (Cin, Cout) of pnx_conv3x3_x3
 
 
@@ -513,6 +531,77 @@ def conv3x3_wgrad_x3(x_hi, x_lo, dy_hi, dy_lo, mask, stride=1):
     check(lib().pnx_conv3x3_wgrad_x3(ptr(x_hi), ptr(x_lo), ptr(dy_hi), ptr(dy_lo), ptr(mask), ptr(dw), B, H, W, ci, co, stride, ptr(ws), ws.numel(), stream_ptr()),
           "pnx_conv3x3_wgrad_x3")
     return dw
+
+
+def _bf16_maps(tensors, what):
+    for tns in tensors:
+        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)
+                and tns.shape == tensors[0].shape):
+            raise PnxError(f"{what} needs channels_last bf16 CUDA pieces of one shape")
+
+
+def conv3x3_x6(x_pieces, wfrag_pieces, cout, stride, mask, bias=None):
+    """fp32 (B,Cout,Ho,Wo) channels_last = masked 3x3 convolution of x_hi + x_mid + x_lo (split3_f32) with W_hi + W_mid + W_lo (each packed by
+    conv3x3_pack_weights): the six products of piece orders 0..2 accumulated in fp32 in one launch (pnx_conv3x3_x6) [+ bias, fp32 (Cout,)];
+    mask uint8 (B,Ho,Wo) of the OUTPUT sites or None (dense); zeros at inactive sites."""
+    x_hi, x_mid, x_lo = x_pieces
+    w_hi, w_mid, w_lo = wfrag_pieces
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()):
+        raise PnxError("conv3x3_x6: bias must be a contiguous fp32 CUDA vector of Cout values")
+    _bf16_maps((x_hi, x_mid, x_lo), "conv3x3_x6")
+    if any(w.dtype != torch.bfloat16 or w.numel() != w_hi.numel() for w in (w_hi, w_mid, w_lo)):
+        raise PnxError("conv3x3_x6: the weights must be three packed bf16 pieces of one size")
+    B, ci, H, W = x_hi.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if mask is not None and (tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8):
+        raise PnxError("conv3x3_x6: mask must be uint8 (B,Ho,Wo)")
+    y = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x_hi.device, memory_format=torch.channels_last)
+    check(lib().pnx_conv3x3_x6(ptr(x_hi), ptr(x_mid), ptr(x_lo), ptr(w_hi), ptr(w_mid), ptr(w_lo), ptr(bias), ptr(mask), ptr(y), B, H, W, ci, cout, stride,
+                               stream_ptr()), "pnx_conv3x3_x6")
+    return y
+
+
+def conv3x3_wgrad_x6(x_pieces, dy_pieces, mask, stride=1):
+    """conv3x3_wgrad of x_hi + x_mid + x_lo with dy_hi + dy_mid + dy_lo (split3_f32 pieces; six products, one pass: pnx_conv3x3_wgrad_x6):
+    (Cout, Cin, 3, 3) fp32, deterministic."""
+    x_hi, x_mid, x_lo = x_pieces
+    dy_hi, dy_mid, dy_lo = dy_pieces
+    _bf16_maps((x_hi, x_mid, x_lo), "conv3x3_wgrad_x6")
+    _bf16_maps((dy_hi, dy_mid, dy_lo), "conv3x3_wgrad_x6")
+    B, ci, H, W = x_hi.shape
+    co = dy_hi.shape[1]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if stride not in (1, 2) or tuple(dy_hi.shape) != (B, co, Ho, Wo) or tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8:
+        raise PnxError("conv3x3_wgrad_x6: stride 1 or 2, dy (B,Cout,Ho,Wo) and a uint8 (B,Ho,Wo) mask of the output sites")
+    nbytes = int(lib().pnx_conv3x3_wgrad_workspace_bytes(ci, co))
+    if nbytes == 0:
+        raise PnxError(f"conv3x3_wgrad_x6: no kernel for {ci} -> {co} channels")
+    key = (nbytes, x_hi.device, torch.cuda.current_stream().cuda_stream)
+    ws = _WGRAD_WS.get(key)
+    if ws is None:
+        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=x_hi.device)
+    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x_hi.device)
+    check(lib().pnx_conv3x3_wgrad_x6(ptr(x_hi), ptr(x_mid), ptr(x_lo), ptr(dy_hi), ptr(dy_mid), ptr(dy_lo), ptr(mask), ptr(dw), B, H, W, ci, co, stride,
+                                     ptr(ws), ws.numel(), stream_ptr()), "pnx_conv3x3_wgrad_x6")
+    return dw
+
+
+def conv3x3_dgrad_s2_x6(g_pieces, wfrag_t_pieces, cin, in_hw, mask_in):
+    """conv3x3_dgrad_s2 from three bf16 pieces of the upstream gradient (split3_f32) and of the TRANSPOSED weight pack (pnx_conv3x3_dgrad_s2_x6):
+    six products, fp32 dx (B,cin,H,W) channels_last, zeros at inactive input sites."""
+    g_hi, g_mid, g_lo = g_pieces
+    w_hi, w_mid, w_lo = wfrag_t_pieces
+    _bf16_maps((g_hi, g_mid, g_lo), "conv3x3_dgrad_s2_x6")
+    H, W = in_hw
+    B, co, Ho, Wo = g_hi.shape
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1) or tuple(mask_in.shape) != (B, H, W) or mask_in.dtype != torch.uint8 or not mask_in.is_contiguous():
+        raise PnxError("conv3x3_dgrad_s2_x6: g (B,cout,Ho,Wo) with Ho = (H - 1) // 2 + 1 and a contiguous uint8 (B,H,W) mask of the input sites")
+    if any(w.dtype != torch.bfloat16 or w.numel() != w_hi.numel() for w in (w_hi, w_mid, w_lo)):
+        raise PnxError("conv3x3_dgrad_s2_x6: the weights must be three packed bf16 pieces of one size")
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=g_hi.device, memory_format=torch.channels_last)
+    check(lib().pnx_conv3x3_dgrad_s2_x6(ptr(g_hi), ptr(g_mid), ptr(g_lo), ptr(w_hi), ptr(w_mid), ptr(w_lo), ptr(mask_in), ptr(dx), B, H, W, cin, co,
+                                        stream_ptr()), "pnx_conv3x3_dgrad_s2_x6")
+    return dx
 
 
 def conv3x3_dgrad_s2(g, wfrag_t, cin, in_hw, mask_in, g_lo=None, wfrag_t_lo=None):
