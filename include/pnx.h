@@ -477,7 +477,7 @@ int pnx_gather_kept(const float* boxes9, const float* scores, const int32_t* kee
  *   bwd_apply  dx = scale * (g - mean_g - xhat * mean_gx), dresidual (optional) = g; mean_g = sum g / count, mean_gx = sum g*xhat / count
  * The per-channel arithmetic between those passes, as three small launches instead of ~30 host tensor statements per layer:
  *   reduce        sums fp64[cols] = the rows of a partials array added in a fixed order (all-reduce `sums` under SyncBatchNorm before the next call)
- *   finalize      from sums = [sum d | sum d^2 | count]: mean, invstd, scale, shift, count (fp32 vectors for apply / the backward) and torch's running-statistics
+ *   finalize      from sums = [sum d | sum d^2 | count]: mean (0 when count is 0), invstd, scale, shift, count (fp32 vectors for apply / the backward) and torch's running-statistics
  *                 update in place (running_mean / running_var fp32, both or neither; unbiased variance; num_batches_tracked += 1 when not NULL); center may
  *                 alias running_mean
  *   bwd_finalize  dgamma / dbeta from the LOCAL sums [sum g | sum g xhat], mean_g / mean_gx from the global ones (NULL: the local ones) */

@@ -51,6 +51,12 @@ __device__ __forceinline__ bf16x8 tr_frag(const uint8_t* base) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// a with every sign bit flipped when m = 0x80008000 (exact: -a), unchanged when m = 0
+__device__ __forceinline__ bf16x8 neg_if(bf16x8 a, uint32_t m) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  return __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a) ^ m);
+}
+
 // One tile's operands on their way from HBM to LDS: NY + NX chunks of 16 bytes per thread, held in registers while the previous tile's K steps run.
 template <int S>
 struct TileRegs {
@@ -203,9 +209,21 @@ __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__
 #define PNX_WG_LOAD(V_) \
   if constexpr (NP == 3) wg_load6<S>(R, V_, s_list[1 + (V_) / NV], x, x_mid, x_lo, dy, dy_mid, dy_lo, mask, tiles_x, tiles_y, H, W, Ho, Wo, cin, cout, cb, ib, t); \
   else visit_load(V_);
+  // NP > 1: the low-order visits add products ~2^-8 .. 2^-16 of the running sum into it, and an MFMA that adds a much smaller term to its
+  // accumulator rounds it down (toward -inf; measured: every element of dW low by the same amount, whatever the sign of dY -- 4.7e-6 relative at
+  // 32 tiles per workgroup against 7e-7 for round-to-nearest).  So the tiles accumulate the sum with signs + - - + + - - ..., (-1)^((k + 1) / 2):
+  // the accumulators are negated at the first visit of each odd tile and the dY fragments of the minus tiles carry flipped signs (both exact); the
+  // bias of the minus tiles cancels that of the plus tiles, and the pairs' order (+ - then - +) cancels its growth with the running sum as well.
   if (n_mine > 0) { PNX_WG_LOAD(0) }
   for (int v = 0; v < NV * n_mine; v++) {
     const int k = v / NV, ph = NV > 1 ? v % NV : 0;
+    if constexpr (NP > 1) {
+      if (ph == 0 && (k & 1)) {
+#pragma unroll
+        for (int j = 0; j < 9; j++) acc[j] = -acc[j];
+      }
+    }
+    const uint32_t flip = NP > 1 && (((k + 1) >> 1) & 1) ? 0x80008000u : 0u;
     uint32_t* rm = s_rm + 4 * (k & 1);  // the tile's row masks: set by the visits that stage dY (the same bits each time)
     tile_store<S>(R, sx, sy, rm, t, new_x(ph), new_y(ph));
     __syncthreads();
@@ -215,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__
     for (int ks = 0; ks < 2 * TH; ks++) {  // rolled: unrolled, the steps' reads are hoisted and the accumulators spill
       const int r = ks >> 1, hs = ks & 1;
       if (((rm[r] >> (16 * hs)) & 0xFFFFu) == 0u) continue;  // block-uniform: no active output among these 16 pixels
-      const bf16x8 a = tr_frag<0, 4>(ay + (r * 32 + 16 * hs) * WG_PS);
+      const bf16x8 a = neg_if(tr_frag<0, 4>(ay + (r * 32 + 16 * hs) * WG_PS), flip);
       const uint8_t* bb = bx + (S * r * XW + S * 16 * hs) * WG_PS;
 #define PNX_WG_TAP(KY, KX) acc[(KY) * 3 + (KX)] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, tr_frag<((KY) * XW + (KX)) * WG_PS, 4 * S>(bb), acc[(KY) * 3 + (KX)], 0, 0, 0);
       PNX_WG_TAP(0, 0) PNX_WG_TAP(0, 1) PNX_WG_TAP(0, 2) PNX_WG_TAP(1, 0) PNX_WG_TAP(1, 1) PNX_WG_TAP(1, 2) PNX_WG_TAP(2, 0) PNX_WG_TAP(2, 1) PNX_WG_TAP(2, 2)
@@ -224,6 +242,10 @@ __global__ __launch_bounds__(256, 2) void k_wgrad64(const uint16_t* __restrict__
     __syncthreads();  // the next tile overwrites the LDS image
   }
 #undef PNX_WG_LOAD
+  if (NP > 1 && ((n_mine >> 1) & 1)) {  // the last tile was a minus tile: the accumulators hold minus the sum
+#pragma unroll
+    for (int j = 0; j < 9; j++) acc[j] = -acc[j];
+  }
   // ---- the workgroup's partial: [pair][group][tap][64 co][64 ci] fp32; D[m][n]: m = (i & 3) + 8 (i >> 2) + 4 (l >> 5), n = l & 31
   float* out = part + ((int64_t)pair * G + blockIdx.x) * 9 * 4096;
 #pragma unroll

@@ -294,7 +294,8 @@ __global__ __launch_bounds__(256) void k_mbn_finalize(const double* __restrict__
   const double dmean = sums[c] / cnt;
   double var = sums[C + c] / cnt - dmean * dmean;
   var = var < 0.0 ? 0.0 : var;
-  const double mean = (center != nullptr ? (double)center[c] : 0.0) + dmean;
+  // no active site: mean 0 (sum / max(count, 1), the torch statement), not the centre -- the running mean decays by the momentum as it does there
+  const double mean = sums[2 * C] < 1.0 ? 0.0 : (center != nullptr ? (double)center[c] : 0.0) + dmean;
   const double invstd = 1.0 / sqrt(var + eps);
   if (running_mean != nullptr) {
     const float keep = (float)(1.0 - momentum), mom = (float)momentum;
