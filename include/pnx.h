@@ -584,6 +584,42 @@ typedef struct pnx_lazy_decode {
 int pnx_decode_lazy_enqueue(const pnx_lazy_decode* desc_host, pnx_stream_t stream);
 size_t pnx_lazy_decode_bytes(void);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sparse 3-D convolution, eval mode: SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py, utils/sparse_conv.py:66-104) on the
+ * active sites of a (batch, D, H, W) grid (csrc/sparse3d.hip).
+ *   coords      (n, 4) int32 [b, z, y, x] rows, 16-byte aligned; rows with a coordinate outside the grid are ignored
+ *   index       caller-owned buffer of pnx_sp3_index_bytes(batch, grid): a key-order occupancy bitmap (key = ((b*D + z)*H + y)*W + x,
+ *               64-bit) and its popcount word prefix.  A site's rank is the number of active keys below it: [b, z, y, x] order.
+ *   grid3, kernel3, stride3, pad3: host int32[3] over (D, H, W); kernels 1..3, strides 1..2, padding < kernel
+ *   count       optional device int32: number of active sites of the set the call indexed
+ * pnx_sp3_index_build: index of an existing set; row_of_rank (optional, n int32) receives the input row of every rank.
+ * pnx_sp3_out_index: index of SparseConv3d's output set over the grid pnx_sp3_out_grid gives ((n + 2 pad - k) / s + 1 per axis): an
+ *   output q exists iff some active input lies at q*s - pad + o.  Reading `count` back sizes what follows.
+ * pnx_sp3_index_coords: the set's rows in rank order (the first `capacity`).
+ * pnx_sp3_neighbor_map: map (n_out, T) int32, T = kd*kh*kw, tap (od*kh + oh)*kw + ow: the input row at q*s - pad + o (its rank, or
+ *   row_of_rank_in[rank] when given), -1 where that site is inactive or outside.  Submanifold layers pass the set's own index, stride 1.
+ * pnx_sp3_conv: y (n_out, cout) = relu?(sum over taps and cin of x[map[row][t]][c] * w[t][c][:] + shift (+ residual (n_out, cout))),
+ *   fp32 in and out on the fp32 matrix cores, every row reduced in one fixed order (bit-identical run to run).  w_packed is
+ *   (T, round_up(cin, 4), round_up(cout, 16)) fp32 = pnx_sp3_packed_weight_floats, zero-padded, BatchNorm scale folded in; cout <= 144.
+ * pnx_sp3_dense: out (batch, channels*D, H, W) fp32 zero-filled, then out[b][c*D + z][y][x] = feat[row][c] (x.dense().view(B, C*D, H, W)). */
+size_t pnx_sp3_index_bytes(int32_t batch, const int32_t* grid3_host);
+int pnx_sp3_index_build(const int32_t* coords, int64_t n, int32_t batch, const int32_t* grid3_host, void* index, size_t index_bytes, int32_t* row_of_rank,
+                        int32_t* count, pnx_stream_t stream);
+int pnx_sp3_out_grid(int32_t batch, const int32_t* grid_in3_host, const int32_t* kernel3_host, const int32_t* stride3_host, const int32_t* pad3_host,
+                     int32_t* grid_out3_host);
+int pnx_sp3_out_index(const int32_t* coords_in, int64_t n_in, int32_t batch, const int32_t* grid_in3_host, const int32_t* kernel3_host,
+                      const int32_t* stride3_host, const int32_t* pad3_host, void* index_out, size_t index_out_bytes, int32_t* count, pnx_stream_t stream);
+int pnx_sp3_index_coords(const void* index, size_t index_bytes, int32_t batch, const int32_t* grid3_host, int32_t* coords, int64_t capacity,
+                         pnx_stream_t stream);
+int pnx_sp3_neighbor_map(const int32_t* coords_out, int64_t n_out, const void* index_in, size_t index_in_bytes, int32_t batch, const int32_t* grid_in3_host,
+                         const int32_t* row_of_rank_in, const int32_t* kernel3_host, const int32_t* stride3_host, const int32_t* pad3_host, int32_t* map,
+                         pnx_stream_t stream);
+size_t pnx_sp3_packed_weight_floats(int32_t taps, int32_t cin, int32_t cout);
+int pnx_sp3_conv(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
+                 const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream);
+int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* out,
+                  pnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _f32 = ctypes.c_float
 _sz = ctypes.c_size_t
+_i3p = ctypes.POINTER(ctypes.c_int32)   # host int32[3]
 
 # name -> (restype, argtypes); every symbol include/pnx.h declares (tests/test_capi_symbols.py checks the two agree)
 PROTOTYPES = {
@@ -125,6 +126,15 @@ PROTOTYPES = {
     "pnx_debug_nms_pair_cap": (_i32, [_i32]),
     "pnx_nms_rotated_batched": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "pnx_nms_normal_batched": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "pnx_sp3_index_bytes": (_sz, [_i32, _i3p]),
+    "pnx_sp3_index_build": (ctypes.c_int, [_vp, _i64, _i32, _i3p, _vp, _sz, _vp, _vp, _vp]),
+    "pnx_sp3_out_grid": (ctypes.c_int, [_i32, _i3p, _i3p, _i3p, _i3p, _i3p]),
+    "pnx_sp3_out_index": (ctypes.c_int, [_vp, _i64, _i32, _i3p, _i3p, _i3p, _i3p, _vp, _sz, _vp, _vp]),
+    "pnx_sp3_index_coords": (ctypes.c_int, [_vp, _sz, _i32, _i3p, _vp, _i64, _vp]),
+    "pnx_sp3_neighbor_map": (ctypes.c_int, [_vp, _i64, _vp, _sz, _i32, _i3p, _vp, _i3p, _i3p, _i3p, _vp, _vp]),
+    "pnx_sp3_packed_weight_floats": (_sz, [_i32, _i32, _i32]),
+    "pnx_sp3_conv": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "pnx_sp3_dense": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i3p, _vp, _vp]),
 }
 
 _LIB = None

@@ -1,0 +1,413 @@
+// sparse3d.hip -- sparse 3-D convolution for SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py, utils/sparse_conv.py:66-104), eval mode:
+//   pnx_sp3_index_build   key-order occupancy bitmap + popcount word prefix of an active set (the index)
+//   pnx_sp3_out_index     index of the output set of SparseConv3d: every input x tap sets the bit of the output it reaches
+//   pnx_sp3_index_coords  the set's [b, z, y, x] rows in key (= rank) order
+//   pnx_sp3_neighbor_map  (N_out, T) input row per output site and tap, -1 where the neighbour is inactive
+//   pnx_sp3_conv          gather-GEMM on the fp32 matrix cores + folded BN shift (+ residual) (+ ReLU)
+//   pnx_sp3_dense         rows -> zero-initialised (B, C*D, H, W), channel c*D + d (x.dense().view(B, C*D, H, W), :67-71)
+//
+// A site's key is ((b*D + z)*H + y)*W + x (64-bit), one bit of the bitmap; its rank (the row it occupies) is the number of set bits
+// below it: blk[word >> PNX_SCAN_SHIFT] + pre[word] + popc(bitmap[word] & below).  Ranks follow [b, z, y, x] lexicographic order, which
+// is torch.unique(dim=0)'s order and so the voxel reader's row order.  Neighbour lookup is a bit test and that rank: no hash table.
+//
+// Convolution: a wave owns 16 output rows and every output channel (NT tiles of 16); K runs tap by tap, Cin in steps of 4, on
+// v_mfma_f32_16x16x4_f32 -- exact fp32 products accumulated in k order, so every output row is reduced in one fixed order whatever the
+// tiling (a missing neighbour contributes 0 * w, which leaves the sum unchanged), and a tap none of the 16 rows has is skipped.
+#include "pnx_common.h"
+#include "pnx_scan.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct Sp3Grid {
+  int B, D, H, W;
+};
+
+struct Sp3Index {
+  uint32_t* bitmap;
+  uint32_t* pre;
+  uint32_t* blk;
+  int64_t nwords;
+  int nblk;
+  size_t bytes;
+};
+
+Sp3Index sp3_carve(void* base, const Sp3Grid& g) {
+  Sp3Index r;
+  const int64_t cells = (int64_t)g.B * g.D * g.H * g.W;
+  r.nwords = (cells + 31) >> 5;
+  r.nblk = (int)((r.nwords + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
+  PnxCarver c(base);
+  r.bitmap = c.take<uint32_t>((size_t)r.nwords);
+  r.pre = c.take<uint32_t>((size_t)r.nwords);
+  r.blk = c.take<uint32_t>((size_t)r.nblk + 1);
+  r.bytes = c.used();
+  return r;
+}
+
+int sp3_grid(int32_t batch, const int32_t* grid3, Sp3Grid* g) {
+  PNX_REQUIRE(grid3 != nullptr, PNX_ERR_INVALID, "sparse3d: grid is NULL");
+  PNX_REQUIRE(batch >= 0 && grid3[0] >= 1 && grid3[1] >= 1 && grid3[2] >= 1, PNX_ERR_INVALID, "sparse3d: bad grid %d x (%d, %d, %d)", batch,
+              grid3[0], grid3[1], grid3[2]);
+  const int64_t cells = (int64_t)batch * grid3[0] * grid3[1] * grid3[2];
+  PNX_REQUIRE(cells < ((int64_t)1 << 36), PNX_ERR_UNSUPPORTED, "sparse3d: %lld grid cells (at most 2^36)", (long long)cells);
+  g->B = batch, g->D = grid3[0], g->H = grid3[1], g->W = grid3[2];
+  return PNX_OK;
+}
+
+// output extent (n + 2 pad - k) / s + 1 per axis; fills o and returns PNX_OK, or an error for a geometry without outputs
+int sp3_conv_geom(const Sp3Grid& in, const int32_t* k3, const int32_t* s3, const int32_t* p3, Sp3Grid* out) {
+  PNX_REQUIRE(k3 && s3 && p3, PNX_ERR_INVALID, "sparse3d: kernel / stride / padding is NULL");
+  const int n[3] = {in.D, in.H, in.W};
+  int o[3];
+  for (int a = 0; a < 3; a++) {
+    PNX_REQUIRE(k3[a] >= 1 && k3[a] <= 3 && s3[a] >= 1 && s3[a] <= 2 && p3[a] >= 0 && p3[a] < k3[a], PNX_ERR_UNSUPPORTED,
+                "sparse3d: axis %d kernel %d stride %d padding %d (kernels 1..3, strides 1..2)", a, k3[a], s3[a], p3[a]);
+    PNX_REQUIRE(n[a] + 2 * p3[a] >= k3[a], PNX_ERR_INVALID, "sparse3d: axis %d of extent %d is smaller than the kernel", a, n[a]);
+    o[a] = (n[a] + 2 * p3[a] - k3[a]) / s3[a] + 1;
+  }
+  out->B = in.B, out->D = o[0], out->H = o[1], out->W = o[2];
+  return PNX_OK;
+}
+
+struct Sp3Conv {
+  int k[3], s[3], p[3];
+};
+
+__device__ __forceinline__ int64_t sp3_key(const Sp3Grid& g, int b, int z, int y, int x) { return (((int64_t)b * g.D + z) * g.H + y) * g.W + x; }
+
+__device__ __forceinline__ bool sp3_row(const int32_t* __restrict__ coords, int64_t i, const Sp3Grid& g, int (&c)[4]) {
+  const int4 v = *reinterpret_cast<const int4*>(coords + 4 * i);
+  c[0] = v.x, c[1] = v.y, c[2] = v.z, c[3] = v.w;
+  return c[0] >= 0 && c[0] < g.B && c[1] >= 0 && c[1] < g.D && c[2] >= 0 && c[2] < g.H && c[3] >= 0 && c[3] < g.W;
+}
+
+__device__ __forceinline__ uint32_t sp3_rank(const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk,
+                                             int64_t k) {
+  const int64_t w = k >> 5;
+  return blk[w >> PNX_SCAN_SHIFT] + pre[w] + (uint32_t)__popc(bitmap[w] & ((1u << (k & 31)) - 1u));
+}
+
+// rows with a coordinate outside the grid are skipped here (the module rejects them before calling)
+__global__ __launch_bounds__(kBlock) void k_sp3_mark(const int32_t* __restrict__ coords, int64_t n, Sp3Grid g, uint32_t* __restrict__ bitmap) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int c[4];
+  if (!sp3_row(coords, i, g, c)) return;
+  const int64_t k = sp3_key(g, c[0], c[1], c[2], c[3]);
+  atomicOr(&bitmap[k >> 5], 1u << (k & 31));
+}
+
+__global__ __launch_bounds__(kBlock) void k_sp3_row_of_rank(const int32_t* __restrict__ coords, int64_t n, Sp3Grid g, const uint32_t* __restrict__ bitmap,
+                                                            const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk, int32_t* __restrict__ row_of_rank) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int c[4];
+  if (!sp3_row(coords, i, g, c)) return;
+  const uint32_t r = sp3_rank(bitmap, pre, blk, sp3_key(g, c[0], c[1], c[2], c[3]));
+  if ((int64_t)r < n) row_of_rank[r] = (int32_t)i;
+}
+
+// output q exists iff some active input p = q*s - pad + o: for every input and tap, (p + pad - o) divisible by s and inside the output grid
+__global__ __launch_bounds__(kBlock) void k_sp3_mark_out(const int32_t* __restrict__ coords, int64_t n, Sp3Grid gi, Sp3Grid go, Sp3Conv cv,
+                                                         uint32_t* __restrict__ bitmap) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int c[4];
+  if (!sp3_row(coords, i, gi, c)) return;
+  for (int od = 0; od < cv.k[0]; od++) {
+    const int z = c[1] + cv.p[0] - od;
+    if (z < 0 || z % cv.s[0] != 0 || z / cv.s[0] >= go.D) continue;
+    for (int oh = 0; oh < cv.k[1]; oh++) {
+      const int yy = c[2] + cv.p[1] - oh;
+      if (yy < 0 || yy % cv.s[1] != 0 || yy / cv.s[1] >= go.H) continue;
+      for (int ow = 0; ow < cv.k[2]; ow++) {
+        const int xx = c[3] + cv.p[2] - ow;
+        if (xx < 0 || xx % cv.s[2] != 0 || xx / cv.s[2] >= go.W) continue;
+        const int64_t k = sp3_key(go, c[0], z / cv.s[0], yy / cv.s[1], xx / cv.s[2]);
+        atomicOr(&bitmap[k >> 5], 1u << (k & 31));
+      }
+    }
+  }
+}
+
+// one thread per bitmap word: every set bit writes its [b, z, y, x] row at its rank
+__global__ __launch_bounds__(kBlock) void k_sp3_coords(const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk,
+                                                       int64_t nwords, Sp3Grid g, int32_t* __restrict__ coords, int64_t cap) {
+  const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (w >= nwords) return;
+  uint32_t m = bitmap[w];
+  int64_t r = (int64_t)blk[w >> PNX_SCAN_SHIFT] + pre[w];
+  const int64_t hw = (int64_t)g.H * g.W, dhw = hw * g.D;
+  while (m) {
+    const int bit = __ffs(m) - 1;
+    m &= m - 1;
+    if (r < cap) {
+      int64_t k = (w << 5) + bit;
+      const int b = (int)(k / dhw);
+      k -= (int64_t)b * dhw;
+      const int z = (int)(k / hw);
+      k -= (int64_t)z * hw;
+      *reinterpret_cast<int4*>(coords + 4 * r) = make_int4(b, z, (int)(k / g.W), (int)(k % g.W));
+    }
+    r++;
+  }
+}
+
+// map[row][tap] = input row at q*s - pad + o (tap = (od*kh + oh)*kw + ow, spconv's kernel order), -1 where that site is inactive or outside
+__global__ __launch_bounds__(kBlock) void k_sp3_nbmap(const int32_t* __restrict__ coords_out, int64_t n_out, Sp3Grid go, Sp3Grid gi, Sp3Conv cv,
+                                                      const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ pre,
+                                                      const uint32_t* __restrict__ blk, const int32_t* __restrict__ row_of_rank, int T,
+                                                      int32_t* __restrict__ map) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= n_out * T) return;
+  const int64_t i = e / T;
+  const int t = (int)(e - i * T);
+  int c[4];
+  int32_t v = -1;
+  if (sp3_row(coords_out, i, go, c)) {
+    const int o[3] = {t / (cv.k[1] * cv.k[2]), (t / cv.k[2]) % cv.k[1], t % cv.k[2]};
+    const int n[3] = {gi.D, gi.H, gi.W};
+    int p[3];
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      p[a] = c[1 + a] * cv.s[a] - cv.p[a] + o[a];
+      ok = ok && p[a] >= 0 && p[a] < n[a];
+    }
+    if (ok) {
+      const int64_t k = sp3_key(gi, c[0], p[0], p[1], p[2]);
+      if ((bitmap[k >> 5] >> (k & 31)) & 1u) {
+        const uint32_t r = sp3_rank(bitmap, pre, blk, k);
+        v = row_of_rank ? row_of_rank[r] : (int32_t)r;
+      }
+    }
+  }
+  map[e] = v;
+}
+
+// y[row] = relu?( sum_t sum_c x[map[row][t]][c] * w'[t][c][:] + shift (+ residual[row]) ).  w' is (T, cin4, NT*16): BN scale folded in, zero-padded.
+template <int NT>
+__global__ __launch_bounds__(kBlock) void k_sp3_conv(const float* __restrict__ x, int64_t n_in, int cin, const int32_t* __restrict__ map, int64_t n_out, int T,
+                                                     const float* __restrict__ wp, const float* __restrict__ shift, const float* __restrict__ res, int relu,
+                                                     float* __restrict__ y, int cout) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row0 = ((int64_t)blockIdx.x * (kBlock / 64) + wave) * 16;
+  if (row0 >= n_out) return;  // wave-uniform; the kernel has no barrier
+  const int r = lane & 15, kk = lane >> 4;
+  const int64_t row = row0 + r;
+  const int cin4 = (cin + 3) & ~3, ldw = NT * 16;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; j++) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < T; t++) {
+    int32_t nb = row < n_out ? map[row * T + t] : -1;
+    if ((int64_t)nb >= n_in) nb = -1;
+    if (__ballot(nb >= 0) == 0) continue;  // no row of the tile has this neighbour: no MFMA
+    const float* xr = x + (int64_t)(nb < 0 ? 0 : nb) * cin;
+    const float* wt = wp + (int64_t)t * cin4 * ldw + r;
+    for (int k0 = 0; k0 < cin; k0 += 4) {
+      const int k = k0 + kk;
+      const float a = (nb >= 0 && k < cin) ? xr[k] : 0.f;
+      const float* wk = wt + (int64_t)k * ldw;
+#pragma unroll
+      for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wk[j * 16], acc[j], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NT; j++) {
+    const int col = j * 16 + r;
+    if (col >= cout) continue;
+    const float sh = shift[col];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int64_t orow = row0 + kk * 4 + i;
+      if (orow >= n_out) continue;
+      float v = acc[j][i] + sh;
+      if (res) v += res[orow * cout + col];
+      if (relu && v < 0.f) v = 0.f;
+      y[orow * cout + col] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_sp3_dense(const float* __restrict__ feat, const int32_t* __restrict__ coords, int64_t n, int C, Sp3Grid g,
+                                                      float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= n * C) return;
+  const int64_t i = e / C;
+  const int ch = (int)(e - i * C);
+  int c[4];
+  if (!sp3_row(coords, i, g, c)) return;
+  out[((((int64_t)c[0] * C + ch) * g.D + c[1]) * g.H + c[2]) * g.W + c[3]] = feat[e];
+}
+
+unsigned sp3_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
+  *ix = sp3_carve(index, g);
+  PNX_REQUIRE(index != nullptr && ((uintptr_t)index & 255) == 0, PNX_ERR_INVALID, "sparse3d: index must be a 256-byte aligned buffer");
+  PNX_REQUIRE(index_bytes >= ix->bytes, PNX_ERR_WORKSPACE, "sparse3d: index %zu bytes < %zu needed", index_bytes, ix->bytes);
+  return PNX_OK;
+}
+
+// bitmap already marked: word prefix (level 1 + level 2), total set bits -> count
+int sp3_scan(const Sp3Index& ix, int32_t* count, hipStream_t st) {
+  if (ix.nblk > 0) k_scan_local<SCAN_POPC><<<ix.nblk, kBlock, 0, st>>>(ix.bitmap, ix.nwords, ix.pre, ix.blk);
+  k_scan_blocks<<<1, kBlock, 0, st>>>(ix.blk, ix.nblk, count);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+template <int NT>
+void sp3_conv_launch(unsigned nb, hipStream_t st, const float* x, int64_t n_in, int cin, const int32_t* map, int64_t n_out, int T, const float* wp,
+                     const float* shift, const float* res, int relu, float* y, int cout) {
+  k_sp3_conv<NT><<<nb, kBlock, 0, st>>>(x, n_in, cin, map, n_out, T, wp, shift, res, relu, y, cout);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pnx_sp3_index_bytes(int32_t batch, const int32_t* grid3_host) {
+  Sp3Grid g;
+  if (sp3_grid(batch, grid3_host, &g) != PNX_OK) return 0;
+  return sp3_carve(nullptr, g).bytes;
+}
+
+int pnx_sp3_index_build(const int32_t* coords, int64_t n, int32_t batch, const int32_t* grid3_host, void* index, size_t index_bytes, int32_t* row_of_rank,
+                        int32_t* count, pnx_stream_t stream) {
+  Sp3Grid g;
+  Sp3Index ix;
+  int rc = sp3_grid(batch, grid3_host, &g);
+  if (rc == PNX_OK) rc = sp3_index_args(g, index, index_bytes, &ix);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_index_build: %lld rows", (long long)n);
+  PNX_REQUIRE(n == 0 || (coords != nullptr && ((uintptr_t)coords & 15) == 0), PNX_ERR_INVALID, "pnx_sp3_index_build: coords NULL or not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  PNX_CHECK_HIP(hipMemsetAsync(ix.bitmap, 0, (size_t)ix.nwords * 4, st));
+  if (n > 0) k_sp3_mark<<<sp3_blocks(n), kBlock, 0, st>>>(coords, n, g, ix.bitmap);
+  rc = sp3_scan(ix, count, st);
+  if (rc != PNX_OK) return rc;
+  if (row_of_rank && n > 0) {
+    k_sp3_row_of_rank<<<sp3_blocks(n), kBlock, 0, st>>>(coords, n, g, ix.bitmap, ix.pre, ix.blk, row_of_rank);
+    PNX_LAUNCH_CHECK();
+  }
+  return PNX_OK;
+}
+
+int pnx_sp3_out_grid(int32_t batch, const int32_t* grid_in3_host, const int32_t* kernel3_host, const int32_t* stride3_host, const int32_t* pad3_host,
+                     int32_t* grid_out3_host) {
+  Sp3Grid gi, go;
+  int rc = sp3_grid(batch, grid_in3_host, &gi);
+  if (rc == PNX_OK) rc = sp3_conv_geom(gi, kernel3_host, stride3_host, pad3_host, &go);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(grid_out3_host != nullptr, PNX_ERR_INVALID, "pnx_sp3_out_grid: grid_out3_host is NULL");
+  grid_out3_host[0] = go.D, grid_out3_host[1] = go.H, grid_out3_host[2] = go.W;
+  return PNX_OK;
+}
+
+int pnx_sp3_out_index(const int32_t* coords_in, int64_t n_in, int32_t batch, const int32_t* grid_in3_host, const int32_t* kernel3_host,
+                      const int32_t* stride3_host, const int32_t* pad3_host, void* index_out, size_t index_out_bytes, int32_t* count, pnx_stream_t stream) {
+  Sp3Grid gi, go;
+  Sp3Index ix;
+  int rc = sp3_grid(batch, grid_in3_host, &gi);
+  if (rc == PNX_OK) rc = sp3_conv_geom(gi, kernel3_host, stride3_host, pad3_host, &go);
+  if (rc == PNX_OK) rc = sp3_index_args(go, index_out, index_out_bytes, &ix);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(n_in >= 0 && n_in < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_out_index: %lld rows", (long long)n_in);
+  PNX_REQUIRE(n_in == 0 || (coords_in != nullptr && ((uintptr_t)coords_in & 15) == 0), PNX_ERR_INVALID,
+              "pnx_sp3_out_index: coords NULL or not 16-byte aligned");
+  Sp3Conv cv;
+  for (int a = 0; a < 3; a++) cv.k[a] = kernel3_host[a], cv.s[a] = stride3_host[a], cv.p[a] = pad3_host[a];
+  hipStream_t st = (hipStream_t)stream;
+  PNX_CHECK_HIP(hipMemsetAsync(ix.bitmap, 0, (size_t)ix.nwords * 4, st));
+  if (n_in > 0) k_sp3_mark_out<<<sp3_blocks(n_in), kBlock, 0, st>>>(coords_in, n_in, gi, go, cv, ix.bitmap);
+  return sp3_scan(ix, count, st);
+}
+
+int pnx_sp3_index_coords(const void* index, size_t index_bytes, int32_t batch, const int32_t* grid3_host, int32_t* coords, int64_t capacity,
+                         pnx_stream_t stream) {
+  Sp3Grid g;
+  Sp3Index ix;
+  int rc = sp3_grid(batch, grid3_host, &g);
+  if (rc == PNX_OK) rc = sp3_index_args(g, const_cast<void*>(index), index_bytes, &ix);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(capacity >= 0 && (capacity == 0 || (coords != nullptr && ((uintptr_t)coords & 15) == 0)), PNX_ERR_INVALID,
+              "pnx_sp3_index_coords: coords NULL or not 16-byte aligned");
+  if (capacity == 0 || ix.nwords == 0) return PNX_OK;
+  k_sp3_coords<<<sp3_blocks(ix.nwords), kBlock, 0, (hipStream_t)stream>>>(ix.bitmap, ix.pre, ix.blk, ix.nwords, g, coords, capacity);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_neighbor_map(const int32_t* coords_out, int64_t n_out, const void* index_in, size_t index_in_bytes, int32_t batch, const int32_t* grid_in3_host,
+                         const int32_t* row_of_rank_in, const int32_t* kernel3_host, const int32_t* stride3_host, const int32_t* pad3_host, int32_t* map,
+                         pnx_stream_t stream) {
+  Sp3Grid gi, go;
+  Sp3Index ix;
+  int rc = sp3_grid(batch, grid_in3_host, &gi);
+  if (rc == PNX_OK) rc = sp3_conv_geom(gi, kernel3_host, stride3_host, pad3_host, &go);
+  if (rc == PNX_OK) rc = sp3_index_args(gi, const_cast<void*>(index_in), index_in_bytes, &ix);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_neighbor_map: %lld rows", (long long)n_out);
+  PNX_REQUIRE(n_out == 0 || (coords_out != nullptr && ((uintptr_t)coords_out & 15) == 0 && map != nullptr), PNX_ERR_INVALID,
+              "pnx_sp3_neighbor_map: coords_out / map NULL or coords not 16-byte aligned");
+  Sp3Conv cv;
+  for (int a = 0; a < 3; a++) cv.k[a] = kernel3_host[a], cv.s[a] = stride3_host[a], cv.p[a] = pad3_host[a];
+  const int T = cv.k[0] * cv.k[1] * cv.k[2];
+  if (n_out == 0) return PNX_OK;
+  k_sp3_nbmap<<<sp3_blocks(n_out * T), kBlock, 0, (hipStream_t)stream>>>(coords_out, n_out, go, gi, cv, ix.bitmap, ix.pre, ix.blk, row_of_rank_in, T, map);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_sp3_packed_weight_floats(int32_t taps, int32_t cin, int32_t cout) {
+  if (taps < 1 || cin < 1 || cout < 1) return 0;
+  return (size_t)taps * ((cin + 3) & ~3) * ((cout + 15) & ~15);
+}
+
+int pnx_sp3_conv(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
+                 const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
+  PNX_REQUIRE(cin >= 1 && cin <= 1024 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
+              "pnx_sp3_conv: %d -> %d channels over %d taps (cin 1..1024, cout 1..144, taps 1..27)", cin, cout, taps);
+  PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_conv: %lld -> %lld rows", (long long)n_in,
+              (long long)n_out);
+  if (n_out == 0) return PNX_OK;
+  PNX_REQUIRE(map && w_packed && shift && y && (n_in == 0 || x), PNX_ERR_INVALID, "pnx_sp3_conv: null pointer");
+  const unsigned nb = (unsigned)((n_out + 63) / 64);
+  hipStream_t st = (hipStream_t)stream;
+  switch ((cout + 15) / 16) {
+    case 1: sp3_conv_launch<1>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 2: sp3_conv_launch<2>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 3: sp3_conv_launch<3>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 4: sp3_conv_launch<4>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 5: sp3_conv_launch<5>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 6: sp3_conv_launch<6>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 7: sp3_conv_launch<7>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 8: sp3_conv_launch<8>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    default: sp3_conv_launch<9>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+  }
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* out,
+                  pnx_stream_t stream) {
+  Sp3Grid g;
+  int rc = sp3_grid(batch, grid3_host, &g);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(n >= 0 && channels >= 1, PNX_ERR_INVALID, "pnx_sp3_dense: %lld rows of %d channels", (long long)n, channels);
+  const size_t bytes = (size_t)g.B * channels * g.D * g.H * g.W * sizeof(float);
+  if (bytes == 0) return PNX_OK;  // a batch of 0 samples
+  PNX_REQUIRE(out != nullptr && (n == 0 || (feat && coords && ((uintptr_t)coords & 15) == 0)), PNX_ERR_INVALID, "pnx_sp3_dense: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  PNX_CHECK_HIP(hipMemsetAsync(out, 0, bytes, st));
+  if (n == 0) return PNX_OK;
+  k_sp3_dense<<<sp3_blocks(n * channels), kBlock, 0, st>>>(feat, coords, n, channels, g, out);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+}  // extern "C"

@@ -707,3 +707,117 @@ def conv3x3_masked(x, wfrag, bias, cout, stride=1, mask=None, residual=None, rel
     check(_conv_fn("conv3x3", x.dtype)(ptr(x), ptr(wfrag), ptr(bias), ptr(residual), ptr(mask), ptr(y), B, H, W, ci, cout, stride, 1 if relu else 0,
                                        ptr(dirty), ptr(tl), ptr(tc), stream_ptr()), "pnx_conv3x3")
     return y
+
+
+# --------------------------------------------------------------------------------------------- sparse 3-D convolution (csrc/sparse3d.hip)
+def _i3(v):
+    return (ctypes.c_int32 * 3)(*[int(a) for a in v])
+
+
+class Sp3Index:
+    """An active set's index on the device (pnx_sp3_index_bytes): key-order occupancy bitmap + popcount word prefix over (batch, D, H, W)."""
+
+    def __init__(self, batch, grid, device):
+        self.batch, self.grid = int(batch), tuple(int(g) for g in grid)
+        self.nbytes = lib().pnx_sp3_index_bytes(self.batch, _i3(self.grid))
+        if self.nbytes == 0:
+            raise PnxError(f"sparse3d: bad grid {self.batch} x {self.grid}")
+        self.buf = torch.empty((self.nbytes,), dtype=torch.uint8, device=device)
+
+
+def _need_coords(coords):
+    _need_cuda(coords, "coords")
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4:
+        raise PnxError("coords must be (N, 4) int32 [b, z, y, x]")
+
+
+def sp3_out_grid(batch, grid, kernel, stride, pad):
+    """(n + 2 pad - k) // s + 1 per axis of (D, H, W)."""
+    out = _i3((0, 0, 0))
+    check(lib().pnx_sp3_out_grid(int(batch), _i3(grid), _i3(kernel), _i3(stride), _i3(pad), out), "pnx_sp3_out_grid")
+    return tuple(out)
+
+
+def sp3_index_build(coords, batch, grid, want_rows=False):
+    """pnx_sp3_index_build -> (Sp3Index, row_of_rank (N,) int32 or None, count (1,) int32 device tensor)."""
+    _need_coords(coords)
+    ix = Sp3Index(batch, grid, coords.device)
+    n = coords.shape[0]
+    rows = torch.full((max(n, 1),), -1, dtype=torch.int32, device=coords.device) if want_rows else None
+    count = torch.zeros((1,), dtype=torch.int32, device=coords.device)
+    check(lib().pnx_sp3_index_build(ptr(coords), n, ix.batch, _i3(ix.grid), ptr(ix.buf), ix.nbytes, ptr(rows), ptr(count), stream_ptr()),
+          "pnx_sp3_index_build")
+    return ix, (rows[:n] if want_rows else None), count
+
+
+def sp3_out_index(coords_in, batch, grid_in, kernel, stride, pad):
+    """pnx_sp3_out_index: SparseConv3d's output set -> (Sp3Index over the output grid, count (1,) int32 device tensor)."""
+    _need_coords(coords_in)
+    ix = Sp3Index(batch, sp3_out_grid(batch, grid_in, kernel, stride, pad), coords_in.device)
+    count = torch.zeros((1,), dtype=torch.int32, device=coords_in.device)
+    check(lib().pnx_sp3_out_index(ptr(coords_in), coords_in.shape[0], ix.batch, _i3(grid_in), _i3(kernel), _i3(stride), _i3(pad), ptr(ix.buf), ix.nbytes,
+                                  ptr(count), stream_ptr()), "pnx_sp3_out_index")
+    return ix, count
+
+
+def sp3_index_coords(ix, n):
+    """pnx_sp3_index_coords: the set's first n rows [b, z, y, x] in rank order."""
+    coords = torch.empty((max(int(n), 1), 4), dtype=torch.int32, device=ix.buf.device)
+    check(lib().pnx_sp3_index_coords(ptr(ix.buf), ix.nbytes, ix.batch, _i3(ix.grid), ptr(coords), int(n), stream_ptr()), "pnx_sp3_index_coords")
+    return coords[: int(n)]
+
+
+def sp3_neighbor_map(coords_out, ix_in, row_of_rank, kernel, stride, pad):
+    """pnx_sp3_neighbor_map -> (N_out, kd*kh*kw) int32, -1 for an inactive neighbour."""
+    _need_coords(coords_out)
+    T = int(kernel[0]) * int(kernel[1]) * int(kernel[2])
+    m = torch.empty((coords_out.shape[0], T), dtype=torch.int32, device=coords_out.device)
+    check(lib().pnx_sp3_neighbor_map(ptr(coords_out), coords_out.shape[0], ptr(ix_in.buf), ix_in.nbytes, ix_in.batch, _i3(ix_in.grid), ptr(row_of_rank),
+                                     _i3(kernel), _i3(stride), _i3(pad), ptr(m), stream_ptr()), "pnx_sp3_neighbor_map")
+    return m
+
+
+def sp3_pack_weight(w):
+    """(Cout, kd, kh, kw, Cin) fp32 (BN scale folded in) -> (T, round_up(Cin, 4), round_up(Cout, 16)) zero-padded, the layout of pnx_sp3_conv."""
+    co, ci = w.shape[0], w.shape[-1]
+    T = w.shape[1] * w.shape[2] * w.shape[3]
+    n = lib().pnx_sp3_packed_weight_floats(T, ci, co)
+    ci4, co16 = (ci + 3) // 4 * 4, (co + 15) // 16 * 16
+    if n != T * ci4 * co16:
+        raise PnxError(f"sp3_pack_weight: no packing for {tuple(w.shape)}")
+    wp = torch.zeros((T, ci4, co16), dtype=torch.float32, device=w.device)
+    wp[:, :ci, :co] = w.float().reshape(co, T, ci).permute(1, 2, 0)
+    return wp
+
+
+def sp3_conv(x, nbmap, w_packed, shift, cout, residual=None, relu=True):
+    """pnx_sp3_conv: x (N_in, Cin) fp32, nbmap (N_out, T) int32 -> (N_out, cout) fp32."""
+    for t, name in ((x, "x"), (nbmap, "nbmap"), (w_packed, "w_packed"), (shift, "shift")):
+        _need_cuda(t, name)
+    if x.dtype != torch.float32 or w_packed.dtype != torch.float32 or shift.dtype != torch.float32 or nbmap.dtype != torch.int32:
+        raise PnxError("sp3_conv: fp32 features, weights and shift, int32 map")
+    n_out, T = nbmap.shape
+    ci = x.shape[1]
+    if tuple(w_packed.shape) != (T, (ci + 3) // 4 * 4, (cout + 15) // 16 * 16) or shift.numel() < cout:
+        raise PnxError(f"sp3_conv: packed weight {tuple(w_packed.shape)} does not fit {T} taps x {ci} -> {cout}")
+    if residual is not None:
+        _need_cuda(residual, "residual")
+        if residual.dtype != torch.float32 or tuple(residual.shape) != (n_out, cout):
+            raise PnxError("sp3_conv: residual must be (N_out, cout) fp32")
+    y = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
+    check(lib().pnx_sp3_conv(ptr(x), x.shape[0], ci, ptr(nbmap), n_out, T, ptr(w_packed), ptr(shift), ptr(residual), 1 if relu else 0, ptr(y), cout,
+                             stream_ptr()), "pnx_sp3_conv")
+    return y
+
+
+def sp3_dense(feat, coords, batch, grid):
+    """pnx_sp3_dense: rows -> (batch, C*D, H, W) fp32, channel c*D + d, zero elsewhere."""
+    _need_coords(coords)
+    _need_cuda(feat, "feat")
+    if feat.dtype != torch.float32 or feat.dim() != 2 or feat.shape[0] != coords.shape[0]:
+        raise PnxError("sp3_dense: feat must be (N, C) fp32 with one row per coordinate")
+    D, H, W = (int(g) for g in grid)
+    C = feat.shape[1]
+    out = torch.empty((int(batch), C * D, H, W), dtype=torch.float32, device=feat.device)
+    check(lib().pnx_sp3_dense(ptr(feat), ptr(coords), coords.shape[0], C, int(batch), _i3(grid), ptr(out), stream_ptr()), "pnx_sp3_dense")
+    return out

@@ -1,0 +1,225 @@
+"""SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py:9-72, blocks of det3d/models/utils/sparse_conv.py:66-104) on the sparse 3-D HIP
+kernels of csrc/sparse3d.hip (include/pnx.h: pnx_sp3_*).  Eval mode only: the backward of the 3-D layers is not built.
+
+    SparseResNet3D(...).forward(pillar_features (V, C) fp32, coors (V, 4) int32 [b, z, y, x], input_shape [D, H, W]) -> (B, C_out*D', H', W')
+
+Same constructor, state-dict keys and weight layout as the reference (spconv >= 2.2: (Cout, kD, kH, kW, Cin); the older (kD, kH, kW, Cin, Cout)
+is accepted on load).  Each layer is a gather-GEMM over its active sites:
+  - an active set is indexed by a key-order occupancy bitmap + popcount prefix (a site's row = its rank in [b, z, y, x] order, the voxel
+    reader's row order);
+  - SparseConv3d marks the outputs every input x tap reaches (one host sync per strided layer reads their count), SubMConv3d keeps the set;
+  - a neighbour map (N_out, taps) per set and geometry -- shared by the four SubM layers of a stage -- feeds pnx_sp3_conv, which applies the
+    folded BatchNorm, the residual and the ReLU in its epilogue.
+"""
+import math
+
+import torch
+from torch import nn
+
+from . import ops
+from ._lib import PnxError
+from .mvf_encoder import _params_version
+
+
+def _triple(v):
+    return tuple(int(a) for a in v) if isinstance(v, (list, tuple)) else (int(v),) * 3
+
+
+def _spconv3d_weight(w, want):
+    """spconv >= 2.2 stores (Cout, kD, kH, kW, Cin), older releases (kD, kH, kW, Cin, Cout)."""
+    co, kd, kh, kw, ci = want
+    if tuple(w.shape) == want:
+        return w
+    if tuple(w.shape) == (kd, kh, kw, ci, co):
+        return w.permute(4, 0, 1, 2, 3).contiguous()
+    raise RuntimeError(f"cannot map sparse-conv weight {tuple(w.shape)} onto SparseConv3d {want}")
+
+
+class SparseConv3d(nn.Module):
+    """spconv.pytorch.SparseConv3d / SubMConv3d without bias: holds the weight (Cout, kD, kH, kW, Cin) and the geometry."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, subm=False):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding = _triple(kernel_size), _triple(stride), _triple(padding)
+        self.subm = subm
+        self.weight = nn.Parameter(torch.empty((out_channels, *self.kernel_size, in_channels)))
+        bound = 1.0 / math.sqrt(in_channels * math.prod(self.kernel_size))
+        nn.init.uniform_(self.weight, -bound, bound)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = prefix + "weight"
+        if k in state_dict:
+            state_dict[k] = _spconv3d_weight(state_dict[k], tuple(self.weight.shape))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}"
+                + (", subm=True" if self.subm else ""))
+
+
+class SparseConv3dBlock(nn.Module):
+    """sparse_conv.py:66-82: SubMConv3d (stride 1 and use_subm) or SparseConv3d, padding k // 2, + BatchNorm1d(eps 1e-3) + ReLU."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, use_subm=True):
+        super().__init__()
+        self.conv = SparseConv3d(in_channels, out_channels, kernel_size, stride, int(kernel_size) // 2, subm=stride == 1 and use_subm)
+        self.norm = nn.BatchNorm1d(out_channels, eps=1e-3, momentum=0.01)
+        self.act = nn.ReLU()
+
+
+class SparseBasicBlock3d(nn.Module):
+    """sparse_conv.py:85-104: SubM + BN + ReLU, SubM + BN, + identity, ReLU."""
+
+    def __init__(self, channels, kernel_size):
+        super().__init__()
+        self.block1 = SparseConv3dBlock(channels, channels, kernel_size, 1)
+        self.conv2 = SparseConv3d(channels, channels, kernel_size, 1, int(kernel_size) // 2, subm=True)
+        self.norm2 = nn.BatchNorm1d(channels, eps=1e-3, momentum=0.01)
+        self.act2 = nn.ReLU()
+
+
+def _fold(conv, bn):
+    """Eval BatchNorm folded into the conv: packed weight (BN scale baked in) and per-channel shift, fp32."""
+    a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+    w = conv.weight.detach().float() * a.view(-1, 1, 1, 1, 1)
+    shift = (bn.bias.detach().float() - bn.running_mean.detach().float() * a).contiguous()
+    return ops.sp3_pack_weight(w), shift
+
+
+class SparseResNet3D(nn.Module):
+    """Same constructor and keys as the reference (sparse_resnet3d.py:10-47)."""
+
+    def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, num_input_features, kernel_size=[3, 3, 3, 3], out_channels=128):
+        super().__init__()
+        assert len(ds_layer_strides) == len(layer_nums) == len(ds_num_filters)
+        self._layer_strides, self._num_filters, self._layer_nums = list(ds_layer_strides), list(ds_num_filters), list(layer_nums)
+        self._num_input_features = num_input_features
+        in_filters = [num_input_features, *ds_num_filters[:-1]]
+        blocks = []
+        for i, n in enumerate(layer_nums):
+            layers = [SparseConv3dBlock(in_filters[i], ds_num_filters[i], kernel_size[i], ds_layer_strides[i], use_subm=False)]
+            layers += [SparseBasicBlock3d(ds_num_filters[i], kernel_size[i]) for _ in range(n)]
+            blocks.append(nn.Sequential(*layers))
+        self.blocks = nn.ModuleList(blocks)
+        c = ds_num_filters[-1]
+        self.mapping = SparseConv3dBlock(c, out_channels, kernel_size=1, stride=1, use_subm=True)
+        self.extra_conv = nn.Sequential(SparseConv3d(c, c, (3, 1, 1), (2, 1, 1), 0), nn.BatchNorm1d(c, eps=1e-3, momentum=0.01), nn.ReLU())
+        self.profile = None  # a list: every phase of the next forwards appends (name, end event) -- tools/bench_voxel18.py
+
+    # ------------------------------------------------------------------------------------------ plan
+    def _folded(self):
+        """Packed weights and shifts, folded once per parameter version (as mvf_encoder's view nets are)."""
+        f = self.__dict__.get("_folded_cache")
+        if f is None or f[0] != _params_version(self):
+            layers = {}
+            for i, seq in enumerate(self.blocks):
+                layers[f"blocks.{i}.0"] = _fold(seq[0].conv, seq[0].norm)
+                for j, blk in enumerate(seq[1:], 1):
+                    layers[f"blocks.{i}.{j}.block1"] = _fold(blk.block1.conv, blk.block1.norm)
+                    layers[f"blocks.{i}.{j}.conv2"] = _fold(blk.conv2, blk.norm2)
+            layers["extra_conv"] = _fold(self.extra_conv[0], self.extra_conv[1])
+            layers["mapping"] = _fold(self.mapping.conv, self.mapping.norm)
+            f = (_params_version(self), layers)
+            self.__dict__["_folded_cache"] = f
+        return f[1]
+
+    def _tick(self, name):
+        if self.profile is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.profile.append((name, e))
+
+    def _check(self, pillar_features, coors):
+        if self.training:
+            raise PnxError("SparseResNet3D: training is not implemented (the backward of the sparse 3-D layers is not built); call .eval()")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise PnxError("SparseResNet3D: gradients are not implemented (the backward of the sparse 3-D layers is not built); "
+                           "run under torch.no_grad() or freeze the parameters")
+        if pillar_features.dtype != torch.float32:
+            raise PnxError(f"SparseResNet3D: features must be fp32, got {pillar_features.dtype} (there is no bf16 / fp16 form)")
+        if coors.dtype not in (torch.int32, torch.int64) or coors.dim() != 2 or coors.shape[1] != 4:
+            raise PnxError("SparseResNet3D: coors must be (V, 4) integer [b, z, y, x]")
+        if pillar_features.dim() != 2 or pillar_features.shape[0] != coors.shape[0]:
+            raise PnxError("SparseResNet3D: pillar_features must be (V, C) with one row per coordinate")
+        if pillar_features.shape[1] != self._num_input_features:
+            raise PnxError(f"SparseResNet3D: {pillar_features.shape[1]} input channels, the model takes {self._num_input_features}")
+        if not (pillar_features.is_cuda and coors.is_cuda):
+            raise PnxError("SparseResNet3D: features and coords must be CUDA (ROCm) tensors; the sparse 3-D convolution has no CPU implementation")
+
+    def _strided(self, x, coords, ix, rows, B, conv, name):
+        """SparseConv3d: output set (one host sync for its count), its coords, the neighbour map into the input set."""
+        k, s, p = conv.kernel_size, conv.stride, conv.padding
+        oix, cnt = ops.sp3_out_index(coords, B, ix.grid, k, s, p)
+        n = int(cnt.item())
+        oc = ops.sp3_index_coords(oix, n)
+        self._tick(name + ".index")
+        m = ops.sp3_neighbor_map(oc, ix, rows, k, s, p)
+        self._tick(name + ".map")
+        return oix, oc, m
+
+    def _conv(self, x, m, folded, cout, name, residual=None):
+        y = ops.sp3_conv(x, m, folded[0], folded[1], cout, residual=residual, relu=True)
+        self._tick(name + ".conv")
+        return y
+
+    def forward_sparse(self, pillar_features, coors, input_shape, batch_size=None):
+        """The active sets: [(coords (N, 4) int32, features (N, C) fp32, grid (D, H, W))] after stage 0, 1, ..., extra_conv and mapping."""
+        self._check(pillar_features, coors)
+        if batch_size is None:
+            batch_size = len(torch.unique(coors[:, 0]))  # the reference's own rule (:62)
+        B = int(batch_size)
+        grid = tuple(int(v) for v in input_shape)
+        if len(grid) != 3 or min(grid) < 1:
+            raise PnxError(f"SparseResNet3D: input_shape must be [D, H, W], got {list(input_shape)}")
+        coords = coors.int().contiguous()
+        x = pillar_features.contiguous()
+        n = coords.shape[0]
+        self._tick("start")
+        ix, rows, cnt = ops.sp3_index_build(coords, B, grid, want_rows=True)
+        if n:
+            lo, hi = coords.min(0).values, coords.max(0).values
+            ok, distinct = torch.stack([(lo >= 0).all() & (hi < torch.tensor([B, *grid], device=coords.device)).all(), cnt[0] == n]).tolist()
+            if not ok:
+                raise PnxError(f"SparseResNet3D: coords [b, z, y, x] outside the batch of {B} / input_shape {list(grid)}")
+            if not distinct:
+                raise PnxError("SparseResNet3D: coords hold duplicate sites")
+        self._tick("input.index")
+        folded = self._folded()
+        sets = []
+        for i, seq in enumerate(self.blocks):
+            conv = seq[0].conv
+            if conv.subm:
+                m = ops.sp3_neighbor_map(coords, ix, rows, conv.kernel_size, (1, 1, 1), conv.padding)
+                self._tick(f"blocks.{i}.0.map")
+            else:
+                ix, coords, m = self._strided(x, coords, ix, rows, B, conv, f"blocks.{i}.0")
+            rows = None  # a layer's output rows are in rank order
+            x = self._conv(x, m, folded[f"blocks.{i}.0"], conv.out_channels, f"blocks.{i}.0")
+            if len(seq) > 1:
+                k = seq[1].conv2.kernel_size
+                m = ops.sp3_neighbor_map(coords, ix, None, k, (1, 1, 1), tuple(a // 2 for a in k))  # shared by the stage's SubM layers
+                self._tick(f"blocks.{i}.subm.map")
+                for j, blk in enumerate(seq[1:], 1):
+                    y = self._conv(x, m, folded[f"blocks.{i}.{j}.block1"], blk.block1.conv.out_channels, f"blocks.{i}.{j}.block1")
+                    x = self._conv(y, m, folded[f"blocks.{i}.{j}.conv2"], blk.conv2.out_channels, f"blocks.{i}.{j}.conv2", residual=x)
+            sets.append((coords, x, ix.grid))
+        ix, coords, m = self._strided(x, coords, ix, rows, B, self.extra_conv[0], "extra_conv")
+        x = self._conv(x, m, folded["extra_conv"], self.extra_conv[0].out_channels, "extra_conv")
+        sets.append((coords, x, ix.grid))
+        mc = self.mapping.conv
+        m = ops.sp3_neighbor_map(coords, ix, None, mc.kernel_size, (1, 1, 1), mc.padding)
+        self._tick("mapping.map")
+        x = self._conv(x, m, folded["mapping"], mc.out_channels, "mapping")
+        sets.append((coords, x, ix.grid))
+        return sets
+
+    def forward(self, pillar_features, coors, input_shape, batch_size=None):
+        """sparse_resnet3d.py:61-72: x.dense() then view(B, C*D, H, W) -- channel index c*D + d."""
+        if batch_size is None:
+            self._check(pillar_features, coors)
+            batch_size = len(torch.unique(coors[:, 0]))
+        coords, x, grid = self.forward_sparse(pillar_features, coors, input_shape, batch_size)[-1]
+        out = ops.sp3_dense(x, coords, batch_size, grid)
+        self._tick("dense")
+        return out

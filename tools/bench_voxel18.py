@@ -1,0 +1,150 @@
+"""Voxel18 backbone on one MI355X: nuScenes-shaped sweep clouds (synth C2, 4 frames) through VoxelFeatureNet + SparseResNet3D
+(channels 18/36/72/144, the geometry of configs/voxel18_aspp_nusc.yaml), random weights and BN statistics.
+
+Prints the active sites per stage, ms per layer from HIP events (index, neighbour map and convolution separately), backbone ms per frame,
+peak memory, and -- for context -- the same backbone as a torch statement on the GPU (fp32 gather + matmul + index_add_ per tap, neighbours
+from torch.unique / searchsorted).  Usage: python tools/bench_voxel18.py [--frames 4] [--iters 5]"""
+import argparse
+import collections
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from pillarnext_amd import synth  # noqa: E402
+from pillarnext_amd.sparse3d import SparseResNet3D  # noqa: E402
+from pillarnext_amd.voxel_encoder import VoxelFeatureNet  # noqa: E402
+
+NUSC = dict(voxel_size=[0.075, 0.075, 0.2], pc_range=[-50.4, -50.4, -5.0, 50.4, 50.4, 3.0])
+
+
+def _keys(c, grid):
+    D, H, W = grid
+    c = c.long()
+    return ((c[:, 0] * D + c[:, 1]) * H + c[:, 2]) * W + c[:, 3]
+
+
+def torch_layer(coords, x, grid, w, k, s, p, subm, shift, residual=None):
+    """fp32 torch statement of one layer (folded BN): the context number, not a reference."""
+    og = tuple((n + 2 * pp - kk) // ss + 1 for n, kk, ss, pp in zip(grid, k, s, p))
+    dev = x.device
+    taps = [(a, b, d) for a in range(k[0]) for b in range(k[1]) for d in range(k[2])]
+    c = coords.long()
+    sv, pv = torch.tensor(s, device=dev), torch.tensor(p, device=dev)
+    if subm:
+        oc = coords
+    else:
+        cand = []
+        for o in taps:
+            t = c[:, 1:] + pv - torch.tensor(o, device=dev)
+            ok = (t >= 0).all(1) & (t % sv == 0).all(1) & (t // sv < torch.tensor(og, device=dev)).all(1)
+            cand.append(_keys(torch.cat([c[ok, :1], t[ok] // sv], 1), og))
+        u = torch.unique(torch.cat(cand))
+        D, H, W = og
+        oc = torch.stack([u // (D * H * W), u // (H * W) % D, u // W % H, u % W], 1).int()
+    skey, order = torch.sort(_keys(coords, grid))
+    q = oc.long()
+    out = torch.zeros((oc.shape[0], w.shape[0]), dtype=torch.float32, device=dev)
+    for o in taps:
+        pin = q[:, 1:] * sv - pv + torch.tensor(o, device=dev)
+        inside = (pin >= 0).all(1) & (pin < torch.tensor(grid, device=dev)).all(1)
+        key = _keys(torch.cat([q[:, :1], pin.clamp(min=0)], 1), grid)
+        pos = torch.searchsorted(skey, key).clamp(max=skey.numel() - 1)
+        sel = (inside & (skey[pos] == key)).nonzero()[:, 0]
+        out.index_add_(0, sel, x[order[pos[sel]]] @ w[:, o[0], o[1], o[2], :].T)
+    out = out + shift
+    if residual is not None:
+        out = out + residual
+    return oc, torch.relu(out), og
+
+
+def torch_backbone(bb, feats, coords, grid):
+    def fold(conv, bn):
+        a = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
+        return conv.weight * a.view(-1, 1, 1, 1, 1), bn.bias - bn.running_mean * a
+
+    x = feats
+    for seq in bb.blocks:
+        cv = seq[0].conv
+        w0, b0 = fold(cv, seq[0].norm)
+        coords, x, grid = torch_layer(coords, x, grid, w0, cv.kernel_size, cv.stride, cv.padding, False, b0)
+        for blk in seq[1:]:
+            w1, b1 = fold(blk.block1.conv, blk.block1.norm)
+            w2, b2 = fold(blk.conv2, blk.norm2)
+            k = blk.conv2.kernel_size
+            _, y, _ = torch_layer(coords, x, grid, w1, k, (1, 1, 1), (1, 1, 1), True, b1)
+            _, x, _ = torch_layer(coords, y, grid, w2, k, (1, 1, 1), (1, 1, 1), True, b2, residual=x)
+    cv = bb.extra_conv[0]
+    w, b = fold(cv, bb.extra_conv[1])
+    coords, x, grid = torch_layer(coords, x, grid, w, cv.kernel_size, cv.stride, cv.padding, False, b)
+    w, b = fold(bb.mapping.conv, bb.mapping.norm)
+    _, x, _ = torch_layer(coords, x, grid, w, (1, 1, 1), (1, 1, 1), (0, 0, 0), True, b)
+    return x
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=5)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    B = a.frames
+    pts = torch.from_numpy(synth.make_batch("C2", B, "sweep")).cuda()
+    reader = VoxelFeatureNet(**NUSC).cuda()
+    bb = SparseResNet3D([2, 2, 2, 2], [1, 2, 2, 2], [18, 36, 72, 144], 5).cuda().eval()
+    with torch.no_grad():
+        for m in bb.modules():
+            if isinstance(m, torch.nn.BatchNorm1d):
+                m.weight.uniform_(0.5, 1.5), m.bias.uniform_(-0.2, 0.2), m.running_mean.uniform_(-0.2, 0.2), m.running_var.uniform_(0.5, 2.0)
+        feats, coords, grid = reader(pts, B)
+        torch.cuda.synchronize()
+        print(f"# voxel18 backbone, synth C2 sweep x {B} frames ({pts.shape[0]} points), grid {tuple(int(g) for g in grid)}, {feats.shape[0]} voxels")
+        sets = bb.forward_sparse(feats, coords, grid, B)
+        names = ["stage0", "stage1", "stage2", "stage3", "extra_conv", "mapping"]
+        print("active sites:", ", ".join(f"{n} {int(s[0].shape[0])} (grid {s[2]})" for n, s in zip(names, sets)))
+        for _ in range(2):
+            bb(feats, coords, grid, B)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        per = collections.defaultdict(float)
+        walls = []
+        for _ in range(a.iters):
+            bb.profile = []
+            t0 = time.perf_counter()
+            bb(feats, coords, grid, B)
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t0) * 1e3)
+            ev = bb.profile
+            for (_, e0), (name, e1) in zip(ev[:-1], ev[1:]):
+                per[name] += e0.elapsed_time(e1) / a.iters
+            bb.profile = None
+        peak = torch.cuda.max_memory_allocated() - base
+        print("ms per layer (HIP events, mean of %d):" % a.iters)
+        kinds = collections.defaultdict(float)
+        for name, ms in per.items():
+            print(f"  {name:28s} {ms:8.3f}")
+            kinds[name.rsplit(".", 1)[-1]] += ms
+        print("by phase:", ", ".join(f"{k} {v:.3f} ms" for k, v in kinds.items()))
+        walls.sort()
+        print(f"backbone: {walls[len(walls) // 2]:.2f} ms per batch (median wall), {walls[len(walls) // 2] / B:.2f} ms per frame; "
+              f"event sum {sum(per.values()):.2f} ms")
+        print(f"peak memory above inputs: {peak / 2**30:.2f} GiB")
+        torch_backbone(bb, feats, coords, tuple(int(g) for g in grid))
+        torch.cuda.synchronize()
+        tw = []
+        for _ in range(max(1, a.iters // 2)):
+            t0 = time.perf_counter()
+            torch_backbone(bb, feats, coords, tuple(int(g) for g in grid))
+            torch.cuda.synchronize()
+            tw.append((time.perf_counter() - t0) * 1e3)
+        tw.sort()
+        print(f"torch statement (fp32 gather + matmul + index_add_ per tap): {tw[len(tw) // 2]:.2f} ms per batch, {tw[len(tw) // 2] / B:.2f} ms per frame")
+
+
+if __name__ == "__main__":
+    main()
