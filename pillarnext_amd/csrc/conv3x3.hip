@@ -12,7 +12,8 @@
 //                      slots while 8 consumer waves (row groups x 32-channel groups) run the taps; one workgroup per CU
 //   k_conv3x3_lds      stride 1, 64 input channels: 18x34 halo tile staged once in LDS, 1..7 passes of 64 output channels
 //   k_conv3x3_ldsx     stride 1, 128 -> 128 and 256 -> 256: 10x34 tile, 64-channel input slabs through one LDS buffer under live
-//                      accumulators, 128 output channels per pass
+//                      accumulators, 128 output channels per pass; with a mask, 128 -> 128 and 256 -> 256 compute the tile's active pixels
+//                      packed in groups of 32 (PNX_CONV_PACK, default on; see conv_pix_x)
 //   k_sephead_out      block-diagonal 16-output convolution closing the merged SepHead branches (16x16x32 MFMA)
 // Rows/tiles without an active site skip their MFMAs (and, with row_dirty, their HBM traffic) -- that is where the sparsity of
 // the BEV map pays in a dense layout; bias and residual start the accumulators, the epilogue (ReLU, mask, bf16 pack) writes
@@ -575,10 +576,13 @@ __device__ __forceinline__ void conv_taps_rolled(v16f (&acc)[NR][MB], const uint
 #ifndef TAPS_NOBUFW  // (-DTAPS_NOBUFW: per-lane global loads, the A/B reference: profiles/r06_conv_pc_ab.txt)
 #define TAPS_BUFW
 #endif
-template <int NR, int MTALL, int CB = 4, int STRIDE = 1, int MB = 2, int WD = TAPS_WD>
+// PIX (the packed-pixel form of k_conv3x3_ldsx): rbase[0] is not a wave-uniform row base but this lane's own pixels in the NR pixel groups, one
+// pix_code byte per group (byte j: group j), and the slot of every group is recomputed per j from an opaque copy of that word.
+template <int NR, int MTALL, int CB = 4, int STRIDE = 1, int MB = 2, int WD = TAPS_WD, bool PIX = false>
 __device__ __forceinline__ void conv_taps(v16f (&acc)[NR][MB], const uint4* __restrict__ s_in, const uint4* __restrict__ wfrag, const int (&rbase)[4],
                                           int mg, int px, int kb, int lane, int kstep0 = 0) {
 #ifdef PNX_TAPS_ROLLED
+  static_assert(!PIX, "the rolled tap loop has no packed-pixel form");
   conv_taps_rolled<NR, MTALL, CB, STRIDE, MB>(acc, s_in, wfrag, rbase, mg, px, kb, lane, kstep0);
 #else
   constexpr int RS = STRIDE == 1 ? LDS_HW : S2_RS;
@@ -614,6 +618,18 @@ __device__ __forceinline__ void conv_taps(v16f (&acc)[NR][MB], const uint4* __re
   int addr[NR];
   auto group_addr = [&](int grp) {
     const int dx = grp >> 2, cbl = grp & 3;
+    if constexpr (PIX) {
+      int p = rbase[0];
+      asm volatile("" : "+v"(p));
+#pragma unroll
+      for (int j = 0; j < NR; j++) {
+        const int q = (p >> (8 * j)) & 255;
+        const int c = tap_slot<STRIDE>(q & 31, dx);
+        addr[j] = (q >> 5) * (RS * 8) + c * 8 + ((2 * cbl + kb) ^ lds_swz(c));
+        asm volatile("" : "+v"(addr[j]));  // the dy rows stay immediate offsets of one address (hipcc would otherwise distribute the row term over them)
+      }
+      return;
+    }
     int p = px;
     asm volatile("" : "+v"(p));
     const int c = tap_slot<STRIDE>(p, dx);
@@ -947,7 +963,93 @@ __device__ __forceinline__ void conv_rows_x(uint4* __restrict__ s_in, const uint
   }
 }
 
-template <int CIN, int COUT, bool HAS_RES>
+// ---- packed-pixel form (PNX_CONV_PACK, default on with a mask): the active pixels of a tile, listed in row-major order (s_list: pix_code per
+// entry), are cut into groups of 32 and the groups -- not the row segments -- are dealt round-robin to the 2 row groups.  On the LiDAR masks about
+// half the pixels of an active row segment are inactive; packing never makes more groups than there are active rows (ceil(P / 32) <= rows), and
+// on a tile whose rows are all half-empty it halves the MFMA work.  Per output element the k-steps and MFMAs are those of the row form (same
+// accumulator start, same (dx, chunk, dy) order, same epilogue arithmetic): the output is bit-identical.  Only the addressing changes: a lane's B
+// fragments come from its own listed pixel (conv_taps<PIX>), and stores / residual loads are a uniform tile-origin pointer + a 32-bit per-lane
+// pixel offset.  Inactive pixels of active rows are zeroed separately (zero_inactive_pixels), so nothing else of the output contract changes.
+__device__ __forceinline__ int pix_code(int row, int col) { return (row << 5) | col; }
+// byte offset of pixel `code` from the tile origin, channel 0, in an NHWC tensor of CSTRIDE channels and row pitch W pixels
+template <int CSTRIDE>
+__device__ __forceinline__ uint32_t pix_off(int code, int W) { return (uint32_t)(((code >> 5) * W + (code & 31)) * CSTRIDE) * 2u; }
+
+// store_row64 for a pixel group: store d of lane L is chunk L & 7 of listed pixel 8 d + (L >> 3), whose code lanes 0..31 hold (code of lane px = its
+// pixel px of the group); pixels >= n_valid are not stored.  Every store instruction still writes 8 complete 128-byte lines.  Called by all 64 lanes.
+template <int CSTRIDE>
+__device__ __forceinline__ void store_pix64(const uint4 (&D)[4], uint16_t* __restrict__ tile, int code, int n_valid, int W, int lane) {
+  int l = lane;
+  asm volatile("" : "+v"(l));  // opaque: keeps the per-lane permute addresses from being hoisted out of the tile loop (and spilled)
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    const int P = 8 * d + (l >> 3);
+    const int pc = __builtin_amdgcn_ds_bpermute(P << 2, code);
+    if (P < n_valid) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(tile) + pix_off<CSTRIDE>(pc, W) + (uint32_t)((l & 7) * 16)) = D[d];
+  }
+}
+
+// conv_rows_x on NR pixel groups: byte j of `codes` = pix_code of this lane's pixel in group j (lanes px >= n_g[j] carry code 0 and are neither loaded
+// nor stored: one register for all groups keeps the kernel at 256 VGPRs without scratch), ytile / rtile = output / residual at the tile origin
+// (wave-uniform).  One pass of 128 output channels, the same barriers as conv_rows_x.
+template <int NR, int CIN, int COUT, bool HAS_RES>
+__device__ __forceinline__ void conv_pix_x(uint4* __restrict__ s_in, const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
+                                           const float* __restrict__ bias, const uint16_t* __restrict__ rtile, int codes, const int (&n_g)[4],
+                                           uint16_t* __restrict__ ytile, int b, int H, int W, int y0, int x0, uint32_t need, int mg0, int relu, int px,
+                                           int kb, int lane, int hsel) {
+  constexpr int NS = CIN / 64, NRA = NR > 0 ? NR : 1;
+  const int mg = mg0 + 4 * hsel;
+  v16f acc[NRA][2];
+  if (NR > 0) {
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+      const v16f bq = bias_tile(bias, (mg + m) * 32, kb);
+#pragma unroll
+      for (int j = 0; j < NR; j++) acc[j][m] = bq;
+    }
+  }
+  // residual: group 0's lines are requested before the last slab's taps, group j + 1's before group j is packed (as in conv_rows_x)
+  const uint16_t* const rres = HAS_RES ? rtile + mg * 32 : nullptr;
+  auto code = [&](int j) { return (codes >> (8 * j)) & 255; };
+  auto res_off = [&](int j) { return pix_off<COUT>(code(j), W) + (uint32_t)(16 * kb); };
+  const int cw[4] = {codes, 0, 0, 0};
+  uint4 rq[2][2];
+#pragma unroll 1
+  for (int sl = 0; sl < NS; sl++) {
+    if (sl) {
+      __syncthreads();  // previous slab consumed
+      stage_tile64<CIN, L128_TH>(s_in, x, b, H, W, 64 * sl, y0, x0, need);
+      __syncthreads();
+    }
+    if (NR > 0 && HAS_RES && sl == NS - 1) load_residual_u(rq, rres, res_off(0), px < n_g[0]);
+    if (NR > 0) conv_taps<NRA, COUT / 32, CIN / 16, 1, 2, HAS_RES ? LDSX_RES_WD : TAPS_WD, true>(acc, s_in, wfrag, cw, mg, px, kb, lane, 4 * sl);
+  }
+  if (NR > 0) {
+#pragma unroll
+    for (int j = 0; j < NR; j++) {
+      const bool act = px < n_g[j];
+      uint4 rc[2][2];
+      if (HAS_RES) {
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+          for (int t = 0; t < 2; t++) rc[m][t] = rq[m][t];
+        if (j + 1 < NR) load_residual_u(rq, rres, res_off(j + 1), px < n_g[j + 1]);
+      }
+      uint4 D[4];
+#pragma unroll
+      for (int m = 0; m < 2; m++) {
+        uint4 pk[2];
+        pack_tile(acc[j][m], act, relu, pk, HAS_RES ? rc[m] : nullptr);
+        D[2 * m] = pk[0], D[2 * m + 1] = pk[1];
+      }
+      transpose_row64(D, lane);
+      store_pix64<COUT>(D, ytile + mg * 32, code(j), n_g[j], W, lane);
+    }
+  }
+}
+
+template <int CIN, int COUT, bool HAS_RES, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                       const float* __restrict__ bias, const uint16_t* __restrict__ res,
                                                       const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W,
@@ -956,7 +1058,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
   static_assert(CIN % 64 == 0 && (COUT % 128 == 0 || COUT == 64), "64-channel input slabs, 128-channel output passes (or one of 64)");
   constexpr int TH = L128_TH, HW_ = LDS_HW;
   constexpr int NRG = COUT == 64 ? 4 : 2, NRMAX = TH / NRG;  // row groups (the other waves split the 128 output channels of a pass)
+  static_assert(!PACK || (CIN == COUT && NRG == 2), "the packed-pixel form serves 128 -> 128 and 256 -> 256");
   __shared__ uint4 s_in[L128_NSTAGE];
+  __shared__ uint16_t s_list[PACK ? TH * 32 : 1];  // PACK: pix_code of the tile's active pixels, row-major
   __shared__ uint32_t s_rowmask2[2 * TH];  // double-buffered by iteration parity (an empty tile has a single barrier)
   __shared__ unsigned int s_next[2];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1011,11 +1115,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
     const int x0 = tx * 32, y0 = ty * TH;
     const int ox = x0 + px;
     bool was[2];
+    uint32_t bal[2];
 #pragma unroll
     for (int j = 0; j < 2; j++) {  // active sites: one 32-bit column mask per row of the tile, from the bytes requested one tile ago
       was[j] = __builtin_amdgcn_readfirstlane(wasP[j]) != 0;
-      const uint32_t bal = (uint32_t)__ballot(aP[j]);
-      if (lane == 0) s_rowmask[wv * 2 + j] = bal;
+      bal[j] = (uint32_t)__ballot(aP[j]);
+      if (lane == 0) s_rowmask[wv * 2 + j] = bal[j];
     }
     __syncthreads();  // row masks visible; everybody is done reading the previous tile's s_in
     idxC = sched_next2(s_next, it, slot, idxB);
@@ -1038,6 +1143,65 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
       if (row_dirty != nullptr && oy < H && lane == 0 && was[j] != active) row_dirty[((int64_t)b * H + oy) * tiles_x + tx] = active ? 1 : 0;
     }
     if (am == 0) continue;  // uniform over the workgroup
+    if constexpr (PACK) {
+      // the list: every wave enters the active pixels of its own 2 rows, at the count of active pixels in the rows above (lanes 0..7 hold the row masks)
+      const int wvu = __builtin_amdgcn_readfirstlane(wv);
+      int n_px = 0, pos = 0;
+#pragma unroll
+      for (int k = 0; k < TH; k++) {
+        const int n = __builtin_popcount(__builtin_amdgcn_readlane(my_rm, k));
+        n_px += n;
+        pos += k < 2 * wvu ? n : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        if (kb == 0 && ((bal[j] >> px) & 1u)) s_list[pos + __builtin_popcount(bal[j] & ((1u << px) - 1u))] = (uint16_t)pix_code(wvu * 2 + j, px);
+        pos += __builtin_popcount(bal[j]);
+      }
+      // groups of 32 listed pixels, dealt round-robin to the 2 row groups: group rg + 2 j is this wave's j-th (at most TH / 2 of them)
+      const int n_grp = (n_px + 31) >> 5, rgu = __builtin_amdgcn_readfirstlane(rg);
+      const int nr = n_grp > rgu ? (n_grp - rgu + 1) >> 1 : 0;
+      const uint32_t need = am | (am << 1) | (am << 2);  // halo rows some active row reads
+      stage_tile64<CIN, TH>(s_in, x, b, H, W, 0, y0, x0, need);
+      __syncthreads();  // also publishes s_list
+      int codes = 0, n_g[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int g = rgu + 2 * j;
+        n_g[j] = min(max(n_px - 32 * g, 0), 32);
+        if (j < nr && px < n_g[j]) codes |= (int)s_list[32 * g + px] << (8 * j);  // lanes past the last pixel read pixel (0, 0) and are not stored
+      }
+      const int64_t t0 = (((int64_t)b * H + y0) * W + x0) * COUT;  // tile origin
+#define PNX_PIX_X(N_) conv_pix_x<N_, CIN, COUT, HAS_RES>(s_in, x, wfrag, bias, HAS_RES ? res + t0 : nullptr, codes, n_g, y + t0, b, H, W, y0, x0, need, mg0, relu, px, kb, lane, hsel)
+      switch (nr) {  // wave-uniform; every case runs the same barriers
+        case 0: PNX_PIX_X(0); break;
+        case 1: PNX_PIX_X(1); break;
+        case 2: PNX_PIX_X(2); break;
+        case 3: PNX_PIX_X(3); break;
+        default: PNX_PIX_X(4); break;
+      }
+#undef PNX_PIX_X
+      // inactive pixels of active rows: the row form stores their zeros with the row; here they are zeroed (this pass's 128 channels) where the row
+      // segment may hold stale values (row_dirty; without one, always).  After the pass's stores: a store ahead of the tap loop's loads would stall them.
+      // Lane L writes chunk L & 15 of pixel c0 + (L >> 4): a store instruction covers 4 consecutive pixels x 256 bytes = 8 complete 128-byte lines.
+      int l = lane;
+      asm volatile("" : "+v"(l));  // opaque: the per-lane offset is recomputed here, not held across the tap loop
+      const uint32_t cols = W - x0 >= 32 ? 0xffffffffu : (1u << (W - x0)) - 1u;  // columns inside the image
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const int rr = wvu * 2 + j;
+        const uint32_t idle = ~bal[j] & cols;  // inactive pixels of the row (wave-uniform)
+        if (!((am >> rr) & 1u) || !was[j] || y0 + rr >= H || idle == 0) continue;
+        char* const row = reinterpret_cast<char*>(y + t0) + (uint32_t)(rr * W * COUT * 2 + hsel * 256);
+#pragma unroll 1
+        for (int c0 = 0; c0 < 32; c0 += 4) {
+          if (((idle >> c0) & 15u) == 0) continue;
+          const int p = c0 + (l >> 4);
+          if ((idle >> p) & 1u) *reinterpret_cast<uint4*>(row + (uint32_t)(p * COUT * 2 + (l & 15) * 16)) = make_uint4(0, 0, 0, 0);
+        }
+      }
+      continue;
+    }
     int nr = 0;
     int rbase[4], rrow[4];
     {  // the active rows, dealt round-robin to the 2 row groups
@@ -1077,12 +1241,25 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
   sched_done(slot);
 }
 
+// pack: the packed-pixel form (masked 128 -> 128 / 256 -> 256 only; the caller decides)
 template <int CIN, int COUT>
 int launch_ldsx(const void* x, const void* wfrag, const float* bias, const void* res, const uint8_t* mask, void* y, int B, int H, int W, int relu,
-                uint8_t* row_dirty, const int32_t* tlist, const int32_t* tcount, hipStream_t st) {
+                uint8_t* row_dirty, const int32_t* tlist, const int32_t* tcount, hipStream_t st, bool pack = false) {
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   int64_t nb = (int64_t)B * ((H + L128_TH - 1) / L128_TH) * ((W + 31) / 32) * ((COUT + 127) / 128);  // work units = (tile, pass)
   if (nb > 512) nb = 512;  // resident workgroups: 2 per CU (registers)
+  if constexpr (CIN == COUT) {
+    if (pack && mask != nullptr) {
+      if (res != nullptr)
+        k_conv3x3_ldsx<CIN, COUT, true, true><<<(unsigned)nb, 256, 0, st>>>((const uint16_t*)x, (const uint4*)wfrag, bias, (const uint16_t*)res, mask,
+                                                                          (uint16_t*)y, B, H, W, relu, row_dirty, slot, tlist, tcount);
+      else
+        k_conv3x3_ldsx<CIN, COUT, false, true><<<(unsigned)nb, 256, 0, st>>>((const uint16_t*)x, (const uint4*)wfrag, bias, nullptr, mask, (uint16_t*)y, B, H,
+                                                                           W, relu, row_dirty, slot, tlist, tcount);
+      PNX_LAUNCH_CHECK();
+      return PNX_OK;
+    }
+  }
   if (res != nullptr)
     k_conv3x3_ldsx<CIN, COUT, true><<<(unsigned)nb, 256, 0, st>>>((const uint16_t*)x, (const uint4*)wfrag, bias, (const uint16_t*)res, mask, (uint16_t*)y,
                                                                  B, H, W, relu, row_dirty, slot, tlist, tcount);
@@ -1692,9 +1869,11 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
       }
     }
     if (cin == 64 && cout == 64) return launch_lds<64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
-    if (cin == 128 && cout == 128) return launch_ldsx<128, 128>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
+    // PNX_CONV_PACK (default 1): masked 128 -> 128 and 256 -> 256 on the packed-pixel form of k_conv3x3_ldsx; 0: the row form (the cross-check)
+    static const bool pack = getenv("PNX_CONV_PACK") == nullptr || atoi(getenv("PNX_CONV_PACK")) != 0;
+    if (cin == 128 && cout == 128) return launch_ldsx<128, 128>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st, pack);
     if (cin == 256 && cout == 64) return launch_ldsx<256, 64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
-    if (cin == 256 && cout == 256) return launch_ldsx<256, 256>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
+    if (cin == 256 && cout == 256) return launch_ldsx<256, 256>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st, pack);
     if (cin == 64 && cout == 384) return launch_lds<384>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
     if (cin == 64 && cout == 320) return launch_lds<320>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
     if (cin == 64 && cout == 448) return launch_lds<448>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
