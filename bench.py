@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- PillarNeXt-B inference frames/s on synthetic nuScenes-shaped clouds (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A step = one batch of `--batch` frames through the whole path with inputs already resident in HBM:
   HIP reader (voxelize + PFN + dense bf16 canvas)  ->  dense masked ResNet-18 + ASPP + CenterHead (PyTorch-ROCm + HIP conv kernels,
@@ -9,7 +9,10 @@ A step = one batch of `--batch` frames through the whole path with inputs alread
   beside that batch's convolutions: PNX_DECODE_STREAM=0 keeps one stream).  FOUR different frame batches rotate through the loop.
 `--gpus N` without WORLD_SIZE in the environment re-launches itself under torch.distributed.run with N ranks (one per GPU, RCCL);
 under a launcher (RANK/LOCAL_RANK/WORLD_SIZE set) it is one rank.  Frames are sharded by rank, there is no collective on the path
-("replicas only"); time = max over ranks between barriers.  Rank 0 prints ONE JSON line.  Extra objects:
+("replicas only"); time = max over ranks between barriers.  Rank 0 prints ONE JSON line.
+A plain run does what the line's `value` needs -- set-up, warm-up, the K timed steps, --dump-outputs -- and reports beside it only what the
+timed steps measure themselves: host_enqueue_ms_per_step and the reader's in-loop roofline / roofline_fill / roofline_pfn.  Everything else
+below takes runs of its own and comes with `--full` (without it roofline.back_to_back and cpu_baseline are null).  Extra objects:
   roofline        the READER (all of its kernels): algorithmic bytes (24*N + nx*ny*64*2) * frames per launch over the time
                   from the reader's first to its last kernel, HIP events recorded on the reader's own stream inside libpnx_hip.so
   roofline_fill   its dominant interval (span grouping + PFN kernel with the canvas zero-fill kernel beside it on a second stream, HBM-write
@@ -24,7 +27,7 @@ under a launcher (RANK/LOCAL_RANK/WORLD_SIZE set) it is one rank.  Frames are sh
   value_train_fp32 / train_fp32   the same step at the reference's precision (fp32 channels_last; 3x3 layers as three bf16 products accumulated in fp32 on the HIP kernels, the rest on MIOpen fp32, immediate mode); N = 1 only;
                   PNX_BENCH_NO_TRAIN_FP32=1 skips it (MIOpen compiles its fp32 kernels for ~3.5 minutes on a fresh box)
   value_uniform / roofline_uniform   frames/s on the worst-case uniform cloud (~1.2 points per pillar) and the reader's in-loop roofline on it
-  ranks           per-rank ms/step (min / max) and the world size the backend reports; N > 1 runs the short form (value, roofline, value_train)
+  ranks           per-rank ms/step (min / max) and the world size the backend reports; N > 1 with --full runs the short form (value, roofline, value_train)
   value_c4/_c5    frames/s of the Waymo detector (configs/pillarnext_b_waymo.yaml) at BASELINE configs[3] / [4]: 180 k points bf16, 540 k fp16
   sections_us     reader / backbone / neck / head / decode+NMS per step (torch.cuda events, separate short pass)
   nms_us          stand-alone batched rotated NMS on SURVEY 8d's box sets
@@ -57,18 +60,21 @@ def parse():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--dist", default="sweep", choices=["uniform", "sweep"],
                     help="sweep = ring-structured 10-sweep cloud (BASELINE configs[1]); uniform = worst case, ~1.2 points per pillar")
-    ap.add_argument("--cpu-frames", type=int, default=24, help="frames of the bounded one-thread CPU-baseline sample (0 = skip all CPU legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: back-to-back reader calls, the uniform / H2D-merge / Waymo / training legs, "
+                         "sections, NMS, the backbone roofline and the CPU baselines (default: set-up, warm-up, timed steps, outputs, the line)")
+    ap.add_argument("--cpu-frames", type=int, default=24, help="with --full: frames of the bounded one-thread CPU-baseline sample (0 = skip all CPU legs)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--dry-run", action="store_true",
                     help="launch/rendezvous/timing/JSON plumbing only, no GPU work (CPU test of the --gpus path, backend gloo)")
-    ap.add_argument("--include-h2d", action="store_true", help="also time the loop with the COLLATED frames uploaded from pinned host memory each step (no merge)")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_uniform / sections / NMS / CPU legs (profiling runs)")
-    ap.add_argument("--no-back-to-back", action="store_true", help="skip the 15 back-to-back reader calls behind the timed loop (PMC passes: every reader call is then an in-loop call)")
+    ap.add_argument("--include-h2d", action="store_true", help="with --full: also time the loop with the COLLATED frames uploaded from pinned host memory each step (no merge)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_uniform / sections / NMS / CPU legs (profiling runs)")
+    ap.add_argument("--no-back-to-back", action="store_true", help="with --full: skip the 15 back-to-back reader calls behind the timed loop (PMC passes: every reader call is then an in-loop call)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="ranks beyond the visible GPUs share devices (rank r -> cuda:(r mod device_count)): runs the N-rank path with real kernels on a 1-GPU box (use --backend gloo)")
     ap.add_argument("--leg", default="", choices=["", "train_fp32", "train_bf16"],
                     help="internal: run ONE leg in this process and print its dict as a JSON line (the fp32 training leg runs in a child process with a clean MIOpen environment)")
-    ap.add_argument("--all-legs", action="store_true", help="with --gpus > 1: also run the uniform / H2D-merge / Waymo legs (default: value, roofline, value_train only, so that an 8-rank run stays short)")
+    ap.add_argument("--all-legs", action="store_true", help="with --gpus > 1 and --full: also run the uniform / H2D-merge / Waymo legs (default: value, roofline, value_train only, so that an 8-rank run stays short)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed loop, write the detections of its last step to DIR/<name>.npy (see dump_outputs); rank r > 0 prefixes rank<r>_")
     a = ap.parse_args()
@@ -588,7 +594,7 @@ def main():
         # power / cache state in which the reader's kernels run 12-20 % slower (profiles/r04_reader_between.txt); `roofline` is the in-loop figure
         ny_, nx_ = (int(v) for v in model.reader.grid_size)
         rb_us, cb_us, nb_ = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_int32(0)
-        if not a.no_back_to_back:
+        if a.full and not a.no_back_to_back:
             # into the SAME canvas / occupancy buffers the timed loop writes (the launch plan's persistent ones): a freshly allocated 3.2 GB canvas
             # made this figure bimodal from run to run (617 or ~700 us, with or without the decoder stream; where the allocator places it)
             bbp = model._backbone_plan(a.batch, dev) if model._plan_ok() else None
@@ -606,7 +612,7 @@ def main():
 
         extras = {}
         short = world > 1 and not a.all_legs   # an N-rank run: value, roofline and value_train only (DESIGN.md section 7 gives its expected wall time)
-        if not a.no_extras and not short:
+        if a.full and not a.no_extras and not short:
             other = "uniform" if a.dist == "sweep" else "sweep"
             ex2 = make_examples(other)
             for i in range(ROTATE):
@@ -691,7 +697,7 @@ def main():
                     del wm, wex
                     torch.cuda.empty_cache()
             # the training step (BASELINE configs[2]: 4 frames per GPU), timed by this run: value_train / roofline_train
-        if not a.no_extras:
+        if a.full and not a.no_extras:
             if a.config == "C2" and not os.environ.get("PNX_BENCH_NO_TRAIN"):
                 # N = 1: both training legs in child processes with MIOpen's default solver set (train_child_leg); N > 1: in process, under DDP
                 extras.update(train_child_leg(dev, "train_bf16") if world == 1 else train_leg(dev, rank, world))
@@ -755,7 +761,7 @@ def main():
                      "frac": round(reader_gbs / HBM_PEAK_GBS, 4) if reader_gbs else None, "traffic": traffic, "traffic_source": tsrc, "traffic_condition": tcond,
                      "algorithmic_bytes_per_launch": reader_bytes, "kernel_us": round(r_us.value, 2), "samples": ns.value,
                      "voxelize_us": round(vox_us, 2),
-                     "back_to_back": None if a.no_back_to_back else {"kernel_us": round(rb_us.value, 2), "frac": round(reader_bytes / rb_us.value / 1e3 / HBM_PEAK_GBS, 4) if rb_us.value > 0 else None,
+                     "back_to_back": None if a.no_back_to_back or not a.full else {"kernel_us": round(rb_us.value, 2), "frac": round(reader_bytes / rb_us.value / 1e3 / HBM_PEAK_GBS, 4) if rb_us.value > 0 else None,
                                       "note": "the same reader calls with nothing else on the GPU between them (12 calls); frac above is measured inside the detector's loop"}},
         "roofline_fill": {"bound": "hbm", "kernel": "k_span_pfn (span grouping + PFN: the pillar cells) and k_canvas_fill_bytes (every pillar-free tile) running concurrently, fork to join",
                           "achieved": round(fill_gbs, 1) if fill_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -767,7 +773,7 @@ def main():
     }
     res.update(extras)
     if rank == 0:
-        if world == 1 and a.cpu_frames > 0 and not a.no_extras:
+        if a.full and world == 1 and a.cpu_frames > 0 and not a.no_extras:
             res["cpu_baseline"] = cpu_baselines(cfg, a.config, a.dist, a.cpu_frames)
         else:
             res["cpu_baseline"] = None

@@ -40,7 +40,7 @@ def test_gpus_2_with_real_kernels_on_one_gpu():
     """The N-rank path on hardware: `bench.py --gpus 2` respawns under torch.distributed.run, both ranks rendezvous (gloo: a 1-GPU box has no second
     device for RCCL) and run the real detector on cuda:0 (--share-gpu), frames sharded by rank, barrier-bracketed timed loop, max over ranks, ONE JSON
     line from rank 0 -- plus one DDP + SyncBN training step (2 x 1 frame) through the same process group.  The short N > 1 form: no Waymo / uniform legs."""
-    r = run(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--batch", "2", "--steps", "2", "--warmup", "1"],
+    r = run(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--batch", "2", "--steps", "2", "--warmup", "1", "--full"],
             {"PNX_BENCH_TRAIN_FRAMES": "1", "PNX_BENCH_TRAIN_STEPS": "1", "PNX_BENCH_TRAIN_WARMUP": "1", "MIOPEN_FIND_MODE": "2"}, timeout=900)
     assert r["n_gpus"] == 2 and r["steps"] == 2 and r["config"]["global_batch"] == 4 and r["config"]["parallelism"] == "frame-sharded replicas x2"
     assert r["ranks"]["world_size_seen_by_backend"] == 2 and r["ranks"]["ms_per_step_min"] <= r["ranks"]["ms_per_step_max"]
@@ -72,13 +72,23 @@ def test_dump_outputs_holds_the_last_timed_step(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_the_timed_loop_only():
+    """Without --full the run is set-up, warm-up, the timed steps and the line: none of the legs that take runs of their own."""
+    r = run(["--batch", "2", "--steps", "2", "--warmup", "1"], {"PNX_NO_MIOPEN_BENCH": "1"}, timeout=900)
+    assert r["value"] > 0 and r["ms_per_step"] > 0 and r["unit"] == "frames/s" and r["higher_is_better"] and r["dtype"] == "bf16"
+    assert r["roofline"]["frac"] > 0 and r["roofline"]["back_to_back"] is None and r["cpu_baseline"] is None and r["detections_last_step"] > 0
+    legs = ("value_uniform", "value_with_h2d_merge", "value_c4", "value_c5", "value_train", "value_train_fp32", "sections_us", "nms_us", "roofline_backbone")
+    assert not [k for k in legs if k in r]
+
+
+@pytest.mark.gpu
 def test_gpus_2_over_rccl_when_two_devices_are_visible():
     """The same line over RCCL (backend nccl, one rank per GPU): runs wherever >= 2 devices are visible -- the boxes this repository is developed on have
     one, so there it skips and the gloo form above is what exercises the N-rank path."""
     torch = pytest.importorskip("torch")
     if torch.cuda.device_count() < 2:
         pytest.skip("needs 2 GPUs (RCCL refuses two ranks on one device)")
-    r = run(["--gpus", "2", "--backend", "nccl", "--batch", "2", "--steps", "2", "--warmup", "1"],
+    r = run(["--gpus", "2", "--backend", "nccl", "--batch", "2", "--steps", "2", "--warmup", "1", "--full"],
             {"PNX_BENCH_TRAIN_FRAMES": "1", "PNX_BENCH_TRAIN_STEPS": "1", "PNX_BENCH_TRAIN_WARMUP": "1", "MIOPEN_FIND_MODE": "2", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=1200)
     assert r["n_gpus"] == 2 and r["ranks"]["backend"] == "nccl" and r["ranks"]["world_size_seen_by_backend"] == 2
     assert r["value"] > 0 and r["value_train"] > 0 and r["train"]["loss_finite"]

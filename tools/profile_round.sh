@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats -d $O/bench_trace -o p -- python $R/bench.py --steps 6 --warmup 4 --no-extras > $O/bench_trace.json 2> $O/bench_trace.err
+timeout 400 rocprofv3 --kernel-trace --stats -d $O/bench_trace -o p -- python $R/bench.py --steps 6 --warmup 4 --full --no-extras > $O/bench_trace.json 2> $O/bench_trace.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/reader_trace -o p -- python $R/tools/reader_ab.py --exact "spans default" --batch $BATCH --iters 20 > $O/reader_trace.log 2>&1
 # PMC passes in the condition bench.py's roofline.frac is measured in: the reader calls of the detector's loop (bench.py --no-extras --no-back-to-back:
 # every reader call of the process follows a step's convolutions), each counter in its own run with nothing but --kernel-trace
