@@ -399,6 +399,9 @@ int pnx_boxes_aligned_iou_bev_cpu(const float* boxes_a_host, const float* boxes_
  *                 k-th kept box, ascending -- exactly what nms_gpu writes into `keep`
  *   keep_count    int32[num_segments]: number kept (already min'ed with post_max if post_max > 0)
  *   max_seg_len   an upper bound on any segment's length (host value; sizes the launch)
+ *   workspace     pnx_nms_workspace_bytes(total_boxes, num_segments, max_seg_len) bytes, 8-byte aligned.  The box count is known on the device only, so
+ *                 pnx_nms_rotated_batched checks what the host can: workspace_bytes below pnx_nms_workspace_bytes(1, num_segments, max_seg_len) -- its
+ *                 layout plus the mask words of ONE box -- is PNX_ERR_WORKSPACE; sizing it for all boxes stays the caller's duty.
  */
 size_t pnx_nms_workspace_bytes(int64_t total_boxes, int32_t num_segments, int32_t max_seg_len);
 /* Test hook: capacity (entries) of the rotated NMS's candidate-pair list, 0 = the default (32 per box); returns the previous value.  A small list sends

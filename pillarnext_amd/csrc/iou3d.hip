@@ -410,15 +410,19 @@ int nms_batched(const float* boxes, const int32_t* seg_offsets, const int32_t* s
   PNX_REQUIRE(num_segments <= 65535, PNX_ERR_UNSUPPORTED, "more than 65535 segments");
   const int cbmax = (max_seg_len + 63) / 64;
   PNX_REQUIRE(cbmax * 8 <= 64 * 1024, PNX_ERR_UNSUPPORTED, "segment longer than 524288 boxes");
-  // workspace_bytes is validated by the caller against pnx_nms_workspace_bytes(total, ...): we cannot know
-  // `total` here without reading seg_offsets back, so only the alignment is checked.
+  // the caller sizes the workspace with pnx_nms_workspace_bytes(total, ...); `total` lives in seg_offsets on the device, so here the alignment is checked
+  // and, for the rotated form below, the layout plus one box's row of mask words (the least any call with a box in it needs)
   PNX_REQUIRE(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= 8, PNX_ERR_WORKSPACE, "bad workspace");
   uint64_t* mask = (uint64_t*)workspace;
   dim3 grid(cbmax, cbmax, num_segments);
   if (ROTATED) {
     // workspace = [segment slots of BoxPre | pair list | overflow tile list | counters | mask words]; every size is known on the host
     const NmsLayout lay = nms_layout(num_segments, max_seg_len);
-    PNX_REQUIRE(workspace_bytes > lay.mask_off + 8, PNX_ERR_WORKSPACE, "workspace smaller than pnx_nms_workspace_bytes");
+    // the mask words behind the layout: box gi owns the cbmax words mask[gi * cbmax ..] (k_box_pre, k_nms_pairs, k_nms_greedy).  The number of boxes lives in
+    // seg_offsets on the device; what the host knows is that a call with a box in it has at least one such row, i.e. at least
+    // pnx_nms_workspace_bytes(1, num_segments, max_seg_len): anything below that cannot hold the mask of ANY non-empty call
+    PNX_REQUIRE(workspace_bytes >= lay.mask_off + (size_t)cbmax * sizeof(uint64_t) + 8, PNX_ERR_WORKSPACE,
+                "workspace smaller than pnx_nms_workspace_bytes(1, num_segments, max_seg_len): no room for one box's mask words");
     PNX_REQUIRE(max_seg_len < (1 << 20) && (size_t)num_segments * cbmax * (cbmax + 1) / 2 <= ((size_t)1 << 24), PNX_ERR_UNSUPPORTED,
                 "rotated NMS: segments of at most 2^20 boxes, at most 2^24 mask tiles in all");
     char* wsb = reinterpret_cast<char*>(workspace);

@@ -37,13 +37,14 @@ def test_lazy_kernel_equals_dense_convolutions_at_the_cells(shape, pre_max, lens
 
     B, H, W = shape
     g = torch.Generator(device="cuda").manual_seed(5)
-    tasks, dense = [], []
+    tasks, dense, raw = [], [], []
     for ti in range(2):                                                                               # two tasks of one class each
         W1, b1, W2, b2 = _weights(3 + ti)
         up = torch.randn((B, 64, H, W), device="cuda", generator=g).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         t = torch.relu(torch.nn.functional.conv2d(up.float(), W1, b1, padding=1)).to(torch.bfloat16).float()
         dense.append(torch.nn.functional.conv2d(t, W2, b2, padding=1).to(torch.bfloat16).float().permute(0, 2, 3, 1).reshape(-1, 10))
         tasks.append((up, ops.conv3x3_pack_weights(W1), b1, ops.sephead_lazy_pack_w2(_w2m(W2)), b2))
+        raw.append((up, W1, b1, W2, b2))
     S = 2 * B
     local = torch.randint(0, B * H * W, (S, pre_max), device="cuda", generator=g)
     local[:, :4] = torch.tensor([0, W - 1, (H - 1) * W, B * H * W - 1], device="cuda")                # the four kinds of corner
@@ -56,6 +57,21 @@ def test_lazy_kernel_equals_dense_convolutions_at_the_cells(shape, pre_max, lens
     torch.testing.assert_close(got, ref, rtol=2e-2, atol=2e-2)
     assert float((got == ref).float().mean()) > 0.8
     assert torch.equal(got, ops.sephead_lazy(tasks, [0, 1], B, local, seg_len, pre_max))              # deterministic
+    # the fp64 bar of tests/test_gpu_tail_kernels_at_scale.py holds at these shapes too: every candidate against fp64 on the bf16 operands
+    from test_gpu_tail_kernels_at_scale import BF_REL, FRO_MARGIN, OUT_ROUND, TINY, _lazy_ref
+
+    num = den = 0.0
+    for ti in range(2):
+        v = valid[ti::2]
+        if not bool(v.any()):
+            continue
+        r64, mag, flip = _lazy_ref(*raw[ti], local[ti::2][v], torch.bfloat16)
+        g64 = got[ti::2][v].double()
+        assert bool(((g64 - r64).abs() <= BF_REL * mag + OUT_ROUND[torch.bfloat16] * r64.abs() + flip + TINY).all()), ti
+        num += float(((g64 - r64) ** 2).sum())
+        den += float(((r64.float().to(torch.bfloat16).double() - r64) ** 2).sum())
+    print(f"lazy kernel {shape}: Frobenius error / once-rounded fp64 reference {(num / den) ** 0.5:.4f}")
+    assert num <= FRO_MARGIN ** 2 * den
 
 
 def _fused(lazy):
