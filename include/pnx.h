@@ -604,7 +604,21 @@ size_t pnx_lazy_decode_bytes(void);
  * pnx_sp3_conv: y (n_out, cout) = relu?(sum over taps and cin of x[map[row][t]][c] * w[t][c][:] + shift (+ residual (n_out, cout))),
  *   fp32 in and out on the fp32 matrix cores, every row reduced in one fixed order (bit-identical run to run).  w_packed is
  *   (T, round_up(cin, 4), round_up(cout, 16)) fp32 = pnx_sp3_packed_weight_floats, zero-padded, BatchNorm scale folded in; cout <= 144.
- * pnx_sp3_dense: out (batch, channels*D, H, W) fp32 zero-filled, then out[b][c*D + z][y][x] = feat[row][c] (x.dense().view(B, C*D, H, W)). */
+ * pnx_sp3_dense: out (batch, channels*D, H, W) fp32 zero-filled, then out[b][c*D + z][y][x] = feat[row][c] (x.dense().view(B, C*D, H, W)).
+ * Training (gradients of y[o] = sum_t w[:, t, :] . x[map[o][t]]):
+ * pnx_sp3_conv_train: pnx_sp3_conv with another fixed summation order, for the training graph (forward and data gradient): every tap is summed
+ *   from zero on its own and the taps are added in tap order, the tree of a matmul per tap.  A row with t taps has chains 1/t as long as in
+ *   pnx_sp3_conv and about 1/sqrt(t) of its rounding error; bit-identical run to run, not bit-identical to pnx_sp3_conv.
+ * pnx_sp3_transpose_map: tmap (n_in, T) int32 with tmap[map[o][t]][t] = o and -1 elsewhere (an input row and tap reach at most one output
+ *   row).  The data gradient dx (n_in, cin) is pnx_sp3_conv_train on dy, tmap and the weights packed the other way round ((T, round_up(cout, 4),
+ *   round_up(cin, 16))), zero shift, no ReLU.  A submanifold layer needs no tmap: tmap[i][t] = map[i][T - 1 - t].
+ * pnx_sp3_wgrad: dw (cout, T, cin) fp32 = sum over output rows o of dy[o][co] * x[map[o][t]][ci] on the fp32 matrix cores; cin, cout <= 144.
+ *   Rows are split statically: with tiles = ceil(cout / 16), mt = tiles if tiles <= 3, else 3 if tiles % 3 == 0, else 2 if tiles % 2 == 0,
+ *   else 3, groups = ceil(tiles / mt) and p0 = max(1, 256 / groups), a workgroup owns R = clamp(round_up(ceil(n_out / p0), 16), 256, 4096)
+ *   consecutive rows, which one wave per tap accumulates in row order, 16 rows per K step; the P = ceil(n_out / R) fp32 partials
+ *   (workspace = pnx_sp3_wgrad_workspace_bytes = P * T * cin * cout floats, at least 256 bytes) are added in index order by a second
+ *   kernel.  No floating-point atomics: bit-identical run to run.
+ * pnx_sp3_dense_backward: dfeat (n, channels)[row][c] = dout[b][c*D + z][y][x], the gradient of pnx_sp3_dense. */
 size_t pnx_sp3_index_bytes(int32_t batch, const int32_t* grid3_host);
 int pnx_sp3_index_build(const int32_t* coords, int64_t n, int32_t batch, const int32_t* grid3_host, void* index, size_t index_bytes, int32_t* row_of_rank,
                         int32_t* count, pnx_stream_t stream);
@@ -620,8 +634,16 @@ int pnx_sp3_neighbor_map(const int32_t* coords_out, int64_t n_out, const void* i
 size_t pnx_sp3_packed_weight_floats(int32_t taps, int32_t cin, int32_t cout);
 int pnx_sp3_conv(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
                  const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream);
+int pnx_sp3_conv_train(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
+                       const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream);
 int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* out,
                   pnx_stream_t stream);
+int pnx_sp3_transpose_map(const int32_t* map, int64_t n_out, int32_t taps, int64_t n_in, int32_t* tmap, pnx_stream_t stream);
+size_t pnx_sp3_wgrad_workspace_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout);
+int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, int32_t cout, const int32_t* map, int64_t n_out, int32_t taps, float* dw,
+                  void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+int pnx_sp3_dense_backward(const float* dout, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* dfeat,
+                           pnx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,14 @@
-// sparse3d.hip -- sparse 3-D convolution for SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py, utils/sparse_conv.py:66-104), eval mode:
+// sparse3d.hip -- sparse 3-D convolution for SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py, utils/sparse_conv.py:66-104):
 //   pnx_sp3_index_build   key-order occupancy bitmap + popcount word prefix of an active set (the index)
 //   pnx_sp3_out_index     index of the output set of SparseConv3d: every input x tap sets the bit of the output it reaches
 //   pnx_sp3_index_coords  the set's [b, z, y, x] rows in key (= rank) order
 //   pnx_sp3_neighbor_map  (N_out, T) input row per output site and tap, -1 where the neighbour is inactive
 //   pnx_sp3_conv          gather-GEMM on the fp32 matrix cores + folded BN shift (+ residual) (+ ReLU)
 //   pnx_sp3_dense         rows -> zero-initialised (B, C*D, H, W), channel c*D + d (x.dense().view(B, C*D, H, W), :67-71)
+// and, for training:
+//   pnx_sp3_transpose_map   tmap (N_in, T): tmap[map[o][t]][t] = o, -1 elsewhere -- the data gradient is pnx_sp3_conv_train on dy, tmap and w^T
+//   pnx_sp3_wgrad           dw[co][t][ci] = sum_o dy[o][co] * x[map[o][t]][ci]: split-K gather-GEMM, fp32 partials added in a fixed order
+//   pnx_sp3_dense_backward  the gather that undoes pnx_sp3_dense
 //
 // A site's key is ((b*D + z)*H + y)*W + x (64-bit), one bit of the bitmap; its rank (the row it occupies) is the number of set bits
 // below it: blk[word >> PNX_SCAN_SHIFT] + pre[word] + popc(bitmap[word] & below).  Ranks follow [b, z, y, x] lexicographic order, which
@@ -13,6 +17,14 @@
 // Convolution: a wave owns 16 output rows and every output channel (NT tiles of 16); K runs tap by tap, Cin in steps of 4, on
 // v_mfma_f32_16x16x4_f32 -- exact fp32 products accumulated in k order, so every output row is reduced in one fixed order whatever the
 // tiling (a missing neighbour contributes 0 * w, which leaves the sum unchanged), and a tap none of the 16 rows has is skipped.
+//
+// Weight gradient: per tap a (Cout x Cin) GEMM whose K runs over the output rows.  Both operands are row-major in memory with the channel
+// contiguous, and the fp32 MFMA wants exactly that: A = dy^T is A[m = lane & 15][k = lane >> 4] = dy[row k][co m], B = x gathered is
+// B[k = lane >> 4][n = lane & 15] = x[map[row k][t]][ci n] -- 16 consecutive lanes read 16 consecutive floats of one row, no transpose.
+// Rows are dealt statically: workgroup c owns rows [c R, (c + 1) R) (sp3_wgrad_split), its four waves take the taps wave, wave + 4, ...
+// one after the other (the chunk's map, x and dy rows stay in cache across the taps), a wave accumulates MT x NT tiles of 16 x 16 over the
+// chunk in row order -- a K step of 16 rows none of which has the tap costs no MFMA -- and writes them to partial c; k_sp3_wgrad_sum adds
+// the partials in index order.  No floating-point atomics: the result does not depend on timing.
 #include "pnx_common.h"
 #include "pnx_scan.h"
 
@@ -188,7 +200,9 @@ __global__ __launch_bounds__(kBlock) void k_sp3_nbmap(const int32_t* __restrict_
 }
 
 // y[row] = relu?( sum_t sum_c x[map[row][t]][c] * w'[t][c][:] + shift (+ residual[row]) ).  w' is (T, cin4, NT*16): BN scale folded in, zero-padded.
-template <int NT>
+// PERTAP (training): every tap is summed from zero on its own and the taps are added in tap order -- the summation tree of a matmul per tap, whose
+// chains are one tap long; a row with t taps otherwise carries a chain t times as long and about sqrt(t) times the rounding error.
+template <int NT, bool PERTAP>
 __global__ __launch_bounds__(kBlock) void k_sp3_conv(const float* __restrict__ x, int64_t n_in, int cin, const int32_t* __restrict__ map, int64_t n_out, int T,
                                                      const float* __restrict__ wp, const float* __restrict__ shift, const float* __restrict__ res, int relu,
                                                      float* __restrict__ y, int cout) {
@@ -207,12 +221,27 @@ __global__ __launch_bounds__(kBlock) void k_sp3_conv(const float* __restrict__ x
     if (__ballot(nb >= 0) == 0) continue;  // no row of the tile has this neighbour: no MFMA
     const float* xr = x + (int64_t)(nb < 0 ? 0 : nb) * cin;
     const float* wt = wp + (int64_t)t * cin4 * ldw + r;
-    for (int k0 = 0; k0 < cin; k0 += 4) {
-      const int k = k0 + kk;
-      const float a = (nb >= 0 && k < cin) ? xr[k] : 0.f;
-      const float* wk = wt + (int64_t)k * ldw;
+    if constexpr (PERTAP) {
+      f32x4 tap[NT];
 #pragma unroll
-      for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wk[j * 16], acc[j], 0, 0, 0);
+      for (int j = 0; j < NT; j++) tap[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int k0 = 0; k0 < cin; k0 += 4) {
+        const int k = k0 + kk;
+        const float a = (nb >= 0 && k < cin) ? xr[k] : 0.f;
+        const float* wk = wt + (int64_t)k * ldw;
+#pragma unroll
+        for (int j = 0; j < NT; j++) tap[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wk[j * 16], tap[j], 0, 0, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < NT; j++) acc[j] += tap[j];
+    } else {
+      for (int k0 = 0; k0 < cin; k0 += 4) {
+        const int k = k0 + kk;
+        const float a = (nb >= 0 && k < cin) ? xr[k] : 0.f;
+        const float* wk = wt + (int64_t)k * ldw;
+#pragma unroll
+        for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wk[j * 16], acc[j], 0, 0, 0);
+      }
     }
   }
 #pragma unroll
@@ -245,6 +274,139 @@ __global__ __launch_bounds__(kBlock) void k_sp3_dense(const float* __restrict__ 
 
 unsigned sp3_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// tmap[map[o][t]][t] = o: for one input row and tap there is at most one output row (q = (p + pad - o) / s), so no two threads meet
+__global__ __launch_bounds__(kBlock) void k_sp3_tmap(const int32_t* __restrict__ map, int64_t n_out, int T, int64_t n_in, int32_t* __restrict__ tmap) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= n_out * T) return;
+  const int64_t o = e / T;
+  const int t = (int)(e - o * T);
+  const int32_t v = map[e];
+  if (v >= 0 && (int64_t)v < n_in) tmap[(int64_t)v * T + t] = (int32_t)o;
+}
+
+// partial[c][co][t][ci] = sum over rows o of chunk c, in row order, of dy[o][co] * x[map[o][t]][ci]
+template <int MT, int NT>
+__global__ __launch_bounds__(kBlock) void k_sp3_wgrad(const float* __restrict__ x, int64_t n_in, int cin, const float* __restrict__ dy, int cout,
+                                                      const int32_t* __restrict__ map, int64_t n_out, int T, int R, float* __restrict__ part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, kk = lane >> 4;
+  const int64_t c = blockIdx.x;
+  const int co0 = blockIdx.y * (MT * 16);
+  const int64_t row_begin = c * R;
+  const int64_t row_end = row_begin + R < n_out ? row_begin + R : n_out;
+  for (int t = wave; t < T; t += kBlock / 64) {
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int m = 0; m < MT; m++)
+#pragma unroll
+      for (int j = 0; j < NT; j++) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int64_t row0 = row_begin; row0 < row_end; row0 += 16) {
+      int32_t nb[4];
+      bool any = false;
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int64_t row = row0 + 4 * s + kk;
+        int32_t v = row < row_end ? map[row * T + t] : -1;
+        if ((int64_t)v >= n_in) v = -1;
+        nb[s] = v;
+        any = any || v >= 0;
+      }
+      if (__ballot(any) == 0) continue;  // no row of the K step has this tap: no MFMA
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const bool on = nb[s] >= 0;
+        const float* dr = dy + (row0 + 4 * s + kk) * cout + co0 + r;
+        const float* xr = x + (int64_t)(on ? nb[s] : 0) * cin + r;
+        float a[MT], b[NT];
+#pragma unroll
+        for (int m = 0; m < MT; m++) a[m] = (on && co0 + m * 16 + r < cout) ? dr[m * 16] : 0.f;
+#pragma unroll
+        for (int j = 0; j < NT; j++) b[j] = (on && j * 16 + r < cin) ? xr[j * 16] : 0.f;
+#pragma unroll
+        for (int m = 0; m < MT; m++) {
+          if (co0 + m * 16 >= cout) continue;  // uniform: a channel tile past the layer's last
+#pragma unroll
+          for (int j = 0; j < NT; j++) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[j], acc[m][j], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; m++)
+#pragma unroll
+      for (int j = 0; j < NT; j++) {
+        const int ci = j * 16 + r;
+        if (ci >= cin) continue;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int co = co0 + m * 16 + kk * 4 + i;
+          if (co < cout) part[(((int64_t)c * cout + co) * T + t) * cin + ci] = acc[m][j][i];
+        }
+      }
+  }
+}
+
+// dw[e] = partial[0][e] + partial[1][e] + ... in that order
+__global__ __launch_bounds__(kBlock) void k_sp3_wgrad_sum(const float* __restrict__ part, int P, int64_t E, float* __restrict__ dw) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= E) return;
+  float v = 0.f;
+#pragma unroll 8
+  for (int p = 0; p < P; p++) v += part[(int64_t)p * E + e];
+  dw[e] = v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_sp3_dense_bwd(const float* __restrict__ dout, const int32_t* __restrict__ coords, int64_t n, int C, Sp3Grid g,
+                                                          float* __restrict__ dfeat) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= n * C) return;
+  const int64_t i = e / C;
+  const int ch = (int)(e - i * C);
+  int c[4];
+  dfeat[e] = sp3_row(coords, i, g, c) ? dout[((((int64_t)c[0] * C + ch) * g.D + c[1]) * g.H + c[2]) * g.W + c[3]] : 0.f;
+}
+
+// The weight gradient's static split: output-channel tiles per wave (MT), rows per workgroup R (a multiple of 16, 256 .. 4096: about 256
+// workgroups, a chunk small enough to stay in cache over the taps) and the number of partials P = ceil(n_out / R).
+struct Sp3WgradSplit {
+  int mt, groups, R;
+  int64_t P;
+};
+
+Sp3WgradSplit sp3_wgrad_split(int64_t n_out, int cout) {
+  Sp3WgradSplit s;
+  const int tiles = (cout + 15) / 16;
+  s.mt = tiles <= 3 ? tiles : (tiles % 3 == 0 ? 3 : (tiles % 2 == 0 ? 2 : 3));
+  s.groups = (tiles + s.mt - 1) / s.mt;
+  const int64_t p0 = 256 / s.groups > 1 ? 256 / s.groups : 1;
+  int64_t R = ((n_out + p0 - 1) / p0 + 15) & ~(int64_t)15;
+  R = R < 256 ? 256 : (R > 4096 ? 4096 : R);
+  s.R = (int)R;
+  s.P = n_out > 0 ? (n_out + R - 1) / R : 0;
+  return s;
+}
+
+template <int MT, int NT>
+void sp3_wgrad_launch(dim3 grid, hipStream_t st, const float* x, int64_t n_in, int cin, const float* dy, int cout, const int32_t* map, int64_t n_out, int T,
+                      int R, float* part) {
+  k_sp3_wgrad<MT, NT><<<grid, kBlock, 0, st>>>(x, n_in, cin, dy, cout, map, n_out, T, R, part);
+}
+
+template <int MT>
+void sp3_wgrad_nt(int nt, dim3 grid, hipStream_t st, const float* x, int64_t n_in, int cin, const float* dy, int cout, const int32_t* map, int64_t n_out,
+                  int T, int R, float* part) {
+  switch (nt) {
+    case 1: sp3_wgrad_launch<MT, 1>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 2: sp3_wgrad_launch<MT, 2>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 3: sp3_wgrad_launch<MT, 3>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 4: sp3_wgrad_launch<MT, 4>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 5: sp3_wgrad_launch<MT, 5>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 6: sp3_wgrad_launch<MT, 6>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 7: sp3_wgrad_launch<MT, 7>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    case 8: sp3_wgrad_launch<MT, 8>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+    default: sp3_wgrad_launch<MT, 9>(grid, st, x, n_in, cin, dy, cout, map, n_out, T, R, part); break;
+  }
+}
+
 int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
   *ix = sp3_carve(index, g);
   PNX_REQUIRE(index != nullptr && ((uintptr_t)index & 255) == 0, PNX_ERR_INVALID, "sparse3d: index must be a 256-byte aligned buffer");
@@ -261,9 +423,12 @@ int sp3_scan(const Sp3Index& ix, int32_t* count, hipStream_t st) {
 }
 
 template <int NT>
-void sp3_conv_launch(unsigned nb, hipStream_t st, const float* x, int64_t n_in, int cin, const int32_t* map, int64_t n_out, int T, const float* wp,
-                     const float* shift, const float* res, int relu, float* y, int cout) {
-  k_sp3_conv<NT><<<nb, kBlock, 0, st>>>(x, n_in, cin, map, n_out, T, wp, shift, res, relu, y, cout);
+void sp3_conv_launch(bool per_tap, unsigned nb, hipStream_t st, const float* x, int64_t n_in, int cin, const int32_t* map, int64_t n_out, int T,
+                     const float* wp, const float* shift, const float* res, int relu, float* y, int cout) {
+  if (per_tap)
+    k_sp3_conv<NT, true><<<nb, kBlock, 0, st>>>(x, n_in, cin, map, n_out, T, wp, shift, res, relu, y, cout);
+  else
+    k_sp3_conv<NT, false><<<nb, kBlock, 0, st>>>(x, n_in, cin, map, n_out, T, wp, shift, res, relu, y, cout);
 }
 
 }  // namespace
@@ -368,29 +533,40 @@ size_t pnx_sp3_packed_weight_floats(int32_t taps, int32_t cin, int32_t cout) {
   return (size_t)taps * ((cin + 3) & ~3) * ((cout + 15) & ~15);
 }
 
-int pnx_sp3_conv(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
-                 const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
+static int sp3_conv_run(bool per_tap, const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed,
+                        const float* shift, const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
+  const char* name = per_tap ? "pnx_sp3_conv_train" : "pnx_sp3_conv";
   PNX_REQUIRE(cin >= 1 && cin <= 1024 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
-              "pnx_sp3_conv: %d -> %d channels over %d taps (cin 1..1024, cout 1..144, taps 1..27)", cin, cout, taps);
-  PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_conv: %lld -> %lld rows", (long long)n_in,
+              "%s: %d -> %d channels over %d taps (cin 1..1024, cout 1..144, taps 1..27)", name, cin, cout, taps);
+  PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "%s: %lld -> %lld rows", name, (long long)n_in,
               (long long)n_out);
   if (n_out == 0) return PNX_OK;
-  PNX_REQUIRE(map && w_packed && shift && y && (n_in == 0 || x), PNX_ERR_INVALID, "pnx_sp3_conv: null pointer");
+  PNX_REQUIRE(map && w_packed && shift && y && (n_in == 0 || x), PNX_ERR_INVALID, "%s: null pointer", name);
   const unsigned nb = (unsigned)((n_out + 63) / 64);
   hipStream_t st = (hipStream_t)stream;
   switch ((cout + 15) / 16) {
-    case 1: sp3_conv_launch<1>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 2: sp3_conv_launch<2>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 3: sp3_conv_launch<3>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 4: sp3_conv_launch<4>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 5: sp3_conv_launch<5>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 6: sp3_conv_launch<6>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 7: sp3_conv_launch<7>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    case 8: sp3_conv_launch<8>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    default: sp3_conv_launch<9>(nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 1: sp3_conv_launch<1>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 2: sp3_conv_launch<2>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 3: sp3_conv_launch<3>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 4: sp3_conv_launch<4>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 5: sp3_conv_launch<5>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 6: sp3_conv_launch<6>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 7: sp3_conv_launch<7>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 8: sp3_conv_launch<8>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    default: sp3_conv_launch<9>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
   }
   PNX_LAUNCH_CHECK();
   return PNX_OK;
+}
+
+int pnx_sp3_conv(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
+                 const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
+  return sp3_conv_run(false, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout, stream);
+}
+
+int pnx_sp3_conv_train(const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed, const float* shift,
+                       const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
+  return sp3_conv_run(true, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout, stream);
 }
 
 int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* out,
@@ -406,6 +582,68 @@ int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t c
   PNX_CHECK_HIP(hipMemsetAsync(out, 0, bytes, st));
   if (n == 0) return PNX_OK;
   k_sp3_dense<<<sp3_blocks(n * channels), kBlock, 0, st>>>(feat, coords, n, channels, g, out);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_transpose_map(const int32_t* map, int64_t n_out, int32_t taps, int64_t n_in, int32_t* tmap, pnx_stream_t stream) {
+  PNX_REQUIRE(taps >= 1 && taps <= 27 && n_out >= 0 && n_out < ((int64_t)1 << 31) && n_in >= 0 && n_in < ((int64_t)1 << 31), PNX_ERR_INVALID,
+              "pnx_sp3_transpose_map: %lld -> %lld rows over %d taps", (long long)n_in, (long long)n_out, taps);
+  PNX_REQUIRE((n_in == 0 || tmap != nullptr) && (n_out == 0 || map != nullptr), PNX_ERR_INVALID, "pnx_sp3_transpose_map: null pointer");
+  if (n_in == 0) return PNX_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PNX_CHECK_HIP(hipMemsetAsync(tmap, 0xff, (size_t)n_in * taps * sizeof(int32_t), st));  // every entry -1
+  if (n_out == 0) return PNX_OK;
+  k_sp3_tmap<<<sp3_blocks(n_out * taps), kBlock, 0, st>>>(map, n_out, taps, n_in, tmap);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_sp3_wgrad_workspace_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout) {
+  if (n_out < 0 || n_out >= ((int64_t)1 << 31) || taps < 1 || taps > 27 || cin < 1 || cin > 144 || cout < 1 || cout > 144) return 0;
+  const size_t bytes = (size_t)sp3_wgrad_split(n_out, cout).P * taps * cin * cout * sizeof(float);
+  return bytes < 256 ? 256 : bytes;
+}
+
+int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, int32_t cout, const int32_t* map, int64_t n_out, int32_t taps, float* dw,
+                  void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
+  PNX_REQUIRE(cin >= 1 && cin <= 144 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
+              "pnx_sp3_wgrad: %d -> %d channels over %d taps (channels 1..144, taps 1..27)", cin, cout, taps);
+  PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_wgrad: %lld -> %lld rows", (long long)n_in, (long long)n_out);
+  PNX_REQUIRE(dw != nullptr, PNX_ERR_INVALID, "pnx_sp3_wgrad: dw is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t E = (int64_t)cout * taps * cin;
+  if (n_out == 0 || n_in == 0) {
+    PNX_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)E * sizeof(float), st));
+    return PNX_OK;
+  }
+  PNX_REQUIRE(x && dy && map && workspace, PNX_ERR_INVALID, "pnx_sp3_wgrad: null pointer");
+  const size_t need = pnx_sp3_wgrad_workspace_bytes(n_out, taps, cin, cout);
+  PNX_REQUIRE(workspace_bytes >= need, PNX_ERR_WORKSPACE, "pnx_sp3_wgrad: workspace %zu bytes < %zu needed", workspace_bytes, need);
+  const Sp3WgradSplit sp = sp3_wgrad_split(n_out, cout);
+  const dim3 grid((unsigned)sp.P, (unsigned)sp.groups);
+  const int nt = (cin + 15) / 16;
+  float* part = static_cast<float*>(workspace);
+  switch (sp.mt) {
+    case 1: sp3_wgrad_nt<1>(nt, grid, st, x, n_in, cin, dy, cout, map, n_out, taps, sp.R, part); break;
+    case 2: sp3_wgrad_nt<2>(nt, grid, st, x, n_in, cin, dy, cout, map, n_out, taps, sp.R, part); break;
+    default: sp3_wgrad_nt<3>(nt, grid, st, x, n_in, cin, dy, cout, map, n_out, taps, sp.R, part); break;
+  }
+  PNX_LAUNCH_CHECK();
+  k_sp3_wgrad_sum<<<sp3_blocks(E), kBlock, 0, st>>>(part, (int)sp.P, E, dw);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_dense_backward(const float* dout, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* dfeat,
+                           pnx_stream_t stream) {
+  Sp3Grid g;
+  int rc = sp3_grid(batch, grid3_host, &g);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(n >= 0 && channels >= 1, PNX_ERR_INVALID, "pnx_sp3_dense_backward: %lld rows of %d channels", (long long)n, channels);
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(dout && dfeat && coords && ((uintptr_t)coords & 15) == 0, PNX_ERR_INVALID, "pnx_sp3_dense_backward: null pointer or coords not 16-byte aligned");
+  k_sp3_dense_bwd<<<sp3_blocks(n * channels), kBlock, 0, (hipStream_t)stream>>>(dout, coords, n, channels, g, dfeat);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

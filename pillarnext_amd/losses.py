@@ -102,6 +102,15 @@ class _CenterLossFn(torch.autograd.Function):
         hm_t, anno, gtb = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (hm_t, anno, gtb))
         ind, cat = ind.to(device=dev, dtype=torch.int64).contiguous(), cat.to(device=dev, dtype=torch.int64).contiguous()
         mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+        # ... and with the head maps' own extents: a target of another map size would be read past its end
+        if tuple(hm_t.shape) != (B, C, H, W):
+            raise ops.PnxError(f"fused center loss: hm target {tuple(hm_t.shape)} does not match the head's hm map {(B, C, H, W)}")
+        for t in maps[1:]:
+            if t is not None and (t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (H, W)):
+                raise ops.PnxError(f"fused center loss: head map {tuple(t.shape)} does not match hm {(B, C, H, W)}")
+        if ind.dim() != 2 or ind.shape[0] != B or tuple(anno.shape[2:]) != (10,) or tuple(gtb.shape[2:]) != (7,):
+            raise ops.PnxError(f"fused center loss: labels must be (B, M) lists with (B, M, 10) anno_box and (B, M, 7) gt_boxes, got ind {tuple(ind.shape)}, "
+                               f"anno_box {tuple(anno.shape)}, gt_boxes {tuple(gtb.shape)}")
         if ind.shape != cat.shape or ind.shape != mask.shape or anno.shape[:2] != ind.shape or gtb.shape[:2] != ind.shape:
             raise ops.PnxError(f"fused center loss: label shapes disagree (ind {tuple(ind.shape)}, cat {tuple(cat.shape)}, mask {tuple(mask.shape)}, "
                                f"anno_box {tuple(anno.shape)}, gt_boxes {tuple(gtb.shape)})")

@@ -790,8 +790,9 @@ def sp3_pack_weight(w):
     return wp
 
 
-def sp3_conv(x, nbmap, w_packed, shift, cout, residual=None, relu=True):
-    """pnx_sp3_conv: x (N_in, Cin) fp32, nbmap (N_out, T) int32 -> (N_out, cout) fp32."""
+def sp3_conv(x, nbmap, w_packed, shift, cout, residual=None, relu=True, per_tap=False):
+    """pnx_sp3_conv: x (N_in, Cin) fp32, nbmap (N_out, T) int32 -> (N_out, cout) fp32.  per_tap: pnx_sp3_conv_train, the training graph's summation
+    order (every tap summed on its own, the taps added in order)."""
     for t, name in ((x, "x"), (nbmap, "nbmap"), (w_packed, "w_packed"), (shift, "shift")):
         _need_cuda(t, name)
     if x.dtype != torch.float32 or w_packed.dtype != torch.float32 or shift.dtype != torch.float32 or nbmap.dtype != torch.int32:
@@ -805,8 +806,9 @@ def sp3_conv(x, nbmap, w_packed, shift, cout, residual=None, relu=True):
         if residual.dtype != torch.float32 or tuple(residual.shape) != (n_out, cout):
             raise PnxError("sp3_conv: residual must be (N_out, cout) fp32")
     y = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    check(lib().pnx_sp3_conv(ptr(x), x.shape[0], ci, ptr(nbmap), n_out, T, ptr(w_packed), ptr(shift), ptr(residual), 1 if relu else 0, ptr(y), cout,
-                             stream_ptr()), "pnx_sp3_conv")
+    fn = lib().pnx_sp3_conv_train if per_tap else lib().pnx_sp3_conv
+    check(fn(ptr(x), x.shape[0], ci, ptr(nbmap), n_out, T, ptr(w_packed), ptr(shift), ptr(residual), 1 if relu else 0, ptr(y), cout, stream_ptr()),
+          "pnx_sp3_conv_train" if per_tap else "pnx_sp3_conv")
     return y
 
 
@@ -821,3 +823,66 @@ def sp3_dense(feat, coords, batch, grid):
     out = torch.empty((int(batch), C * D, H, W), dtype=torch.float32, device=feat.device)
     check(lib().pnx_sp3_dense(ptr(feat), ptr(coords), coords.shape[0], C, int(batch), _i3(grid), ptr(out), stream_ptr()), "pnx_sp3_dense")
     return out
+
+
+def sp3_pack_weight_t(w, mirror=False):
+    """(Cout, kd, kh, kw, Cin) fp32 -> (T, round_up(Cout, 4), round_up(Cin, 16)): the weights of the data gradient, pnx_sp3_conv's layout with
+    the channel roles swapped.  mirror=True reverses the taps, for a submanifold layer run on its own map (tmap[i][t] = map[i][T - 1 - t])."""
+    co, ci = w.shape[0], w.shape[-1]
+    T = w.shape[1] * w.shape[2] * w.shape[3]
+    co4, ci16 = (co + 3) // 4 * 4, (ci + 15) // 16 * 16
+    if lib().pnx_sp3_packed_weight_floats(T, co, ci) != T * co4 * ci16:
+        raise PnxError(f"sp3_pack_weight_t: no packing for {tuple(w.shape)}")
+    wt = w.float().reshape(co, T, ci).permute(1, 0, 2)
+    wp = torch.zeros((T, co4, ci16), dtype=torch.float32, device=w.device)
+    wp[:, :co, :ci] = wt.flip(0) if mirror else wt
+    return wp
+
+
+def sp3_transpose_map(nbmap, n_in):
+    """pnx_sp3_transpose_map: nbmap (N_out, T) int32 -> tmap (n_in, T) int32 with tmap[nbmap[o][t]][t] = o, -1 elsewhere."""
+    _need_cuda(nbmap, "nbmap")
+    if nbmap.dtype != torch.int32 or nbmap.dim() != 2 or not nbmap.is_contiguous():
+        raise PnxError("sp3_transpose_map: nbmap must be a contiguous (N_out, T) int32 tensor")
+    n_out, T = nbmap.shape
+    tmap = torch.empty((int(n_in), T), dtype=torch.int32, device=nbmap.device)
+    check(lib().pnx_sp3_transpose_map(ptr(nbmap), n_out, T, int(n_in), ptr(tmap), stream_ptr()), "pnx_sp3_transpose_map")
+    return tmap
+
+
+def sp3_wgrad_workspace_bytes(n_out, taps, cin, cout):
+    n = lib().pnx_sp3_wgrad_workspace_bytes(int(n_out), int(taps), int(cin), int(cout))
+    if n == 0:
+        raise PnxError(f"sp3_wgrad: no kernel for {cin} -> {cout} channels over {taps} taps and {n_out} rows")
+    return n
+
+
+def sp3_wgrad(x, nbmap, dy):
+    """pnx_sp3_wgrad: x (N_in, Cin), nbmap (N_out, T), dy (N_out, Cout) -> dw (Cout, T, Cin) fp32."""
+    for t, name in ((x, "x"), (nbmap, "nbmap"), (dy, "dy")):
+        _need_cuda(t, name)
+    if x.dtype != torch.float32 or dy.dtype != torch.float32 or nbmap.dtype != torch.int32 or x.dim() != 2 or dy.dim() != 2 or nbmap.dim() != 2:
+        raise PnxError("sp3_wgrad: fp32 (N, C) features and gradients, int32 map")
+    if dy.shape[0] != nbmap.shape[0] or not (x.is_contiguous() and dy.is_contiguous() and nbmap.is_contiguous()):
+        raise PnxError("sp3_wgrad: dy and nbmap must have one row per output site, and every operand must be contiguous")
+    n_out, T = nbmap.shape
+    ci, co = x.shape[1], dy.shape[1]
+    nbytes = sp3_wgrad_workspace_bytes(n_out, T, ci, co)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    dw = torch.empty((co, T, ci), dtype=torch.float32, device=x.device)
+    check(lib().pnx_sp3_wgrad(ptr(x), x.shape[0], ci, ptr(dy), co, ptr(nbmap), n_out, T, ptr(dw), ptr(ws), nbytes, stream_ptr()), "pnx_sp3_wgrad")
+    return dw
+
+
+def sp3_dense_backward(dout, coords, channels):
+    """pnx_sp3_dense_backward: dout (batch, C*D, H, W) fp32 -> (N, C) rows, the gradient of sp3_dense."""
+    _need_coords(coords)
+    dout = dout.contiguous()  # a broadcast gradient (the backward of a sum) arrives with zero strides
+    _need_cuda(dout, "dout")
+    C = int(channels)
+    if dout.dtype != torch.float32 or dout.dim() != 4 or dout.shape[1] % C:
+        raise PnxError("sp3_dense_backward: dout must be (batch, C*D, H, W) fp32")
+    B, D, H, W = dout.shape[0], dout.shape[1] // C, dout.shape[2], dout.shape[3]
+    dfeat = torch.empty((coords.shape[0], C), dtype=torch.float32, device=dout.device)
+    check(lib().pnx_sp3_dense_backward(ptr(dout), ptr(coords), coords.shape[0], C, B, _i3((D, H, W)), ptr(dfeat), stream_ptr()), "pnx_sp3_dense_backward")
+    return dfeat

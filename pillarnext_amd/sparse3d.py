@@ -1,5 +1,5 @@
 """SparseResNet3D (det3d/models/backbones/sparse_resnet3d.py:9-72, blocks of det3d/models/utils/sparse_conv.py:66-104) on the sparse 3-D HIP
-kernels of csrc/sparse3d.hip (include/pnx.h: pnx_sp3_*).  Eval mode only: the backward of the 3-D layers is not built.
+kernels of csrc/sparse3d.hip (include/pnx.h: pnx_sp3_*).
 
     SparseResNet3D(...).forward(pillar_features (V, C) fp32, coors (V, 4) int32 [b, z, y, x], input_shape [D, H, W]) -> (B, C_out*D', H', W')
 
@@ -10,6 +10,11 @@ is accepted on load).  Each layer is a gather-GEMM over its active sites:
   - SparseConv3d marks the outputs every input x tap reaches (one host sync per strided layer reads their count), SubMConv3d keeps the set;
   - a neighbour map (N_out, taps) per set and geometry -- shared by the four SubM layers of a stage -- feeds pnx_sp3_conv, which applies the
     folded BatchNorm, the residual and the ReLU in its epilogue.
+
+That folded path runs in eval mode when no gradient is wanted.  In training mode, or when gradients are enabled and a parameter or the input
+features require one, every layer is conv (SparseConvFunction: pnx_sp3_conv_train with the plain weight; backward = the same on the transposed
+map for dx, pnx_sp3_wgrad for dw) -> the module's own nn.BatchNorm1d on the (N, C) rows -> ReLU on torch ops, over the same index, output sets
+and neighbour maps, which forward and backward share.
 """
 import math
 
@@ -79,6 +84,58 @@ class SparseBasicBlock3d(nn.Module):
         self.act2 = nn.ReLU()
 
 
+def sparse_conv_dgrad(dy, weight, nbmap, n_in, subm):
+    """dx (n_in, Cin) of y[o] = sum_t w[:, t, :] . x[nbmap[o][t]]: pnx_sp3_conv_train on dy, the transposed map and the weights packed the other way
+    round.  subm: the map is a set's own, its transpose is the map with the taps mirrored, so the taps of the weights are mirrored instead."""
+    cin = weight.shape[-1]
+    tmap = nbmap if subm else ops.sp3_transpose_map(nbmap, n_in)
+    return ops.sp3_conv(dy, tmap, ops.sp3_pack_weight_t(weight, mirror=subm), torch.zeros((cin,), dtype=torch.float32, device=dy.device), cin, relu=False,
+                       per_tap=True)
+
+
+class SparseConvFunction(torch.autograd.Function):
+    """y[o] = sum_t w[:, t, :] . x[nbmap[o][t]] with both gradients on the HIP kernels, each computed only if it is wanted.
+    subm: the layer runs on its set's own map, whose transpose is the map with the taps mirrored (no second map is built)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, nbmap, subm, tick):
+        x, w = x.contiguous(), weight.detach()
+        cout = w.shape[0]
+        y = ops.sp3_conv(x, nbmap, ops.sp3_pack_weight(w), torch.zeros((cout,), dtype=torch.float32, device=x.device), cout, relu=False,
+                         per_tap=True)
+        ctx.save_for_backward(x, w, nbmap)
+        ctx.subm, ctx.tick = subm, tick
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, nbmap = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = None
+        ctx.tick("bwd")
+        if ctx.needs_input_grad[0]:
+            dx = sparse_conv_dgrad(dy, w, nbmap, x.shape[0], ctx.subm)
+            ctx.tick("dgrad")
+        if ctx.needs_input_grad[1]:
+            dw = ops.sp3_wgrad(x, nbmap, dy).view(w.shape)
+            ctx.tick("wgrad")
+        return dx, dw, None, None, None
+
+
+class SparseDenseFunction(torch.autograd.Function):
+    """ops.sp3_dense with its gradient, the gather back into rows."""
+
+    @staticmethod
+    def forward(ctx, x, coords, batch, grid):
+        ctx.save_for_backward(coords)
+        ctx.channels = x.shape[1]
+        return ops.sp3_dense(x.contiguous(), coords, batch, grid)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.sp3_dense_backward(dout, ctx.saved_tensors[0], ctx.channels), None, None, None
+
+
 def _fold(conv, bn):
     """Eval BatchNorm folded into the conv: packed weight (BN scale baked in) and per-channel shift, fp32."""
     a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
@@ -130,12 +187,18 @@ class SparseResNet3D(nn.Module):
             e.record()
             self.profile.append((name, e))
 
+    def _differentiable(self, pillar_features):
+        """Training mode, or a gradient is wanted: the autograd path.  Otherwise the folded eval path."""
+        return self.training or (torch.is_grad_enabled() and (pillar_features.requires_grad or any(p.requires_grad for p in self.parameters())))
+
     def _check(self, pillar_features, coors):
-        if self.training:
-            raise PnxError("SparseResNet3D: training is not implemented (the backward of the sparse 3-D layers is not built); call .eval()")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise PnxError("SparseResNet3D: gradients are not implemented (the backward of the sparse 3-D layers is not built); "
-                           "run under torch.no_grad() or freeze the parameters")
+        """Argument checks; returns whether the call takes the autograd path (decided once per forward)."""
+        diff = self._differentiable(pillar_features)
+        if diff and not (pillar_features.is_cuda and coors.is_cuda):
+            if self.training:
+                raise PnxError("SparseResNet3D: training needs CUDA (ROCm) tensors; the sparse 3-D layers have no CPU implementation")
+            raise PnxError("SparseResNet3D: gradients need CUDA (ROCm) tensors; the sparse 3-D layers have no CPU implementation "
+                           "(run under torch.no_grad() or freeze the parameters to reach the device check of the eval path)")
         if pillar_features.dtype != torch.float32:
             raise PnxError(f"SparseResNet3D: features must be fp32, got {pillar_features.dtype} (there is no bf16 / fp16 form)")
         if coors.dtype not in (torch.int32, torch.int64) or coors.dim() != 2 or coors.shape[1] != 4:
@@ -146,6 +209,7 @@ class SparseResNet3D(nn.Module):
             raise PnxError(f"SparseResNet3D: {pillar_features.shape[1]} input channels, the model takes {self._num_input_features}")
         if not (pillar_features.is_cuda and coors.is_cuda):
             raise PnxError("SparseResNet3D: features and coords must be CUDA (ROCm) tensors; the sparse 3-D convolution has no CPU implementation")
+        return diff
 
     def _strided(self, x, coords, ix, rows, B, conv, name):
         """SparseConv3d: output set (one host sync for its count), its coords, the neighbour map into the input set."""
@@ -158,14 +222,25 @@ class SparseResNet3D(nn.Module):
         self._tick(name + ".map")
         return oix, oc, m
 
-    def _conv(self, x, m, folded, cout, name, residual=None):
-        y = ops.sp3_conv(x, m, folded[0], folded[1], cout, residual=residual, relu=True)
+    def _conv(self, x, m, conv, norm, folded, name, residual=None):
+        """One layer.  folded: the plan of packed weights and shifts (eval), or None: conv -> BatchNorm1d -> (+ residual) -> ReLU under autograd."""
+        if folded is None:
+            y = SparseConvFunction.apply(x, conv.weight, m, conv.subm, lambda phase: self._tick(f"{name}.{phase}"))
+            self._tick(name + ".conv")
+            y = norm(y)
+            y = torch.relu(y if residual is None else y + residual)
+            self._tick(name + ".rest")
+            return y
+        wp, shift = folded[name]
+        y = ops.sp3_conv(x, m, wp, shift, conv.out_channels, residual=residual, relu=True)
         self._tick(name + ".conv")
         return y
 
     def forward_sparse(self, pillar_features, coors, input_shape, batch_size=None):
         """The active sets: [(coords (N, 4) int32, features (N, C) fp32, grid (D, H, W))] after stage 0, 1, ..., extra_conv and mapping."""
-        self._check(pillar_features, coors)
+        return self._sets(pillar_features, coors, input_shape, batch_size, self._check(pillar_features, coors))
+
+    def _sets(self, pillar_features, coors, input_shape, batch_size, diff):
         if batch_size is None:
             batch_size = len(torch.unique(coors[:, 0]))  # the reference's own rule (:62)
         B = int(batch_size)
@@ -185,7 +260,7 @@ class SparseResNet3D(nn.Module):
             if not distinct:
                 raise PnxError("SparseResNet3D: coords hold duplicate sites")
         self._tick("input.index")
-        folded = self._folded()
+        folded = None if diff else self._folded()
         sets = []
         for i, seq in enumerate(self.blocks):
             conv = seq[0].conv
@@ -195,31 +270,34 @@ class SparseResNet3D(nn.Module):
             else:
                 ix, coords, m = self._strided(x, coords, ix, rows, B, conv, f"blocks.{i}.0")
             rows = None  # a layer's output rows are in rank order
-            x = self._conv(x, m, folded[f"blocks.{i}.0"], conv.out_channels, f"blocks.{i}.0")
+            x = self._conv(x, m, conv, seq[0].norm, folded, f"blocks.{i}.0")
             if len(seq) > 1:
                 k = seq[1].conv2.kernel_size
                 m = ops.sp3_neighbor_map(coords, ix, None, k, (1, 1, 1), tuple(a // 2 for a in k))  # shared by the stage's SubM layers
                 self._tick(f"blocks.{i}.subm.map")
                 for j, blk in enumerate(seq[1:], 1):
-                    y = self._conv(x, m, folded[f"blocks.{i}.{j}.block1"], blk.block1.conv.out_channels, f"blocks.{i}.{j}.block1")
-                    x = self._conv(y, m, folded[f"blocks.{i}.{j}.conv2"], blk.conv2.out_channels, f"blocks.{i}.{j}.conv2", residual=x)
+                    y = self._conv(x, m, blk.block1.conv, blk.block1.norm, folded, f"blocks.{i}.{j}.block1")
+                    x = self._conv(y, m, blk.conv2, blk.norm2, folded, f"blocks.{i}.{j}.conv2", residual=x)
             sets.append((coords, x, ix.grid))
         ix, coords, m = self._strided(x, coords, ix, rows, B, self.extra_conv[0], "extra_conv")
-        x = self._conv(x, m, folded["extra_conv"], self.extra_conv[0].out_channels, "extra_conv")
+        x = self._conv(x, m, self.extra_conv[0], self.extra_conv[1], folded, "extra_conv")
         sets.append((coords, x, ix.grid))
         mc = self.mapping.conv
         m = ops.sp3_neighbor_map(coords, ix, None, mc.kernel_size, (1, 1, 1), mc.padding)
         self._tick("mapping.map")
-        x = self._conv(x, m, folded["mapping"], mc.out_channels, "mapping")
+        x = self._conv(x, m, mc, self.mapping.norm, folded, "mapping")
         sets.append((coords, x, ix.grid))
         return sets
 
     def forward(self, pillar_features, coors, input_shape, batch_size=None):
         """sparse_resnet3d.py:61-72: x.dense() then view(B, C*D, H, W) -- channel index c*D + d."""
+        diff = self._check(pillar_features, coors)
         if batch_size is None:
-            self._check(pillar_features, coors)
             batch_size = len(torch.unique(coors[:, 0]))
-        coords, x, grid = self.forward_sparse(pillar_features, coors, input_shape, batch_size)[-1]
-        out = ops.sp3_dense(x, coords, batch_size, grid)
+        coords, x, grid = self._sets(pillar_features, coors, input_shape, batch_size, diff)[-1]
+        if diff:
+            out = SparseDenseFunction.apply(x, coords, batch_size, grid)
+        else:
+            out = ops.sp3_dense(x, coords, batch_size, grid)
         self._tick("dense")
         return out

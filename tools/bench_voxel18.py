@@ -3,7 +3,12 @@
 
 Prints the active sites per stage, ms per layer from HIP events (index, neighbour map and convolution separately), backbone ms per frame,
 peak memory, and -- for context -- the same backbone as a torch statement on the GPU (fp32 gather + matmul + index_add_ per tap, neighbours
-from torch.unique / searchsorted).  Usage: python tools/bench_voxel18.py [--frames 4] [--iters 5]"""
+from torch.unique / searchsorted).  Usage: python tools/bench_voxel18.py [--frames 4] [--iters 5]
+
+--train times forward + backward of the backbone in training mode instead (loss = sum of the dense output x a fixed random tensor): ms per step,
+the split into forward convolutions / data gradients / weight gradients / everything else (index, maps, BatchNorm, ReLU, residual, dense: torch
+glue included) from HIP events, peak memory, the weight-gradient workspace per stage, and the same torch statement under autograd, alternating
+with the HIP step in one process (--torch-frames: fewer frames for the statement if it does not fit; its time is then also given per frame)."""
 import argparse
 import collections
 import os
@@ -86,10 +91,98 @@ def torch_backbone(bb, feats, coords, grid):
     return x
 
 
+def _inputs(reader, B):
+    pts = torch.from_numpy(synth.make_batch("C2", B, "sweep")).cuda()
+    with torch.no_grad():
+        feats, coords, grid = reader(pts, B)
+    return pts, feats, coords, grid
+
+
+def train(a, reader, bb):
+    from pillarnext_amd import ops
+
+    B = a.frames
+    pts, feats, coords, grid = _inputs(reader, B)
+    bb.train()
+    print(f"# voxel18 backbone TRAINING step, synth C2 sweep x {B} frames ({pts.shape[0]} points), grid {tuple(int(g) for g in grid)}, {feats.shape[0]} voxels")
+    with torch.no_grad():
+        sets = bb.eval().forward_sparse(feats, coords, grid, B)
+    bb.train()
+    names = ["stage0", "stage1", "stage2", "stage3", "extra_conv", "mapping"]
+    convs = [bb.blocks[0][1].conv2, bb.blocks[1][1].conv2, bb.blocks[2][1].conv2, bb.blocks[3][1].conv2, bb.extra_conv[0], bb.mapping.conv]
+    print("active sites / weight-gradient workspace of one layer:", ", ".join(
+        f"{n} {int(s[0].shape[0])} / {ops.sp3_wgrad_workspace_bytes(int(s[0].shape[0]), cv.weight[0, ..., 0].numel(), cv.in_channels, cv.out_channels) / 2**20:.1f} MiB"
+        for n, s, cv in zip(names, sets, convs)))
+    del sets
+    proj = None
+
+    def hip_step(profile):
+        nonlocal proj
+        bb.zero_grad(set_to_none=True)
+        bb.profile = [] if profile else None
+        out = bb(feats, coords, grid, B)
+        if proj is None:
+            proj = torch.randn(out.shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+        (out * proj).sum().backward()
+        bb._tick("end")
+        ev, bb.profile = bb.profile, None
+        return ev
+
+    tb, tf_, tc, tg = (a.torch_frames or B), None, None, None
+    if tb != B:
+        _, tf_, tc, tg = _inputs(reader, tb)
+    else:
+        tf_, tc, tg = feats, coords, grid
+    tproj = None
+
+    def torch_step():
+        nonlocal tproj
+        bb.zero_grad(set_to_none=True)
+        bb.eval()  # the statement the tool carries folds the running statistics; same convolutions, same graph shape
+        x = torch_backbone(bb, tf_, tc, tuple(int(g) for g in tg))
+        bb.train()
+        if tproj is None:
+            tproj = torch.randn(x.shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+        (x * tproj).sum().backward()
+
+    def wall(fn, *args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn(*args)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    hip_step(False), torch_step(), hip_step(False)  # warm-up
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    hw, tw = [], []
+    per = collections.defaultdict(float)
+    for _ in range(a.iters):  # alternate: both see the same clocks and the same allocator state
+        ms, ev = wall(hip_step, True)
+        hw.append(ms)
+        for (_, e0), (name, e1) in zip(ev[:-1], ev[1:]):
+            per[name.rsplit(".", 1)[-1]] += e0.elapsed_time(e1) / a.iters
+        tw.append(wall(torch_step)[0])
+    peak = torch.cuda.max_memory_allocated() - base
+    hw.sort(), tw.sort()
+    phases = {"forward conv": per["conv"], "dgrad": per["dgrad"], "wgrad": per["wgrad"]}
+    rest = sum(per.values()) - sum(phases.values())
+    print("HIP step by phase (HIP events, mean of %d): " % a.iters + ", ".join(f"{k} {v:.2f} ms" for k, v in phases.items())
+          + f", the rest (index, maps, BatchNorm / ReLU / residual, dense, autograd glue) {rest:.2f} ms")
+    print(f"HIP forward + backward: {hw[len(hw) // 2]:.2f} ms per batch of {B} (median wall of {a.iters}; min {hw[0]:.2f}, max {hw[-1]:.2f}), "
+          f"{hw[len(hw) // 2] / B:.2f} ms per frame")
+    print(f"torch statement forward + backward (fp32 gather + matmul + index_add_ per tap under autograd, {tb} frames): {tw[len(tw) // 2]:.2f} ms per batch "
+          f"(min {tw[0]:.2f}, max {tw[-1]:.2f}), {tw[len(tw) // 2] / tb:.2f} ms per frame")
+    print(f"peak memory above inputs (both steps in the process): {peak / 2**30:.2f} GiB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--train", action="store_true", help="time forward + backward in training mode")
+    ap.add_argument("--torch-frames", type=int, default=0, help="--train: frames of the torch statement (default: --frames)")
     a = ap.parse_args()
     torch.manual_seed(0)
     B = a.frames
@@ -100,6 +193,9 @@ def main():
         for m in bb.modules():
             if isinstance(m, torch.nn.BatchNorm1d):
                 m.weight.uniform_(0.5, 1.5), m.bias.uniform_(-0.2, 0.2), m.running_mean.uniform_(-0.2, 0.2), m.running_var.uniform_(0.5, 2.0)
+    if a.train:
+        return train(a, reader, bb)
+    with torch.no_grad():
         feats, coords, grid = reader(pts, B)
         torch.cuda.synchronize()
         print(f"# voxel18 backbone, synth C2 sweep x {B} frames ({pts.shape[0]} points), grid {tuple(int(g) for g in grid)}, {feats.shape[0]} voxels")
