@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .plan import Dyn, LaunchPlan
 
 
 # ------------------------------------------------------------------------------------------------ backbone
@@ -1145,9 +1146,10 @@ class _HipConv3x3(nn.Module):
         self.cout, self.cin, self.stride = weight.shape[0], weight.shape[1], int(stride)
         self.register_buffer("wfrag", ops.conv3x3_pack_weights(weight, dtype=dtype))
         self.register_buffer("bias", bias.float().contiguous())
-    def forward(self, x, mask=None, residual=None, out=None, tiles=None):
-        return ops.conv3x3_masked(x, self.wfrag, self.bias, self.cout, self.stride, mask, residual, True, out=out,
-                                  tiles=tiles if self.stride == 1 else None)
+    def forward(self, x, mask=None, residual=None, out=None, tiles=None, plan=None):
+        """plan: a LaunchPlan that records the call instead of issuing it (the same arguments; `out` says where it will write)."""
+        call = ops.conv3x3_masked if plan is None else plan.conv3x3
+        return call(x, self.wfrag, self.bias, self.cout, self.stride, mask, residual, True, out=out, tiles=tiles if self.stride == 1 else None)
 
 
 class _HipDeconv2x2(nn.Module):
@@ -1159,8 +1161,10 @@ class _HipDeconv2x2(nn.Module):
         self.register_buffer("wfrag", ops.deconv2x2_pack_weights(weight, dtype=dtype))
         self.register_buffer("bias", bias.float().contiguous())
 
-    def forward(self, x, mask=None, residual=None):
-        return ops.deconv2x2(x, self.wfrag, self.bias, self.cout, self.relu)
+    def forward(self, x, mask=None, residual=None, out=None, plan=None):
+        if plan is None:
+            return ops.deconv2x2(x, self.wfrag, self.bias, self.cout, self.relu)
+        return plan.deconv2x2(x, self.wfrag, self.bias, self.cout, out, self.relu)
 
 
 class _HipSepHeadOut(nn.Module):
@@ -1172,8 +1176,10 @@ class _HipSepHeadOut(nn.Module):
         self.register_buffer("wfrag", ops.sephead_pack_weights(weight, dtype=dtype))
         self.register_buffer("bias", bias.float().contiguous())
 
-    def forward(self, x, mask=None, residual=None):
-        return ops.sephead_out(x, self.wfrag, self.bias)
+    def forward(self, x, mask=None, residual=None, out=None, plan=None):
+        if plan is None:
+            return ops.sephead_out(x, self.wfrag, self.bias)
+        return plan.sephead_out(x, self.wfrag, self.bias, out)
 
 
 def _backbone_conv(weight, bias, stride, padding, dtype, hip_conv):
@@ -1397,42 +1403,22 @@ class FusedPillarNeXt(nn.Module):
                 marks.append((name, e))
 
         mark("start")
-        ny, nx = (int(v) for v in self.reader.grid_size)
         planned = marks is None and taps is None and self._plan_ok()
-        if planned:
+        if planned:   # the reader writes the plan's persistent canvas / occupancy
             bb = self._backbone_plan(batch_size, points.device)
-            self.reader.forward_dense(points, batch_size, dtype=self.dtype, out=bb["canvas"], occupancy=bb["occ"])
-            if after_reader is not None:
-                after_reader()
+            canvas, occ = bb["canvas"], bb["occ"]
+        else:
+            ny, nx = (int(v) for v in self.reader.grid_size)
+            canvas, occ = None, torch.empty((batch_size, ny, nx), dtype=torch.uint8, device=points.device)
+        x = self.reader.forward_dense(points, batch_size, dtype=self.dtype, out=canvas, occupancy=occ)
+        if after_reader is not None:
+            after_reader()
+        mark("reader")
+        if planned:
             bb["plan"].run()
             x, mask = bb["out"], bb["mask"]
         else:
-            occ = torch.empty((batch_size, ny, nx), dtype=torch.uint8, device=points.device)
-            x = self.reader.forward_dense(points, batch_size, dtype=self.dtype, occupancy=occ)
-            mask = occ
-            if after_reader is not None:
-                after_reader()
-        mark("reader")
-        for si, (mods, (stride, subm)) in enumerate(zip(self.stages, self.stage_meta) if not planned else ()):
-            if not subm:
-                mask = ops.mask_pool3(mask, stride)
-            ws, k = self._stage_workspace(si, mods, mask), 0
-            tiles = self._stage_tiles(si, mods, mask, ws)
-
-            def run(m, inp, res=None):
-                nonlocal k
-                if ws is None or not isinstance(m, _HipConv3x3):   # the strided entry conv of a 256-channel stage is MIOpen + epilogue
-                    return m(inp, mask, residual=res)
-                k += 1                                  # x, y, out of a block sit in three different buffers
-                return m(inp, mask, residual=res, out=ws[(k - 1) % 3], tiles=tiles)
-
-            x = run(mods[0], x)
-            for j in range(1, len(mods), 2):
-                y = run(mods[j], x)
-                x = run(mods[j + 1], y, x)
-            mark(f"backbone.stage{si}")
-            if taps is not None:
-                taps[f"stage{si}"] = x
+            x, mask = self._backbone(x, occ, mark=mark, taps=taps)
         x = self.mapping(x, mask)
         # BasicBlock (utils/conv.py): act(block2(block1(x)) + x) where block2 already ends in a ReLU, so the residual is added
         # AFTER that ReLU; both terms are >= 0, which makes the trailing act() the identity.
@@ -1447,26 +1433,71 @@ class FusedPillarNeXt(nn.Module):
         if planned and lazy and self._head_plan_ok():
             packed_out.extend(self._run_head_plan(x))
             return []
-        x = self.shared(x)
         preds = []
-        for ti, (db, c1, c2, (names, outs_n)) in enumerate(zip(self.task_deblock, self.task_conv1, self.task_conv2, self.task_split)):
-            up = db(x)
+        for (t, up), (names, outs_n) in zip(self._head(x, lazy), self.task_split):
             if lazy:
-                packed_out.append(LazyTask(self.lazy_conv2[ti](self.lazy_conv1[ti](up)), up))
-                continue
-            t = c2(c1(up))
-            if packed_out is not None:
+                packed_out.append(LazyTask(t, up))
+            elif packed_out is not None:
                 packed_out.append(t)
-                continue
-            d, o = {}, 0
-            for nme, k in zip(names, outs_n):
-                d[nme] = t[:, o:o + k]
-                o += k
-            preds.append(d)
+            else:
+                d, o = {}, 0
+                for nme, k in zip(names, outs_n):
+                    d[nme] = t[:, o:o + k]
+                    o += k
+                preds.append(d)
         mark("head")
         return preds
 
-    # ------------------------------------------------------------------ launch plans (plan.py, include/pnx.h: pnx_enqueue)
+    # ------------------------------------------------------------------ the launch schedule: each section written once, issued launch by
+    # launch (plan=None) or recorded into a plan.LaunchPlan (include/pnx.h: pnx_enqueue) that replays it with one C call per frame batch
+    def _backbone(self, x, mask, plan=None, mark=lambda name: None, taps=None):
+        """Canvas + occupancy -> (last stage's activation, its mask): per stage [mask_pool3,] tile list, entry convolution, residual blocks.
+        Recorded into a plan, every mask, tile list and activation is a persistent buffer (the plan is only built when _plan_ok() holds)."""
+        for si, (mods, (stride, subm)) in enumerate(zip(self.stages, self.stage_meta)):
+            if not subm:
+                mask = ops.mask_pool3(mask, stride) if plan is None else plan.mask_pool3(mask, ops.mask_pool3_out(mask, stride), stride)
+            ws, k = self._stage_workspace(si, mods, mask), 0
+            tiles = self._stage_tiles(si, mods, mask, ws, plan)
+
+            def run(m, inp, res=None):
+                nonlocal k
+                if ws is None or not isinstance(m, _HipConv3x3):   # launch by launch only: MIOpen + epilogue, or HIP kernels into fresh tensors
+                    assert plan is None
+                    return m(inp, mask, residual=res)
+                k += 1                                  # x, y, out of a block sit in three different buffers
+                return m(inp, mask, residual=res, out=ws[(k - 1) % 3], tiles=tiles, plan=plan)
+
+            x = run(mods[0], x)
+            for j in range(1, len(mods), 2):
+                y = run(mods[j], x)
+                x = run(mods[j + 1], y, x)
+            mark(f"backbone.stage{si}")
+            if taps is not None:
+                taps[f"stage{si}"] = x
+        return x, mask
+
+    def _head(self, x, lazy, plan=None):
+        """Neck output -> per task (map, deblocked features): shared conv, then deblock -> conv1 -> conv2 of the dense [iou] hm branches (lazy) or
+        of all branches.  Recorded into a plan (lazy, and only when _head_plan_ok() holds), x, the deblocked and the dense maps are the slots "x",
+        "up{ti}", "dense{ti}" bound per step; the intermediates are persistent, one per width: the tasks run one after the other on the stream."""
+        c1s, c2s = (self.lazy_conv1, self.lazy_conv2) if lazy else (self.task_conv1, self.task_conv2)
+
+        def run(m, inp, out):
+            return m(inp) if plan is None else m(inp, out=out, plan=plan)
+
+        o_sh, outs = None, [(None, None, None)] * len(c1s)
+        if plan is not None:   # where the recorded launches write; issued at once, every launch allocates its own output
+            def new(c, s):
+                return torch.empty((x.shape[0], c, s * x.shape[2], s * x.shape[3]), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
+
+            o_sh, mids = (new(self.shared.cout, 1), None), {c1.cout: new(c1.cout, 2) for c1 in c1s}
+            outs = [(Dyn(f"up{ti}", new(64, 2)), (mids[c1.cout], None), Dyn(f"dense{ti}", new(16, 2))) for ti, c1 in enumerate(c1s)]
+            x = Dyn("x", x)
+        sh = run(self.shared, x, o_sh)
+        for db, c1, c2, (o_up, o_mid, o_map) in zip(self.task_deblock, c1s, c2s, outs):
+            up = run(db, sh, o_up)
+            yield run(c2, run(c1, up, o_mid), o_map), up
+
     def _plan_ok(self):
         return (self.use_plan and self.sparse_ws and self.tile_lists and self.dtype in ops._HALF and not self.reader.training
                 and self.reader._fused_supported() and all(isinstance(m, _HipConv3x3) for mods in self.stages for m in mods))
@@ -1475,10 +1506,7 @@ class FusedPillarNeXt(nn.Module):
         return isinstance(self.shared, _HipConv3x3) and all(isinstance(d, _HipDeconv2x2) for d in self.task_deblock)
 
     def _backbone_plan(self, B, dev):
-        """The backbone of a B-frame batch as ONE pnx_enqueue call: per stage [mask_pool3,] tile list, convolutions -- the same calls, buffers
-        and order as the Python loop of forward_preds, frozen.  The reader writes the plan's persistent canvas / occupancy."""
-        from .plan import LaunchPlan
-
+        """The backbone of a B-frame batch as ONE pnx_enqueue call, from the persistent canvas / occupancy the reader is to write."""
         key = ("plan_bb", B, dev)
         st = self._ws.get(key)
         wkey = tuple(t.data_ptr() for mods in self.stages for m in mods for t in (m.wfrag, m.bias))   # .to() / a reload / a re-fold moves or replaces them
@@ -1488,83 +1516,32 @@ class FusedPillarNeXt(nn.Module):
         canvas = torch.empty((B, 64, ny, nx), dtype=self.dtype, device=dev, memory_format=torch.channels_last)
         occ = torch.empty((B, ny, nx), dtype=torch.uint8, device=dev)
         plan = LaunchPlan()
-        x, mask = canvas, occ
-        for si, (mods, (stride, subm)) in enumerate(zip(self.stages, self.stage_meta)):
-            if not subm:
-                H, W = mask.shape[1:]
-                pooled = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.uint8, device=dev)
-                plan.mask_pool3(mask, pooled, stride)
-                mask = pooled
-            ws = self._stage_workspace(si, mods, mask)
-            tiles, rows = self._stage_tile_buffers(si, mods, mask)
-            if tiles is not None:
-                plan.tile_list(mask, [w[1] for w in ws], rows, tiles)
-            k = 0
-
-            def run(m, inp, res=None):
-                nonlocal k
-                k += 1
-                out = ws[(k - 1) % 3]
-                plan.conv3x3(inp, m.wfrag, m.bias, m.cout, m.stride, mask, res, True, out=out, tiles=tiles if m.stride == 1 else None)
-                return out[0]
-
-            x = run(mods[0], x)
-            for j in range(1, len(mods), 2):
-                y = run(mods[j], x)
-                x = run(mods[j + 1], y, x)
+        x, mask = self._backbone(canvas, occ, plan)
         st = self._ws[key] = {"canvas": canvas, "occ": occ, "plan": plan.freeze(), "out": x, "mask": mask, "weights_at": wkey}
         return st
 
-    def _run_head_plan(self, x):
-        """shared conv + per task (deblock, dense [iou] hm branches) as ONE pnx_enqueue call.  The deblocked maps and the dense maps are fresh
-        tensors per step (the decoder's fallback may read them after later steps were enqueued); the intermediates are persistent."""
-        from .plan import Dyn, LaunchPlan
-
-        B, _, H, W = x.shape
-        dev = x.device
-        key = ("plan_head", B, H, W, dev, self.shared.wfrag.data_ptr())   # the weights' address: .to() after the plan was built moves them
-        st = self._ws.get(key)
-        T = len(self.task_deblock)
-
-        def fresh():
-            ups = [torch.empty((B, 64, 2 * H, 2 * W), dtype=self.dtype, device=dev, memory_format=torch.channels_last) for _ in range(T)]
-            dense = [torch.empty((B, 16, 2 * H, 2 * W), dtype=self.dtype, device=dev, memory_format=torch.channels_last) for _ in range(T)]
-            return ups, dense
-
-        ups, dense = fresh()
-        if st is None:
+    def _head_plan(self, x):
+        """The lazy head for maps like x as ONE pnx_enqueue call: built once per shape (no launch, no GPU needed), bound and run by _run_head_plan."""
+        key = ("plan_head", *x.shape[:1], *x.shape[2:], x.device, self.shared.wfrag.data_ptr())   # the weights' address: .to() after the plan was built moves them
+        if key not in self._ws:
             plan = LaunchPlan()
-            sh = torch.empty((B, self.shared.cout, H, W), dtype=self.dtype, device=dev, memory_format=torch.channels_last)
-            plan.conv3x3(Dyn("x", x), self.shared.wfrag, self.shared.bias, self.shared.cout, 1, None, None, True, out=(sh, None))
-            mids = {}
-            for ti, db in enumerate(self.task_deblock):
-                c1, c2 = self.lazy_conv1[ti], self.lazy_conv2[ti]
-                plan.deconv2x2(sh, db.wfrag, db.bias, db.cout, Dyn(f"up{ti}", ups[ti]), db.relu)
-                if c1.cout not in mids:      # the tasks run one after the other on the stream: one intermediate per width serves them all
-                    mids[c1.cout] = torch.empty((B, c1.cout, 2 * H, 2 * W), dtype=self.dtype, device=dev, memory_format=torch.channels_last)
-                plan.conv3x3(Dyn(f"up{ti}", ups[ti]), c1.wfrag, c1.bias, c1.cout, 1, None, None, True, out=(mids[c1.cout], None))
-                plan.sephead_out(mids[c1.cout], c2.wfrag, c2.bias, Dyn(f"dense{ti}", dense[ti]))
-            st = self._ws[key] = plan.freeze()
-        st.bind("x", x)
-        for ti in range(T):
-            st.bind(f"up{ti}", ups[ti])
-            st.bind(f"dense{ti}", dense[ti])
-        st.run()
-        return [LazyTask(d, u) for d, u in zip(dense, ups)]
+            list(self._head(x, True, plan))
+            self._ws[key] = plan.freeze()
+        return self._ws[key]
 
-    def _stage_tile_buffers(self, si, mods, mask):
-        """(tile list, count) buffers of a stage and the tile rows of its kernels, without listing anything (see _stage_tiles)."""
-        m = next((m for m in mods if isinstance(m, _HipConv3x3) and m.stride == 1), None)
-        rows = ops.conv_tile_rows(m.cin, m.cout, 1) if m is not None else 0
-        if rows <= 0:
-            return None, 0
-        key = ("tiles", si) + tuple(mask.shape) + (mask.device,)
-        buf = self._ws.get(key)
-        if buf is None:
-            B, H, W = mask.shape
-            n_tiles = B * ((H + rows - 1) // rows) * ((W + 31) // 32)
-            buf = self._ws[key] = (torch.empty((n_tiles,), dtype=torch.int32, device=mask.device), torch.zeros((1,), dtype=torch.int32, device=mask.device))
-        return buf, rows
+    def _run_head_plan(self, x):
+        """The deblocked maps and the dense maps are fresh tensors per step (the decoder's fallback may read them after later steps were enqueued)."""
+        st = self._head_plan(x)
+        B, _, H, W = x.shape
+        st.bind("x", x)
+        tasks = []
+        for ti in range(len(self.task_deblock)):
+            up, dense = (torch.empty((B, c, 2 * H, 2 * W), dtype=self.dtype, device=x.device, memory_format=torch.channels_last) for c in (64, 16))
+            st.bind(f"up{ti}", up)
+            st.bind(f"dense{ti}", dense)
+            tasks.append(LazyTask(dense, up))
+        st.run()
+        return tasks
 
     def _stage_workspace(self, si, mods, mask):
         """Three persistent (activation, row_dirty) pairs per backbone stage for its HIP convolutions: they then touch only the row
@@ -1578,7 +1555,7 @@ class FusedPillarNeXt(nn.Module):
             self._ws[key] = [ops.conv3x3_workspace(B, cout, H, W, mask.device, self.dtype) for _ in range(3)]
         return self._ws[key]
 
-    def _stage_tiles(self, si, mods, mask, ws):
+    def _stage_tiles(self, si, mods, mask, ws, plan=None):
         """Tile list of a stage (ops.conv_tile_list): the submanifold blocks share the stage's mask, so the tiles with an active site
         or a stale row in one of the stage's three buffers are listed once and every stride-1 convolution walks the list."""
         if ws is None or not self.tile_lists:
@@ -1588,10 +1565,15 @@ class FusedPillarNeXt(nn.Module):
         if rows <= 0:
             return None
         key = ("tiles", si) + tuple(mask.shape) + (mask.device,)
-        buf = self._ws.get(key)
-        buf = ops.conv_tile_list(mask, [w[1] for w in ws], rows, out=buf)
-        self._ws[key] = buf
+        buf, dirties = self._ws.get(key), [w[1] for w in ws]
+        list_tiles = ops.conv_tile_list if plan is None else plan.tile_list
+        buf = self._ws[key] = list_tiles(mask, dirties, rows, buf if plan is None else ops.conv_tile_buffers(mask, rows, buf))
         return buf
+
+    def _lazy_tasks(self, ups):
+        """What ops.sephead_lazy / the fused lazy decoder take: per task (deblocked map, packed regression-branch weights), and the task of every class."""
+        tasks = [(up, *(getattr(self, f"lazy_{n}_{ti}") for n in ("wf1", "b1", "w2c", "b2"))) for ti, up in enumerate(ups)]
+        return tasks, [ti for ti, (names, outs) in enumerate(self.task_split) for _ in range(outs[-1])]
 
     def decoder(self):
         if self._decoder is None:
@@ -1619,9 +1601,7 @@ class FusedPillarNeXt(nn.Module):
         vel 2, rounded to bf16 like the dense output.  One HIP launch (ops.sephead_lazy); PNX_HEAD_LAZY_TORCH=1 runs the torch statement
         of the same arithmetic below instead (tests compare the two)."""
         if os.environ.get("PNX_HEAD_LAZY_TORCH", "0") != "1":
-            tasks = [(ups[ti], getattr(self, f"lazy_wf1_{ti}"), getattr(self, f"lazy_b1_{ti}"), getattr(self, f"lazy_w2c_{ti}"),
-                      getattr(self, f"lazy_b2_{ti}")) for ti in range(len(ups))]
-            class_task = [ti for ti, (names, outs) in enumerate(self.task_split) for _ in range(outs[-1])]
+            tasks, class_task = self._lazy_tasks(ups)
             return ops.sephead_lazy(tasks, class_task, ups[0].shape[0], local, seg_len, local.shape[1])
         cand = torch.zeros((*local.shape, 10), dtype=torch.float32, device=local.device)
         for ti, st in enumerate(segs):
@@ -1683,9 +1663,7 @@ class FusedPillarNeXt(nn.Module):
 
         dec = self.decoder()
         if self.use_plan and dec.use_topk and dec.pre_max <= 4096 and os.environ.get("PNX_HEAD_LAZY_TORCH", "0") != "1":
-            tasks = [(ups[ti], getattr(self, f"lazy_wf1_{ti}"), getattr(self, f"lazy_b1_{ti}"), getattr(self, f"lazy_w2c_{ti}"),
-                      getattr(self, f"lazy_b2_{ti}")) for ti in range(len(ups))]
-            class_task = [ti for ti, (names, outs) in enumerate(self.task_split) for _ in range(outs[-1])]
+            tasks, class_task = self._lazy_tasks(ups)
             return dec.launch_lazy_fused([p.dense for p in packed], tasks, class_task, tokens, dense_path)
         return dec.launch_lazy([p.dense for p in packed], lambda *a: self.lazy_eval(ups, *a), tokens, dense_path)
 

@@ -305,11 +305,33 @@ def sum_bias_act(parts, bias, relu=True):
     return out
 
 
+# The five calls a launch table can hold (plan.py) check their arguments in the helpers below, which the eager wrapper and the table
+# builder of a call share.  They read shapes, dtypes and layouts only, so CPU tensors and plan.Dyn slots pass; that a tensor lives on
+# the GPU is asked by the wrappers here and by LaunchPlan.run().
+def _like(a):
+    """The tensor itself, or the tensor a plan.Dyn slot stands for."""
+    return getattr(a, "like", a)
+
+
+def _out_hw(H, W, stride):
+    """Extent of a 3x3 / stride / pad-1 window's output."""
+    return (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+
+
+def mask_pool3_out(mask, stride, out=None):
+    """The uint8 (B,Ho,Wo) tensor mask_pool3(mask, stride) writes: `out` if it is one, a new one without."""
+    B, H, W = _like(mask).shape
+    if out is None:
+        return torch.empty((B, *_out_hw(H, W, stride)), dtype=torch.uint8, device=mask.device)
+    if tuple(_like(out).shape) != (B, *_out_hw(H, W, stride)) or _like(out).dtype != torch.uint8:
+        raise PnxError("mask_pool3: the output must be uint8 (B, Ho, Wo)")
+    return out
+
+
 def mask_pool3(mask, stride):
     """uint8 (B,H,W) occupancy -> occupancy after a 3x3/stride/pad-1 sparse conv."""
     B, H, W = mask.shape
-    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-    out = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=mask.device)
+    out = mask_pool3_out(mask, stride)
     check(lib().pnx_mask_pool3(ptr(mask), B, H, W, stride, ptr(out), stream_ptr()), "pnx_mask_pool3")
     return out
 
@@ -321,6 +343,25 @@ CONV3X3_SHAPES_S2 = {(64, 64), (64, 128), (128, 128), (128, 256), (256, 256)}
 
 
 _HALF = (torch.bfloat16, torch.float16)   # element types of the convolution kernels (csrc/conv3x3.hip is built for both)
+
+
+def _half_nhwc(x, what, dtype=None, cuda=False):
+    """channels_last bf16 / fp16 (of `dtype`, where given: a convolution call runs in one element type); cuda: and on the GPU."""
+    x = _like(x)
+    if cuda and not x.is_cuda:
+        raise PnxError(f"{what} needs a CUDA (ROCm) tensor; the convolutions have no CPU implementation")
+    if not (x.dtype in _HALF and x.dtype == (dtype or x.dtype) and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        raise PnxError(f"{what} needs a channels_last bf16 / fp16 tensor" + (" of the input's dtype" if dtype else ""))
+    return x
+
+
+def _conv_dims(what, x, wfrag, y, cout, scale, cuda=False):
+    """deconv2x2 / sephead_out: -> (B, H, W, Cin, PNX_BF16 / PNX_F16); y, where given, is the (B, cout, scale*H, scale*W) output."""
+    xs = _half_nhwc(x, what, cuda=cuda)
+    B, ci, H, W = xs.shape
+    if wfrag.dtype != xs.dtype or (y is not None and tuple(_half_nhwc(y, what + " output", xs.dtype).shape) != (B, cout, scale * H, scale * W)):
+        raise PnxError(f"{what}: weights of another dtype than the input / output of the wrong shape")
+    return B, H, W, ci, _DT[xs.dtype]
 
 
 def _conv_fn(name, dtype):
@@ -357,9 +398,7 @@ def deconv2x2_pack_weights(w, dtype=torch.bfloat16):
 def deconv2x2(x, wfrag, bias, cout, relu=True):
     """x (B,Cin,H,W) channels_last bf16 / fp16 -> [relu](conv_transpose2d(x, W, stride 2) + bias) as (B,Cout,2H,2W) channels_last, same dtype
     (wfrag packed in that dtype)."""
-    if not (x.is_cuda and x.dtype in _HALF and x.is_contiguous(memory_format=torch.channels_last) and wfrag.dtype == x.dtype):
-        raise PnxError("deconv2x2 needs a channels_last bf16 / fp16 CUDA tensor and weights of the same dtype")
-    B, ci, H, W = x.shape
+    B, H, W, ci, _ = _conv_dims("deconv2x2", x, wfrag, None, cout, 2, cuda=True)
     y = torch.empty((B, cout, 2 * H, 2 * W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     check(_conv_fn("deconv2x2", x.dtype)(ptr(x), ptr(wfrag), ptr(bias), ptr(y), B, H, W, ci, cout, 1 if relu else 0, stream_ptr()), "pnx_deconv2x2_bf16")
     return y
@@ -377,9 +416,7 @@ def sephead_pack_weights(w2, dtype=torch.bfloat16):
 
 def sephead_out(x, wfrag, bias):
     """x (B, nb*64, H, W) channels_last bf16 / fp16 -> (B, 16, H, W) channels_last, same dtype: the last 3x3 conv of every SepHead branch of a task."""
-    if not (x.is_cuda and x.dtype in _HALF and x.is_contiguous(memory_format=torch.channels_last) and wfrag.dtype == x.dtype):
-        raise PnxError("sephead_out needs a channels_last bf16 / fp16 CUDA tensor and weights of the same dtype")
-    B, ci, H, W = x.shape
+    B, H, W, ci, _ = _conv_dims("sephead_out", x, wfrag, None, 16, 1, cuda=True)
     y = torch.empty((B, 16, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     check(_conv_fn("sephead_out", x.dtype)(ptr(x), ptr(wfrag), ptr(bias), ptr(y), B, H, W, ci // 64, stream_ptr()), "pnx_sephead_out_bf16")
     return y
@@ -676,33 +713,48 @@ def conv_tile_rows(cin, cout, stride=1):
     return int(lib().pnx_conv3x3_tile_rows(cin, cout, stride))
 
 
+def conv_tile_buffers(mask, tile_rows, out=None):
+    """The (list int32[>= n_tiles], count int32[1]) pair conv_tile_list(mask, ..., tile_rows) fills: `out` if it is one, a new one without."""
+    B, H, W = _like(mask).shape
+    n_tiles = B * ((H + tile_rows - 1) // tile_rows) * ((W + 31) // 32)
+    if out is None:
+        return torch.empty((n_tiles,), dtype=torch.int32, device=mask.device), torch.zeros((1,), dtype=torch.int32, device=mask.device)
+    if out[0].numel() < n_tiles or out[0].dtype != torch.int32 or out[1].dtype != torch.int32:
+        raise PnxError("conv_tile_list: needs an int32 list of >= n_tiles entries + an int32 count")
+    return out
+
+
 def conv_tile_list(mask, dirties, tile_rows, out=None):
     """(list int32[n_tiles], count int32[1]) of the tile_rows x 32 tiles of `mask` (B,H,W uint8) that hold an active site or a stale row
     of one of the `dirties` (row_dirty arrays of conv3x3_workspace buffers); pass it as tiles= to every stride-1 conv over this mask."""
     B, H, W = mask.shape
-    n_tiles = B * ((H + tile_rows - 1) // tile_rows) * ((W + 31) // 32)
-    if out is None:
-        out = (torch.empty((n_tiles,), dtype=torch.int32, device=mask.device), torch.zeros((1,), dtype=torch.int32, device=mask.device))
+    out = conv_tile_buffers(mask, tile_rows, out)
     arr = (ctypes.c_void_p * max(len(dirties), 1))(*[d.data_ptr() for d in dirties])
     check(lib().pnx_conv_tile_list(ptr(mask), arr, len(dirties), B, H, W, tile_rows, ptr(out[0]), ptr(out[1]), stream_ptr()), "pnx_conv_tile_list")
     return out
+
+
+def _conv3x3_dims(x, wfrag, cout, stride, mask, residual, out, cuda=False):
+    """-> (B, H, W, Cin, PNX_BF16 / PNX_F16, Ho, Wo); out: None, or the (y, row_dirty) pair the call writes -- (y, None) for a plain output buffer."""
+    xs = _half_nhwc(x, "conv3x3", cuda=cuda)
+    if wfrag.dtype != xs.dtype or (residual is not None and _like(residual).dtype != xs.dtype):
+        raise PnxError("conv3x3: weights / residual of another dtype than the input")
+    B, ci, H, W = xs.shape
+    Ho, Wo = _out_hw(H, W, stride)
+    if out is not None:
+        y, dirty = out
+        if (tuple(_half_nhwc(y, "conv3x3 output", xs.dtype).shape) != (B, cout, Ho, Wo)
+                or (dirty is not None and (mask is None or tuple(dirty.shape) != (B, Ho, (Wo + 31) // 32)))):
+            raise PnxError("conv3x3: output / workspace of the wrong shape (a workspace needs a mask)")
+    return B, H, W, ci, _DT[xs.dtype], Ho, Wo
 
 
 def conv3x3_masked(x, wfrag, bias, cout, stride=1, mask=None, residual=None, relu=True, out=None, tiles=None):
     """x (B,Cin,H,W) channels_last bf16 / fp16 -> (B,Cout,Ho,Wo) channels_last, same dtype (wfrag packed in it); mask uint8 (B,Ho,Wo) of the OUTPUT sites.
     out = (y, row_dirty) from conv3x3_workspace: write into the persistent buffer, touching only row segments that are or were active.
     tiles = conv_tile_list(mask, ...) of the same mask (stride 1 only): walk the listed tiles instead of all of them."""
-    if not (x.is_cuda and x.dtype in _HALF and x.is_contiguous(memory_format=torch.channels_last) and wfrag.dtype == x.dtype
-            and (residual is None or residual.dtype == x.dtype)):
-        raise PnxError("conv3x3_masked needs a channels_last bf16 / fp16 CUDA tensor, with weights and residual of the same dtype")
-    B, ci, H, W = x.shape
-    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-    if out is not None:
-        y, dirty = out
-        if mask is None or tuple(y.shape) != (B, cout, Ho, Wo) or tuple(dirty.shape) != (B, Ho, (Wo + 31) // 32) or y.dtype != x.dtype:
-            raise PnxError("conv3x3_masked: out= needs a mask and a workspace of the output shape")
-    else:
-        y, dirty = torch.empty((B, cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last), None
+    B, H, W, ci, _, Ho, Wo = _conv3x3_dims(x, wfrag, cout, stride, mask, residual, out, cuda=True)
+    y, dirty = out if out is not None else (torch.empty((B, cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last), None)
     tl, tc = tiles if tiles is not None else (None, None)
     check(_conv_fn("conv3x3", x.dtype)(ptr(x), ptr(wfrag), ptr(bias), ptr(residual), ptr(mask), ptr(y), B, H, W, ci, cout, stride, 1 if relu else 0,
                                        ptr(dirty), ptr(tl), ptr(tc), stream_ptr()), "pnx_conv3x3")

@@ -1,11 +1,10 @@
 """Launch tables for include/pnx.h::pnx_enqueue: the C-ABI calls of a model section with their arguments frozen once, replayed per frame
-batch by ONE call (csrc/enqueue.hip).  The builder methods mirror the wrappers of ops.py (same checks, same shapes) but record the call
-instead of issuing it; tensors named as `dynamic` are re-bound per step (bind), everything else must stay alive and in place -- the
-plan keeps references."""
+batch by ONE call (csrc/enqueue.hip).  A builder method takes what the wrapper of the same call in ops.py takes and passes that wrapper's
+own argument checks (the helpers in front of it there), but records the call instead of issuing it; tensors named as `dynamic` are re-bound per step (bind),
+everything else must stay alive and in place -- the plan keeps references."""
 import ctypes
 
-import torch
-
+from . import ops
 from ._lib import PnxError, check, lib, stream_ptr
 
 OP_MASK_POOL3, OP_TILE_LIST, OP_CONV3X3, OP_DECONV2X2, OP_SEPHEAD_OUT = 1, 2, 3, 4, 5
@@ -23,24 +22,6 @@ class Dyn:
 
     def __init__(self, name, like):
         self.name, self.like = name, like
-
-
-def _t(a):
-    return a.like if isinstance(a, Dyn) else a
-
-
-def _nhwc_half(x, what, like=None):
-    """channels_last bf16 / fp16 (and, with `like`, of like's dtype: a convolution call runs in one element type)."""
-    x = _t(x)
-    if not (x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise PnxError(f"{what} needs a channels_last bf16 / fp16 tensor")
-    if like is not None and x.dtype != _t(like).dtype:
-        raise PnxError(f"{what}: dtype differs from the input's")
-    return x
-
-
-def _dt(x):
-    return 2 if _t(x).dtype == torch.float16 else 1   # PNX_F16 / PNX_BF16: selects the pnx_*_f16 twin in csrc/enqueue.hip
 
 
 class LaunchPlan:
@@ -67,48 +48,35 @@ class LaunchPlan:
                 self._keep.append(a)
         self._ops.append(op)
 
-    # ---- builders (ops.py: mask_pool3, conv_tile_list, conv3x3_masked, deconv2x2, sephead_out)
+    # ---- builders (ops.py: mask_pool3, conv_tile_list, conv3x3_masked, deconv2x2, sephead_out); each returns what its call will write.
+    # dt (PNX_BF16 / PNX_F16) selects the pnx_*_f16 twin in csrc/enqueue.hip
     def mask_pool3(self, mask_in, mask_out, stride):
-        B, H, W = _t(mask_in).shape
-        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-        if tuple(_t(mask_out).shape) != (B, Ho, Wo) or _t(mask_out).dtype != torch.uint8:
-            raise PnxError("mask_pool3: mask_out must be uint8 (B, Ho, Wo)")
-        self._add(OP_MASK_POOL3, [B, H, W, stride], [mask_in, mask_out])
+        self._add(OP_MASK_POOL3, [*ops._like(mask_in).shape, stride], [mask_in, ops.mask_pool3_out(mask_in, stride, mask_out)])
+        return mask_out
 
     def tile_list(self, mask, dirties, tile_rows, out):
-        B, H, W = _t(mask).shape
-        n_tiles = B * ((H + tile_rows - 1) // tile_rows) * ((W + 31) // 32)
-        if len(dirties) > 8 or out[0].numel() < n_tiles or out[0].dtype != torch.int32 or out[1].dtype != torch.int32:
-            raise PnxError("tile_list: at most 8 row_dirty arrays, int32 list of >= n_tiles entries + int32 count")
-        self._add(OP_TILE_LIST, [len(dirties), B, H, W, tile_rows], [mask, out[0], out[1]] + list(dirties))
+        if len(dirties) > 8:
+            raise PnxError("tile_list: an entry has room for 8 row_dirty arrays")
+        tl, tc = ops.conv_tile_buffers(mask, tile_rows, out)
+        self._add(OP_TILE_LIST, [len(dirties), *ops._like(mask).shape, tile_rows], [mask, tl, tc] + list(dirties))
+        return out
 
     def conv3x3(self, x, wfrag, bias, cout, stride=1, mask=None, residual=None, relu=True, out=None, tiles=None):
         """out = (y, row_dirty) workspace pair, or (y, None) for a plain output buffer."""
-        xs = _nhwc_half(x, "conv3x3")
-        B, ci, H, W = xs.shape
-        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-        y, dirty = out
-        ys = _nhwc_half(y, "conv3x3 output", x)
-        if wfrag.dtype != xs.dtype or (residual is not None and _t(residual).dtype != xs.dtype):
-            raise PnxError("conv3x3: weights / residual of another dtype than the input")
-        if tuple(ys.shape) != (B, cout, Ho, Wo) or (dirty is not None and (mask is None or tuple(dirty.shape) != (B, Ho, (Wo + 31) // 32))):
-            raise PnxError("conv3x3: output / workspace of the wrong shape")
+        B, H, W, ci, dt, _, _ = ops._conv3x3_dims(x, wfrag, cout, stride, mask, residual, out)
         tl, tc = tiles if tiles is not None else (None, None)
-        self._add(OP_CONV3X3, [B, H, W, ci, cout, stride, 1 if relu else 0, _dt(x)], [x, wfrag, bias, residual, mask, y, dirty, tl, tc])
+        self._add(OP_CONV3X3, [B, H, W, ci, cout, stride, 1 if relu else 0, dt], [x, wfrag, bias, residual, mask, *out, tl, tc])
+        return out[0]
 
     def deconv2x2(self, x, wfrag, bias, cout, y, relu=True):
-        xs = _nhwc_half(x, "deconv2x2")
-        B, ci, H, W = xs.shape
-        if tuple(_nhwc_half(y, "deconv2x2 output", x).shape) != (B, cout, 2 * H, 2 * W) or wfrag.dtype != xs.dtype:
-            raise PnxError("deconv2x2: output of the wrong shape / weights of another dtype")
-        self._add(OP_DECONV2X2, [B, H, W, ci, cout, 1 if relu else 0, _dt(x)], [x, wfrag, bias, y])
+        B, H, W, ci, dt = ops._conv_dims("deconv2x2", x, wfrag, y, cout, 2)
+        self._add(OP_DECONV2X2, [B, H, W, ci, cout, 1 if relu else 0, dt], [x, wfrag, bias, y])
+        return y
 
     def sephead_out(self, x, wfrag, bias, y):
-        xs = _nhwc_half(x, "sephead_out")
-        B, ci, H, W = xs.shape
-        if tuple(_nhwc_half(y, "sephead_out output", x).shape) != (B, 16, H, W) or wfrag.dtype != xs.dtype:
-            raise PnxError("sephead_out: output of the wrong shape / weights of another dtype")
-        self._add(OP_SEPHEAD_OUT, [B, H, W, ci // 64, _dt(x)], [x, wfrag, bias, y])
+        B, H, W, ci, dt = ops._conv_dims("sephead_out", x, wfrag, y, 16, 1)
+        self._add(OP_SEPHEAD_OUT, [B, H, W, ci // 64, dt], [x, wfrag, bias, y])
+        return y
 
     # ---- replay
     def freeze(self):
