@@ -527,6 +527,39 @@ int pnx_center_loss_backward(const void* const* maps7, void* const* grads7, cons
                              float* coef_scratch, void* workspace, size_t workspace_bytes, pnx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CenterHead training labels from ground-truth boxes (csrc/assign.hip): det3d/datasets/pipelines/assign.py:23-116 with the Gaussian helpers of
+ * det3d/datasets/pipelines/center_utils.py:12-60, all tasks of a frame batch in one call -- the producer of the label lists
+ * pnx_center_loss_forward consumes.
+ *   gt_boxes   (batch, k, 9) fp32 rows [x, y, z, dx, dy, dz, vx, vy, yaw], padded to k objects per frame
+ *   gt_cls     (batch, k) int32: index into the descriptor's class table; an index outside [0, n_classes) skips the object (an unknown name)
+ *   num_gt     (batch) int32 objects per frame, or NULL = k for every frame; rows beyond it are never read
+ *   desc_host  the config's fp64 values (NOT pnx_geom's fp32 casts: the reference divides by the Python floats), per task its
+ *              out_size_factor, map size (h, w) = grid[:2] // out_size_factor and class count, and the class -> (task, class in task) table
+ * Per task t (HOST arrays of n_tasks device pointers), every element written by the call, no clearing needed:
+ *   hm (batch, ncls_t, h_t, w_t) fp32;  anno_box (batch, max_objs, 10) fp32 [dx, dy, z, log dims (3), vx, vy, sin, cos];
+ *   ind, cat (batch, max_objs) int64;  mask (batch, max_objs) uint8;  gt_boxes_out (batch, max_objs, 7) fp32 [box[0:6], yaw]
+ *   counts   (batch, n_tasks) int32: objects the task accepted BEFORE the max_objs cut (the reference raises IndexError beyond it; here the
+ *            objects past max_objs are dropped from the lists and from the heat map)
+ * An object is skipped unless dx, dy > 0, its centre is finite and its centre cell (truncation of the fp32 cell coordinate) lies inside the map.
+ * Integer outputs and the copies equal the reference's bit for bit; log / sin / cos are the fp64 values rounded once (the reference takes them in
+ * fp32); hm = (float)exp(-(dx^2 + dy^2) / (2 sigma^2)) in fp64 over the (2r+1)^2 window, maximum over the objects.  Deterministic.
+ * workspace: pnx_assign_workspace_bytes(batch, n_tasks, max_objs). */
+#define PNX_ASSIGN_MAX_TASKS 8
+#define PNX_ASSIGN_MAX_CLASSES 32
+typedef struct pnx_assign_desc {
+  double lo[2];    /* pc_range[0:2] */
+  double voxel[2]; /* voxel_size[0:2] */
+  double overlap;  /* gaussian_overlap */
+  int32_t min_radius, max_objs, n_tasks, n_classes;
+  int32_t osf[PNX_ASSIGN_MAX_TASKS], h[PNX_ASSIGN_MAX_TASKS], w[PNX_ASSIGN_MAX_TASKS], ncls[PNX_ASSIGN_MAX_TASKS];
+  int32_t class_task[PNX_ASSIGN_MAX_CLASSES], class_cls[PNX_ASSIGN_MAX_CLASSES];
+} pnx_assign_desc;
+size_t pnx_assign_workspace_bytes(int32_t batch, int32_t n_tasks, int32_t max_objs);
+int pnx_assign_labels(const float* gt_boxes, const int32_t* gt_cls, const int32_t* num_gt, int32_t batch, int32_t k, const pnx_assign_desc* desc_host,
+                      float* const* hm_host, float* const* anno_box_host, int64_t* const* ind_host, uint8_t* const* mask_host, int64_t* const* cat_host,
+                      float* const* gt_boxes_out_host, int32_t* counts, void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * One-call enqueue of prebuilt launch tables (csrc/enqueue.hip).  The reference's step is a Python call tree
  * (det3d/models/detectors/single_stage.py:22-33, then CenterHead.predict centerhead.py:231-384); the arguments of this library's calls for
  * the backbone, the head and the decoder do not change between frame batches (persistent workspaces, weights, shapes), so a host

@@ -26,6 +26,16 @@ class PnxGroupGeom(ctypes.Structure):   # include/pnx.h: pnx_group_geom
                 ("prefilter", ctypes.c_int32), ("keep_min", ctypes.c_float * 3), ("keep_max", ctypes.c_float * 3)]
 
 
+PNX_ASSIGN_MAX_TASKS, PNX_ASSIGN_MAX_CLASSES = 8, 32
+
+
+class PnxAssignDesc(ctypes.Structure):   # include/pnx.h: pnx_assign_desc -- the config's fp64 values, not PnxGeom's fp32 casts
+    _fields_ = [("lo", ctypes.c_double * 2), ("voxel", ctypes.c_double * 2), ("overlap", ctypes.c_double), ("min_radius", ctypes.c_int32),
+                ("max_objs", ctypes.c_int32), ("n_tasks", ctypes.c_int32), ("n_classes", ctypes.c_int32)] + \
+               [(k, ctypes.c_int32 * PNX_ASSIGN_MAX_TASKS) for k in ("osf", "h", "w", "ncls")] + \
+               [(k, ctypes.c_int32 * PNX_ASSIGN_MAX_CLASSES) for k in ("class_task", "class_cls")]
+
+
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
@@ -116,6 +126,8 @@ PROTOTYPES = {
     "pnx_center_loss_workspace_bytes": (_sz, [_i32, _i32]),
     "pnx_center_loss_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "pnx_center_loss_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pnx_assign_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pnx_assign_labels": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(PnxAssignDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pnx_boxes_overlap_bev": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "pnx_boxes_iou_bev": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "pnx_boxes_aligned_overlap_bev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),

@@ -938,3 +938,48 @@ def sp3_dense_backward(dout, coords, channels):
     dfeat = torch.empty((coords.shape[0], C), dtype=torch.float32, device=dout.device)
     check(lib().pnx_sp3_dense_backward(ptr(dout), ptr(coords), coords.shape[0], C, B, _i3((D, H, W)), ptr(dfeat), stream_ptr()), "pnx_sp3_dense_backward")
     return dfeat
+
+
+# --------------------------------------------------------------------------------------------- label assignment
+_ASSIGN_OUT = (("hm", torch.float32), ("anno_box", torch.float32), ("ind", torch.int64), ("mask", torch.uint8), ("cat", torch.int64),
+               ("gt_boxes", torch.float32))
+
+
+def assign_workspace_bytes(batch, n_tasks, max_objs):
+    return int(lib().pnx_assign_workspace_bytes(batch, n_tasks, max_objs))
+
+
+def assign_labels(gt_boxes, gt_classes, num_gt, desc, out, counts, ws):
+    """pnx_assign_labels: gt_boxes (B, K, 9) fp32, gt_classes (B, K) int32 indices into desc's class table, num_gt (B) int32 or None;
+    desc a _lib.PnxAssignDesc; out: {hm, anno_box, ind, mask, cat, gt_boxes} -> one tensor per task, every element written by the call;
+    counts (B, n_tasks) int32; ws: uint8 buffer of assign_workspace_bytes(B, n_tasks, max_objs).  Returns out."""
+    _need_cuda(gt_boxes, "gt_boxes")
+    _need_cuda(gt_classes, "gt_classes")
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 9:
+        raise PnxError(f"gt_boxes must be (B, K, 9) fp32, got {tuple(gt_boxes.shape)} {gt_boxes.dtype}")
+    B, K = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+    if gt_classes.dtype != torch.int32 or tuple(gt_classes.shape) != (B, K):
+        raise PnxError(f"gt_classes must be ({B}, {K}) int32, got {tuple(gt_classes.shape)} {gt_classes.dtype}")
+    if num_gt is not None:
+        _need_cuda(num_gt, "num_gt")
+        if num_gt.dtype != torch.int32 or tuple(num_gt.shape) != (B,):
+            raise PnxError(f"num_gt must be ({B},) int32, got {tuple(num_gt.shape)} {num_gt.dtype}")
+    T, M = int(desc.n_tasks), int(desc.max_objs)
+    want = {"hm": lambda t: (B, desc.ncls[t], desc.h[t], desc.w[t]), "anno_box": lambda t: (B, M, 10), "ind": lambda t: (B, M),
+            "mask": lambda t: (B, M), "cat": lambda t: (B, M), "gt_boxes": lambda t: (B, M, 7)}
+    arrs = []
+    for key, dt in _ASSIGN_OUT:
+        if len(out[key]) != T:
+            raise PnxError(f"assign_labels: {len(out[key])} `{key}` outputs for {T} tasks")
+        for t, o in enumerate(out[key]):
+            _need_cuda(o, f"{key}[{t}]")
+            if o.dtype != dt or tuple(o.shape) != tuple(want[key](t)):
+                raise PnxError(f"assign_labels: {key}[{t}] must be {tuple(want[key](t))} {dt}, got {tuple(o.shape)} {o.dtype}")
+        arrs.append((ctypes.c_void_p * T)(*[o.data_ptr() for o in out[key]]))
+    _need_cuda(counts, "counts")
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (B, T):
+        raise PnxError(f"counts must be ({B}, {T}) int32, got {tuple(counts.shape)} {counts.dtype}")
+    _need_cuda(ws, "workspace")
+    check(lib().pnx_assign_labels(ptr(gt_boxes), ptr(gt_classes), ptr(num_gt), B, K, ctypes.byref(desc), *arrs, ptr(counts), ptr(ws),
+                                  ws.numel() * ws.element_size(), stream_ptr()), "pnx_assign_labels")
+    return out

@@ -178,3 +178,35 @@ def clustered_boxes(n, seed, spread=40.0, n_clusters=None):
     # strictly decreasing scores (torch.sort tie order is unspecified -- box_torch_ops.py:13)
     scores = (scores - np.arange(n, dtype=np.float32) * 1e-6).astype(np.float32)
     return b, scores
+
+
+# typical (dx, dy, dz) per nuScenes class, in the order of the detector's task list (car, truck, construction_vehicle, bus, trailer, barrier,
+# motorcycle, bicycle, pedestrian, traffic_cone)
+GT_CLASS_SIZES = np.array([[4.6, 1.95, 1.73], [6.9, 2.5, 2.85], [6.4, 2.85, 3.2], [11.0, 2.95, 3.5], [12.3, 2.9, 3.9], [0.5, 2.5, 1.0],
+                           [2.1, 0.8, 1.5], [1.7, 0.6, 1.3], [0.73, 0.67, 1.77], [0.41, 0.41, 1.07]])
+
+
+def make_gt_boxes(config="C2", batch=1, seed=0, max_gt=200, n_classes=10):
+    """Ground-truth boxes for the label assignment: (boxes (batch, max_gt, 9) fp32 [x y z dx dy dz vx vy yaw], classes (batch, max_gt) int32,
+    num_gt (batch) int32).  Frame b holds num_gt[b] in [max_gt / 2, max_gt] objects; the rows beyond are zero with class -1.  Sizes are the
+    class's typical size +-15 %; about 3 % of the centres lie outside the x/y range (they exercise the range test) and about 2 % carry class -1
+    (a name no task lists); class i uses GT_CLASS_SIZES[i % 10]."""
+    cfg = CONFIGS[config]
+    lo, hi = np.asarray(cfg["pc_range"][:3], np.float64), np.asarray(cfg["pc_range"][3:], np.float64)
+    rng = np.random.default_rng(5000 + seed)
+    boxes = np.zeros((batch, max_gt, 9), np.float32)
+    classes = np.full((batch, max_gt), -1, np.int32)
+    num_gt = rng.integers(max(max_gt // 2, 1), max_gt + 1, batch).astype(np.int32) if max_gt > 0 else np.zeros(batch, np.int32)
+    for b in range(batch):
+        n = int(num_gt[b])
+        c = rng.integers(0, n_classes, n)
+        xy = rng.uniform(lo[:2], hi[:2], (n, 2))
+        out = rng.random(n) < 0.03
+        xy[out] = hi[:2] + rng.uniform(0.01, 3.0, (int(out.sum()), 2))
+        boxes[b, :n, 0:2] = xy
+        boxes[b, :n, 2] = rng.uniform(lo[2] + 1.0, min(hi[2], lo[2] + 5.0), n)
+        boxes[b, :n, 3:6] = GT_CLASS_SIZES[c % 10] * rng.uniform(0.85, 1.15, (n, 3))
+        boxes[b, :n, 6:8] = rng.normal(0.0, 2.0, (n, 2)) * (rng.random((n, 1)) < 0.5)
+        boxes[b, :n, 8] = rng.uniform(-np.pi, np.pi, n)
+        classes[b, :n] = np.where(rng.random(n) < 0.02, -1, c)
+    return boxes, classes, num_gt

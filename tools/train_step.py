@@ -51,6 +51,8 @@ def main():
     ap.add_argument("--nhwc", action="store_true", help="channels_last without autocast (fp32): the fused masked-BatchNorm kernels need NHWC maps")
     ap.add_argument("--total-steps", type=int, default=1000, help="length of the OneCycle schedule the steps are taken from")
     ap.add_argument("--find", action="store_true", help="let MIOpen time its solvers per conv problem (cudnn.benchmark): ~2 minutes in step 0, a step about a tenth faster")
+    ap.add_argument("--gt-boxes", action="store_true", help="labels from synthetic ground-truth boxes through AssignLabel.assign (csrc/assign.hip) inside every step, "
+                    "instead of the fixed random label tensors")
     ap.add_argument("--yaml", default="", help="build the detector from this YAML (configs/pillarnext_b_waymo.yaml) instead of the nuScenes PillarNeXt-B")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = bool(a.find)
@@ -80,11 +82,23 @@ def main():
     pts = torch.from_numpy(synth.make_batch(a.config, a.batch, "sweep", frame0=rank * a.batch)).to(dev)
     net = model.module if hasattr(model, "module") else model
     ny, nx = (int(v) for v in net.reader.grid_size)
-    ex = synthetic_labels(tasks, a.batch, ny // 4, nx // 4, 500, dev, 100 + rank)
+    if a.gt_boxes:
+        # the reference's prepare_label stage (configs/dataset/base/base_det_train.yaml: gaussian_overlap 0.1, max_objs 500, min_radius 2), on the device
+        from pillarnext_amd.assign import AssignLabel
+
+        assigner = AssignLabel(tasks, 0.1, 500, 2, list(cfg["pc_range"]), list(cfg["voxel_size"]), [4] * len(tasks))
+        assert assigner.map_size == [(ny // 4, nx // 4)] * len(tasks)
+        gt_boxes, gt_classes, num_gt = (torch.from_numpy(v).to(dev) for v in synth.make_gt_boxes(a.config, a.batch, 100 + rank, n_classes=len(assigner.class_names)))
+        ex = {}
+    else:
+        ex = synthetic_labels(tasks, a.batch, ny // 4, nx // 4, 500, dev, 100 + rank)
     ex.update(points=pts, batch_size=a.batch)
     for it in range(a.steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if a.gt_boxes:
+            labels = assigner.assign(gt_boxes, gt_classes, num_gt)
+            ex.update({k: labels[k] for k in ("hm", "ind", "mask", "cat", "anno_box", "gt_boxes")})
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.amp):
             loss, _ = model(ex)
         opt.zero_grad()
