@@ -193,6 +193,21 @@ int pnx_pfn_layer_eval(const float* xa, int32_t lda, int32_t ca, const float* gb
 int pnx_bilinear_gather(const void* image, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t channels, const float* pos, int32_t pos_ld,
                         const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate,
                         int64_t n, float* out, int32_t out_ld, pnx_stream_t stream);
+/* Gradient of pnx_bilinear_gather with respect to the map (the backward of the sampling in training), fp32:
+ *   grad_image[b, y, x, :] = sum over the points p and their corners that are cell (b, y, x) of  weight * grad_out[p, :]
+ *   with sample image, sample position, the four CLAMPED corners and their weights exactly those of pnx_bilinear_gather (the same fp32
+ *   operations): weights can be negative, and where clamping makes two corners one cell that cell receives both terms.
+ *   grad_out (n, grad_ld) fp32, grad_ld >= channels, unit column stride: a column slice of a wider buffer is read in place.
+ *   grad_image (batch, h, w, channels) fp32 is FULLY WRITTEN: cells without a contribution hold +0, the caller does not clear it.  A point whose
+ *   image index is outside [0, batch) contributes nothing.  Any channel count; ds_rate a power of two; n = 0 zero-fills grad_image.
+ * Deterministic: the points are sorted by base cell (a stable radix sort of the point indices, so ties stay in point order) and every cell sums
+ * its terms in fp32 in that order, one rounded product per term -- no floating-point atomics; the same inputs give the same bits.  All work
+ * happens inside the call and its workspace (pnx_bilinear_gather_backward_workspace_bytes; 0 = sizes beyond 32-bit indices; 256-byte aligned). */
+size_t pnx_bilinear_gather_backward_workspace_bytes(int64_t n, int32_t batch, int32_t h, int32_t w);
+int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t batch, int32_t h, int32_t w, int32_t channels, const float* pos,
+                                 int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords,
+                                 const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* grad_image, void* workspace, size_t workspace_bytes,
+                                 pnx_stream_t stream);
 
 /* torch_scatter.scatter_max(x, unq_inv, dim=0) over pillars (call sites :43,:180), fp32, values of
  * any sign.  x (n, channels); index (n) int64 in [0,P); out (P, channels); argmax (P, channels) int64 =

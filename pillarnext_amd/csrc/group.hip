@@ -7,6 +7,8 @@
 //   pnx_pfn_layer_eval   PFNLayer in eval mode with arbitrary widths (pillar_encoder.py:35-50 as SingleView uses it, mvf_encoder.py:150-163,
 //                        187-188): Linear + folded BatchNorm + ReLU + per-cell max, the concat [x, max[inv]] read in place by the next layer
 //   pnx_bilinear_gather  SingleView.bilinear_interpolate (mvf_encoder.py:208-246) on a channels-last map
+//   pnx_bilinear_gather_backward  its gradient w.r.t. the map: a stable sort of the points by base cell, then one wave per map cell sums its
+//                        contributions in sorted order (no atomics: deterministic)
 //
 // Grouping without sorting a point, like the pillar reader's rank outputs: torch.unique(dim=0) over [b, c0, c1(, c2)] rows orders the cells
 // lexicographically = by the linear key ((b*g0 + c0)*g1 + c1)(*g2 + c2); every occupied key sets one bit of a key-order bitmap, a popcount
@@ -14,6 +16,9 @@
 // atomics: exact for these magnitudes, so the result does not depend on the order in which the points arrive (deterministic), and the
 // mean is fp32(sum) / fp32(count) as in the pillar reader.
 // HBM-bound glue around two hash-free passes over the points; nothing here is shaped into a GEMM.
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
 #include "pnx_common.h"
 #define PNX_HD __device__ __forceinline__
 #include "pnx_detmath.h"
@@ -277,6 +282,28 @@ template <>
 __device__ __forceinline__ float ld_f<uint16_t>(const uint16_t* p) { return __uint_as_float((uint32_t)*p << 16); }  // bf16
 template <>
 __device__ __forceinline__ float ld_f<_Float16>(const _Float16* p) { return (float)*p; }
+// sample position, clamped corners and weights of one point: shared by the forward and the backward, so that both use the same bits
+struct BilSample {
+  int x0, x1, y0, y1;
+  float wa, wb, wc, wd;  // corners (y0, x0), (y1, x0), (y0, x1), (y1, x1)
+};
+__device__ __forceinline__ BilSample bil_sample(const float* __restrict__ pos2, float mn0, float mn1, float vs0, float vs1, float inv_ds, int H, int W) {
+  BilSample s;
+  // (feature_pos - bias) / voxel_size (mvf_encoder.py:184), then / ds_rate (:204): ds_rate is a power of two, so * (1 / ds) is exact
+  const float x = __fmul_rn(__fdiv_rn(__fsub_rn(pos2[0], mn0), vs0), inv_ds);
+  const float y = __fmul_rn(__fdiv_rn(__fsub_rn(pos2[1], mn1), vs1), inv_ds);
+  int x0 = (int)floorf(x), y0 = (int)floorf(y);
+  int x1 = x0 + 1, y1 = y0 + 1;
+  s.x0 = min(max(x0, 0), W - 1), s.x1 = min(max(x1, 0), W - 1);
+  s.y0 = min(max(y0, 0), H - 1), s.y1 = min(max(y1, 0), H - 1);
+  // the weights use the CLAMPED corners, as the reference does (:233-240)
+  s.wa = __fmul_rn(__fsub_rn((float)s.x1, x), __fsub_rn((float)s.y1, y));
+  s.wb = __fmul_rn(__fsub_rn((float)s.x1, x), __fsub_rn(y, (float)s.y0));
+  s.wc = __fmul_rn(__fsub_rn(x, (float)s.x0), __fsub_rn((float)s.y1, y));
+  s.wd = __fmul_rn(__fsub_rn(x, (float)s.x0), __fsub_rn(y, (float)s.y0));
+  return s;
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_bilinear(const T* __restrict__ img, int B, int H, int W, int C, const float* __restrict__ pos, int ldp,
                                                      float mn0, float mn1, float vs0, float vs1, const int32_t* __restrict__ cell_coords,
@@ -285,31 +312,138 @@ __global__ __launch_bounds__(kBlock) void k_bilinear(const T* __restrict__ img, 
   const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
   for (int64_t p = wave; p < n; p += nwaves) {
     const int b = cell_coords[inv[p] * 3];                 // unq[unq_inv][:, 0] (mvf_encoder.py:203)
-    // (feature_pos - bias) / voxel_size (mvf_encoder.py:184), then / ds_rate (:204): ds_rate is a power of two, so * (1 / ds) is exact
-    const float x = __fmul_rn(__fdiv_rn(__fsub_rn(pos[p * ldp + 0], mn0), vs0), inv_ds);
-    const float y = __fmul_rn(__fdiv_rn(__fsub_rn(pos[p * ldp + 1], mn1), vs1), inv_ds);
-    int x0 = (int)floorf(x), y0 = (int)floorf(y);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    x0 = min(max(x0, 0), W - 1), x1 = min(max(x1, 0), W - 1);
-    y0 = min(max(y0, 0), H - 1), y1 = min(max(y1, 0), H - 1);
-    // the weights use the CLAMPED corners, as the reference does (:233-240)
-    const float wa = __fmul_rn(__fsub_rn((float)x1, x), __fsub_rn((float)y1, y));
-    const float wb = __fmul_rn(__fsub_rn((float)x1, x), __fsub_rn(y, (float)y0));
-    const float wc = __fmul_rn(__fsub_rn(x, (float)x0), __fsub_rn((float)y1, y));
-    const float wd = __fmul_rn(__fsub_rn(x, (float)x0), __fsub_rn(y, (float)y0));
+    const BilSample s = bil_sample(pos + p * ldp, mn0, mn1, vs0, vs1, inv_ds, H, W);
     const bool okb = b >= 0 && b < B;
-    const T* ia = img + (((int64_t)(okb ? b : 0) * H + y0) * W + x0) * C;
-    const T* ib = img + (((int64_t)(okb ? b : 0) * H + y1) * W + x0) * C;
-    const T* ic = img + (((int64_t)(okb ? b : 0) * H + y0) * W + x1) * C;
-    const T* id = img + (((int64_t)(okb ? b : 0) * H + y1) * W + x1) * C;
+    const T* ia = img + (((int64_t)(okb ? b : 0) * H + s.y0) * W + s.x0) * C;
+    const T* ib = img + (((int64_t)(okb ? b : 0) * H + s.y1) * W + s.x0) * C;
+    const T* ic = img + (((int64_t)(okb ? b : 0) * H + s.y0) * W + s.x1) * C;
+    const T* id = img + (((int64_t)(okb ? b : 0) * H + s.y1) * W + s.x1) * C;
     for (int c = lane; c < C; c += 64) {
-      float v = __fmul_rn(ld_f(ia + c), wa);
-      v = __fadd_rn(v, __fmul_rn(ld_f(ib + c), wb));
-      v = __fadd_rn(v, __fmul_rn(ld_f(ic + c), wc));
-      v = __fadd_rn(v, __fmul_rn(ld_f(id + c), wd));
+      float v = __fmul_rn(ld_f(ia + c), s.wa);
+      v = __fadd_rn(v, __fmul_rn(ld_f(ib + c), s.wb));
+      v = __fadd_rn(v, __fmul_rn(ld_f(ic + c), s.wc));
+      v = __fadd_rn(v, __fmul_rn(ld_f(id + c), s.wd));
       out[p * ldo + c] = okb ? v : 0.f;
     }
   }
+}
+
+// ---- gradient of that sampling w.r.t. the map, without atomics.  A point's four clamped corners lie in {y0, y0 + 1} x {x0, x0 + 1} around its
+// clamped base corner, so cell (b, y, x) receives from the points whose base is (y - 1 .. y, x - 1 .. x) only.
+//   k_bilinear_keys    key[p] = (b H + y0) W + x0 of the clamped base corner; B H W (one past the last cell) for a point outside the batch
+//   rocprim radix sort point indices by key; stable, so the points of one base cell stay in point order
+//   k_bilinear_bounds  start[k] = first sorted position whose key is >= k, k = 0 .. B H W: one binary search per cell
+//   k_bilinear_grad    one wave per cell, lanes = channels: walks the (at most) two runs of sorted positions [start(y', x - 1), start(y', x) + ...)
+//                      for y' = y - 1, y; 64 points at a time the lanes recompute corners and weights (one point each), then the wave adds, point
+//                      by point and corner by corner (a, b, c, d), the product weight * grad_out row of every corner that IS this cell: clamping makes
+//                      that a per-point decision (x1 == x0 in the last column and left of the map).  fp32, a fixed order: the same bits every run.
+__global__ __launch_bounds__(kBlock) void k_bilinear_keys(int B, int H, int W, const float* __restrict__ pos, int ldp, float mn0, float mn1, float vs0,
+                                                          float vs1, const int32_t* __restrict__ cell_coords, const int64_t* __restrict__ inv,
+                                                          float inv_ds, int64_t n, uint32_t* __restrict__ key) {
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= n) return;
+  const int b = cell_coords[inv[p] * 3];
+  const BilSample s = bil_sample(pos + p * ldp, mn0, mn1, vs0, vs1, inv_ds, H, W);
+  key[p] = b >= 0 && b < B ? (uint32_t)((b * H + s.y0) * W + s.x0) : (uint32_t)(B * H * W);
+}
+
+__global__ __launch_bounds__(kBlock) void k_bilinear_bounds(const uint32_t* __restrict__ skey, int n, int cells, int32_t* __restrict__ start) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k > cells) return;
+  int lo = 0, hi = n;  // lower bound of k in the sorted keys
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (skey[mid] < (uint32_t)k) lo = mid + 1;
+    else hi = mid;
+  }
+  start[k] = lo;
+}
+
+constexpr int kBilChunk = 4;  // channels per lane and pass: 256 channels per walk of the cell's points
+
+__global__ __launch_bounds__(kBlock) void k_bilinear_grad(const float* __restrict__ g, int ldg, int B, int H, int W, int C, const float* __restrict__ pos,
+                                                          int ldp, float mn0, float mn1, float vs0, float vs1, float inv_ds,
+                                                          const int32_t* __restrict__ order, const int32_t* __restrict__ start,
+                                                          float* __restrict__ gi) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6), nwaves = (int)(((int64_t)gridDim.x * kBlock) >> 6);
+  const int cells = B * H * W;
+  for (int cell = wave; cell < cells; cell += nwaves) {
+    const int x = cell % W, y = (cell / W) % H;
+    for (int c0 = 0; c0 < C; c0 += 64 * kBilChunk) {
+      float acc[kBilChunk];
+#pragma unroll
+      for (int k = 0; k < kBilChunk; k++) acc[k] = 0.f;
+      for (int r = 0; r < 2; r++) {
+        if (y - 1 + r < 0) continue;
+        const int row0 = cell - x - (1 - r) * W;  // key of (b, y - 1 + r, 0)
+        const int s = start[row0 + max(x - 1, 0)], e = start[row0 + x + 1];
+        for (int i0 = s; i0 < e; i0 += 64) {
+          // one point per lane: which of its corners are this cell, and their weights
+          int p = 0;
+          unsigned m = 0;
+          BilSample sm = {};
+          if (i0 + lane < e) {
+            p = order[i0 + lane];
+            sm = bil_sample(pos + (int64_t)p * ldp, mn0, mn1, vs0, vs1, inv_ds, H, W);
+            m = (sm.y0 == y && sm.x0 == x ? 1u : 0u) | (sm.y1 == y && sm.x0 == x ? 2u : 0u) | (sm.y0 == y && sm.x1 == x ? 4u : 0u) |
+                (sm.y1 == y && sm.x1 == x ? 8u : 0u);
+          }
+          unsigned long long todo = __ballot(m != 0);
+          while (todo) {
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int pj = __builtin_amdgcn_readlane(p, j);
+            const unsigned mj = (unsigned)__builtin_amdgcn_readlane((int)m, j);
+            const float* row = g + (int64_t)pj * ldg + c0 + lane;
+            float gv[kBilChunk];
+#pragma unroll
+            for (int k = 0; k < kBilChunk; k++) gv[k] = c0 + lane + 64 * k < C ? row[64 * k] : 0.f;
+            const float w4[4] = {sm.wa, sm.wb, sm.wc, sm.wd};
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+              if (mj >> q & 1) {  // wave-uniform
+                const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w4[q]), j));
+#pragma unroll
+                for (int k = 0; k < kBilChunk; k++) acc[k] = __fadd_rn(acc[k], __fmul_rn(w, gv[k]));
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kBilChunk; k++)
+        if (c0 + lane + 64 * k < C) gi[(int64_t)cell * C + c0 + lane + 64 * k] = acc[k];
+    }
+  }
+}
+
+struct BilGradWs {
+  uint32_t *key, *skey;
+  int32_t *order, *start;
+  void* sort;
+  size_t sort_bytes, bytes;
+};
+BilGradWs bilgrad_carve(void* ws, int64_t n, int64_t cells) {
+  PnxCarver c(ws);
+  BilGradWs w;
+  w.key = c.take<uint32_t>((size_t)n);
+  w.skey = c.take<uint32_t>((size_t)n);
+  w.order = c.take<int32_t>((size_t)n);
+  w.start = c.take<int32_t>((size_t)cells + 1);
+  w.sort_bytes = 0;
+  if (n > 0) {
+    rocprim::counting_iterator<int32_t> iota(0);
+    (void)rocprim::radix_sort_pairs(nullptr, w.sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, iota, (int32_t*)nullptr, (size_t)n, 0u, 32u,
+                                    (hipStream_t) nullptr);
+  }
+  w.sort = c.take<char>(w.sort_bytes);
+  w.bytes = c.used() + 256;
+  return w;
+}
+// n and batch * h * w must fit the 32-bit keys and positions
+bool bilgrad_sizes_ok(int64_t n, int32_t batch, int32_t h, int32_t w) {
+  return n >= 0 && n < ((int64_t)1 << 31) - 64 && batch > 0 && h > 0 && w > 0 && (int64_t)batch * h * w < ((int64_t)1 << 31) - 1;
 }
 
 }  // namespace
@@ -405,6 +539,49 @@ int pnx_bilinear_gather(const void* image, int32_t dtype, int32_t batch, int32_t
   else
     k_bilinear<_Float16><<<(unsigned)nb, kBlock, 0, st>>>((const _Float16*)image, batch, h, w, channels, pos, pos_ld, pos_min2_host[0], pos_min2_host[1],
                                                           pos_voxel2_host[0], pos_voxel2_host[1], cell_coords, unq_inv, inv_ds, n, out, out_ld);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_bilinear_gather_backward_workspace_bytes(int64_t n, int32_t batch, int32_t h, int32_t w) {
+  if (!bilgrad_sizes_ok(n, batch, h, w)) return 0;
+  return bilgrad_carve(nullptr, n, (int64_t)batch * h * w).bytes;
+}
+
+int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t batch, int32_t h, int32_t w, int32_t channels, const float* pos,
+                                 int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords,
+                                 const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* grad_image, void* workspace, size_t workspace_bytes,
+                                 pnx_stream_t stream) {
+  PNX_REQUIRE(pos_min2_host && pos_voxel2_host && grad_image && batch > 0 && h > 0 && w > 0 && channels > 0 && pos_ld >= 2 && n >= 0 &&
+                  (n == 0 || (grad_out && pos && cell_coords && unq_inv)),
+              PNX_ERR_INVALID, "pnx_bilinear_gather_backward: bad arguments");
+  PNX_REQUIRE(grad_ld >= channels, PNX_ERR_INVALID, "pnx_bilinear_gather_backward: grad_ld %d < %d channels", grad_ld, channels);
+  PNX_REQUIRE(ds_rate >= 1 && (ds_rate & (ds_rate - 1)) == 0, PNX_ERR_UNSUPPORTED, "pnx_bilinear_gather_backward: ds_rate %d is not a power of two", ds_rate);
+  PNX_REQUIRE(bilgrad_sizes_ok(n, batch, h, w), PNX_ERR_UNSUPPORTED, "pnx_bilinear_gather_backward: %lld points / %d x %d x %d cells exceed 32-bit indices",
+              (long long)n, batch, h, w);
+  hipStream_t st = (hipStream_t)stream;
+  const int cells = batch * h * w;
+  if (n == 0) {
+    PNX_CHECK_HIP(hipMemsetAsync(grad_image, 0, (size_t)cells * channels * sizeof(float), st));
+    return PNX_OK;
+  }
+  PNX_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 255) == 0, PNX_ERR_INVALID, "pnx_bilinear_gather_backward: workspace must be 256-byte aligned");
+  const BilGradWs ws = bilgrad_carve(workspace, n, cells);
+  PNX_REQUIRE(workspace_bytes >= ws.bytes, PNX_ERR_WORKSPACE, "pnx_bilinear_gather_backward: workspace %zu bytes < %zu needed", workspace_bytes, ws.bytes);
+  const float inv_ds = 1.0f / (float)ds_rate;
+  const float mn0 = pos_min2_host[0], mn1 = pos_min2_host[1], vs0 = pos_voxel2_host[0], vs1 = pos_voxel2_host[1];
+  k_bilinear_keys<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(batch, h, w, pos, pos_ld, mn0, mn1, vs0, vs1, cell_coords, unq_inv, inv_ds, n, ws.key);
+  PNX_LAUNCH_CHECK();
+  unsigned bits = 1;
+  while (bits < 32 && ((uint32_t)1 << bits) <= (uint32_t)cells) bits++;  // 2^bits > cells: the sentinel key of a point outside the batch sorts last
+  size_t sort_bytes = ws.sort_bytes;
+  rocprim::counting_iterator<int32_t> iota(0);
+  PNX_CHECK_HIP(rocprim::radix_sort_pairs(ws.sort, sort_bytes, (const uint32_t*)ws.key, ws.skey, iota, ws.order, (size_t)n, 0u, bits, st));
+  k_bilinear_bounds<<<(unsigned)(((int64_t)cells + 1 + kBlock - 1) / kBlock), kBlock, 0, st>>>(ws.skey, (int)n, cells, ws.start);
+  int64_t nb = ((int64_t)cells + 3) / 4;
+  if (nb > 16384) nb = 16384;
+  k_bilinear_grad<<<(unsigned)nb, kBlock, 0, st>>>(grad_out, grad_ld, batch, h, w, channels, pos, pos_ld, mn0, mn1, vs0, vs1, inv_ds, ws.order, ws.start,
+                                                   grad_image);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -14,6 +14,7 @@ that reproduces spconv's active-site semantics exactly in eval mode (SURVEY.md H
     BatchNorm1d over sites: per-channel affine at active sites, zero elsewhere (all convs are bias-free).
 """
 import copy
+import inspect
 import os
 import weakref
 
@@ -1034,6 +1035,8 @@ class SingleStageDetector(nn.Module):
             occ = torch.empty((batch_size, ny, nx), dtype=torch.uint8, device=points.device)
             canvas = self.reader.forward_dense(points, batch_size, dtype=dt, occupancy=occ)
             x = self.backbone.forward_dense(canvas, occ.unsqueeze(1).to(dt))
+        elif self.backbone is None and "batch_size" in inspect.signature(self.reader.forward).parameters:
+            x = self.reader(points, batch_size=batch_size)   # a reader that ends in the dense map (MVFFeatureNet): an empty frame keeps its slot
         else:
             x = self.reader(points)
             if self.backbone is not None:

@@ -10,11 +10,15 @@ Same class names, constructor arguments and state-dict keys as the reference.  W
     mask (mvf:290-297) is the call's prefilter and both views write their columns into one (N', 20) buffer -- the torch.cat of mvf:304 never runs;
   * the PFN layers of a view in eval mode: pnx_pfn_layer_eval (Linear + folded BatchNorm + ReLU + per-cell max; the concat [x, max[inv]] of a
     non-last layer is read in place by the next one); in training they are reader.PFNLayer on the HIP scatter-max (autograd);
-  * sampling the view's map back at the points: pnx_bilinear_gather (eval) / its torch statement over flat indices (training: needs autograd);
+  * sampling the view's map back at the points: pnx_bilinear_gather, in eval and as the forward of ops.BilinearGather in training, whose backward is
+    pnx_bilinear_gather_backward (deterministic; PNX_TRAIN_BILINEAR_HIP=0 selects the torch statement over flat indices, which also serves when the
+    positions need a gradient);
   * the per-view sparse ResNets: in eval mode the masked HIP convolution kernels of the PillarNeXt backbone (csrc/conv3x3.hip; BatchNorm folded,
     bf16, the 48 / 96 / 192 channels zero-padded to the kernels' 64 / 128 / 256: _HipViewNet), in training the masked-dense blocks of models.py
     (spconv is absent from the image; like the backbone that part is unpinned); the two PointNets: torch Linear (rocBLAS) + BatchNorm + ReLU.
 CUDA tensors only: there is no CPU path."""
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -270,8 +274,16 @@ class SingleView(nn.Module):
         x = canvas.permute(0, 3, 1, 2)                                         # channels_last view of the NHWC canvas
         for blk in self.blocks:
             x, mask = blk(x, mask)
+        return self.sample(x, pos, unq, unq_inv)
+
+    def sample(self, x, pos, unq, unq_inv):
+        """The view's map x (B, C, H', W') sampled at the points (mvf:213-216) -> (N, C)."""
         if not (self.training or torch.is_grad_enabled() and x.requires_grad) and x.dtype in ops._DT:
             return ops.bilinear_gather(x.contiguous(memory_format=torch.channels_last), pos, self.bias, self.voxel_size, unq, unq_inv, int(self.ds_rate))
+        if (torch.is_grad_enabled() and x.requires_grad and x.is_cuda and x.dtype in ops._DT and not pos.requires_grad
+                and os.environ.get("PNX_TRAIN_BILINEAR_HIP") != "0"):
+            # training: the eval kernel forward, its gradient w.r.t. the map on pnx_bilinear_gather_backward
+            return ops.BilinearGather.apply(x.contiguous(memory_format=torch.channels_last), pos, self.bias, self.voxel_size, unq, unq_inv, int(self.ds_rate))
         vs = torch.from_numpy(self.voxel_size).type_as(pos).to(pos.device)
         bias = torch.from_numpy(self.bias).type_as(pos).to(pos.device)
         cell = (pos - bias) / vs

@@ -213,6 +213,59 @@ def bilinear_gather(image, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rat
     return out
 
 
+_BILGRAD_WS = Workspace()
+
+
+def bilinear_gather_backward(grad_out, image_shape, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate):
+    """pnx_bilinear_gather_backward: grad_out (N, C) fp32 with unit column stride (a column slice of a wider buffer is read in place), image_shape
+    (B, C, H, W), the other arguments as bilinear_gather's -> the gradient of the map, (B, C, H, W) channels_last fp32, fully written.  Deterministic."""
+    B, C, H, W = (int(v) for v in image_shape)
+    n = pos.shape[0]
+    if not (grad_out.dtype == torch.float32 and grad_out.dim() == 2 and tuple(grad_out.shape) == (n, C) and (n == 0 or grad_out.stride(1) == 1 or C == 1)
+            and (n <= 1 or grad_out.stride(0) >= C)):
+        raise PnxError("bilinear_gather_backward: grad_out (N, C) fp32 rows with unit column stride and a row stride >= C")
+    if not (pos.dtype == torch.float32 and pos.dim() == 2 and pos.shape[1] >= 2 and pos.stride(1) == 1 and cell_coords.dtype == torch.int32
+            and unq_inv.dtype == torch.int64 and unq_inv.shape[0] == n):
+        raise PnxError("bilinear_gather_backward: pos fp32 rows, int32 coords, int64 unq_inv")
+    ds = int(ds_rate)
+    if ds < 1 or ds & (ds - 1):
+        raise PnxError(f"bilinear_gather_backward: ds_rate {ds_rate} is not a power of two")
+    if not (grad_out.is_cuda and pos.is_cuda and cell_coords.is_cuda and unq_inv.is_cuda):
+        raise PnxError("bilinear_gather_backward needs CUDA (ROCm) tensors; there is no CPU implementation")
+    nbytes = lib().pnx_bilinear_gather_backward_workspace_bytes(n, B, H, W)
+    if nbytes == 0:
+        raise PnxError("bilinear_gather_backward: point or cell count beyond 32-bit indices")
+    out = torch.empty((B, H, W, C), dtype=torch.float32, device=grad_out.device)
+    ws = _BILGRAD_WS.get(nbytes, grad_out.device)
+    mn = (ctypes.c_float * 2)(float(pos_min[0]), float(pos_min[1]))
+    vs = (ctypes.c_float * 2)(float(pos_voxel[0]), float(pos_voxel[1]))
+    check(lib().pnx_bilinear_gather_backward(ptr(grad_out), grad_out.stride(0) if n > 1 else C, B, H, W, C, ptr(pos), pos.stride(0) if n > 1 else 2, mn, vs,
+                                             ptr(cell_coords.contiguous()), ptr(unq_inv.contiguous()), ds, n, ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+          "pnx_bilinear_gather_backward")
+    return out.permute(0, 3, 1, 2)
+
+
+class BilinearGather(torch.autograd.Function):
+    """bilinear_gather with a gradient for the map (training): forward = the eval kernel, backward = bilinear_gather_backward, cast to the map's dtype.
+    pos and the index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, image, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate):
+        ctx.save_for_backward(pos, cell_coords, unq_inv)
+        ctx.geom = (tuple(image.shape), image.dtype, pos_min, pos_voxel, ds_rate)
+        return bilinear_gather(image, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pos, cell_coords, unq_inv = ctx.saved_tensors
+        shape, dtype, pos_min, pos_voxel, ds_rate = ctx.geom
+        g = grad_out
+        if g.dtype != torch.float32 or g.shape[0] > 0 and (g.stride(1) != 1 or g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+            g = g.float().contiguous()          # an expanded or transposed gradient; the column slice torch.cat's backward hands over is read in place
+        gi = bilinear_gather_backward(g, shape, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate)
+        return gi.to(dtype), None, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------------------------- IoU / NMS
 def _boxes(t, name):
     _need_cuda(t, name)
