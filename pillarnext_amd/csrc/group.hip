@@ -292,7 +292,9 @@ __device__ __forceinline__ BilSample bil_sample(const float* __restrict__ pos2, 
   // (feature_pos - bias) / voxel_size (mvf_encoder.py:184), then / ds_rate (:204): ds_rate is a power of two, so * (1 / ds) is exact
   const float x = __fmul_rn(__fdiv_rn(__fsub_rn(pos2[0], mn0), vs0), inv_ds);
   const float y = __fmul_rn(__fdiv_rn(__fsub_rn(pos2[1], mn1), vs1), inv_ds);
-  int x0 = (int)floorf(x), y0 = (int)floorf(y);
+  // clamped to [-1, W] / [-1, H] as floats, before the conversion: the reference floors to int64, so a position billions of cells away keeps both
+  // corners on one border, while (int) saturates at 2^31 - 1 and the + 1 would wrap to the other side of the map.  Inside the interval nothing changes.
+  int x0 = (int)fminf(fmaxf(floorf(x), -1.f), (float)W), y0 = (int)fminf(fmaxf(floorf(y), -1.f), (float)H);
   int x1 = x0 + 1, y1 = y0 + 1;
   s.x0 = min(max(x0, 0), W - 1), s.x1 = min(max(x1, 0), W - 1);
   s.y0 = min(max(y0, 0), H - 1), s.y1 = min(max(y1, 0), H - 1);
@@ -504,7 +506,9 @@ int pnx_pfn_layer_eval(const float* xa, int32_t lda, int32_t ca, const float* gb
                        int32_t cout, int64_t n, int64_t num_groups, float* y, int32_t ldy, float* gmax, pnx_stream_t stream) {
   PNX_REQUIRE(n >= 0 && ca >= 0 && cb >= 0 && ca + cb >= 1 && ca + cb <= 128 && cout >= 1 && cout <= 256, PNX_ERR_UNSUPPORTED,
               "pnx_pfn_layer_eval: %d + %d inputs (at most 128), %d outputs (at most 256)", ca, cb, cout);
-  PNX_REQUIRE(wt && shift && (ca == 0 || (xa && lda >= ca)) && (cb == 0 || (gb && inv)) && (gmax == nullptr || inv) && (y == nullptr || ldy >= cout),
+  // n == 0 (every point outside the range): the per-point arrays may be NULL, the cells are still zeroed
+  PNX_REQUIRE(wt && shift && (ca == 0 || lda >= ca) && (n == 0 || ((ca == 0 || xa) && (cb == 0 || (gb && inv)) && (gmax == nullptr || inv))) &&
+                  (y == nullptr || ldy >= cout),
               PNX_ERR_INVALID, "pnx_pfn_layer_eval: null pointer / leading dimension");
   PNX_REQUIRE((size_t)(ca + cb) * cout * sizeof(float) <= 64 * 1024, PNX_ERR_UNSUPPORTED, "pnx_pfn_layer_eval: weight larger than 64 KiB");
   hipStream_t st = (hipStream_t)stream;
@@ -521,7 +525,8 @@ int pnx_pfn_layer_eval(const float* xa, int32_t lda, int32_t ca, const float* gb
 int pnx_bilinear_gather(const void* image, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t channels, const float* pos, int32_t pos_ld,
                         const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate,
                         int64_t n, float* out, int32_t out_ld, pnx_stream_t stream) {
-  PNX_REQUIRE(image && pos && pos_min2_host && pos_voxel2_host && cell_coords && unq_inv && out && batch > 0 && h > 0 && w > 0 && channels > 0 && pos_ld >= 2 && out_ld >= channels && n >= 0,
+  PNX_REQUIRE(image && pos_min2_host && pos_voxel2_host && batch > 0 && h > 0 && w > 0 && channels > 0 && pos_ld >= 2 && out_ld >= channels && n >= 0 &&
+                  (n == 0 || (pos && cell_coords && unq_inv && out)),
               PNX_ERR_INVALID, "pnx_bilinear_gather: bad arguments");
   PNX_REQUIRE(dtype == PNX_F32 || dtype == PNX_BF16 || dtype == PNX_F16, PNX_ERR_UNSUPPORTED, "pnx_bilinear_gather: fp32, bf16 or fp16 maps");
   PNX_REQUIRE(ds_rate >= 1 && (ds_rate & (ds_rate - 1)) == 0, PNX_ERR_UNSUPPORTED, "pnx_bilinear_gather: ds_rate %d is not a power of two", ds_rate);

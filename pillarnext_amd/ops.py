@@ -186,7 +186,7 @@ def pfn_layer_eval(xa, gb, inv, wt, shift, num_groups, store=True, want_max=True
     _need_cuda(wt, "wt")
     n = xa.shape[0]
     ca, cb, cout = xa.shape[1], 0 if gb is None else gb.shape[1], wt.shape[1]
-    if not (xa.is_cuda and xa.dtype == torch.float32 and xa.stride(1) == 1 and wt.shape[0] == ca + cb and wt.dtype == torch.float32 and shift.numel() == cout):
+    if not (xa.is_cuda and xa.dtype == torch.float32 and (n == 0 or xa.stride(1) == 1) and wt.shape[0] == ca + cb and wt.dtype == torch.float32 and shift.numel() == cout):
         raise PnxError("pfn_layer_eval: xa (N, ca) fp32 with unit column stride, wt (ca + cb, cout) fp32, shift (cout)")
     if gb is not None:
         _need_cuda(gb, "gb")
