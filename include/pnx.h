@@ -120,7 +120,8 @@ float pnx_profile_last_voxelize_us(void); /* same interval: reader start -> pill
  * The host side of this protocol, including the BatchNorm algebra for dW0/dW1, is pillarnext_amd/pfn_train.py.
  *   params    pnx_pfn_train_param_floats(F) floats: W1 (64x64) | mu1 invstd1 gamma1 beta1 m1 m2 (6 x 64) | mu0 invstd0 gamma0 beta0
  *             (4 x 32) | W0 (32 x (F+5));  m1 = sum(dz1)/N, m2 = sum(dz1*xhat1)/N (backward pass 1 only)
- *   partials  pnx_pfn_train_partial_floats(F, which) floats, which = 0,1 (forward pass 0,1), 3,4 (backward pass 0,1)
+ *   partials  pnx_pfn_train_partial_floats(F, which) floats, which = 0,1 (forward pass 0,1), 3,4 (backward pass 0,1); the Gram sums of the
+ *             forward passes are DOUBLES (8-byte aligned, two floats of the count each), the backward sums fp32
  * pnx_pfn_forward_train: pass 0 groups the points (coords, pillar_of_point, counts = {P, N'} as in pnx_reader_forward) and returns the
  *   Gram sums of the decorated features; pass 1 (params with mu0/invstd0) the Gram sums of u = [h0, max h0]; pass 2 (mu1/invstd1 too)
  *   writes feat_max (P,64) fp32.

@@ -837,7 +837,8 @@ int pnx_launch_pfn3_tail(int F, const uint32_t* rec64, const uint32_t* pfirst, c
                          hipStream_t st, const int32_t* row_of = nullptr);
 
 // implemented in pfn_train.hip
-int pnx_launch_pfn_train(int F, int pass, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* counters,
+int pnx_launch_pfn_train(int F, int pass, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, uint32_t* canon, uint32_t* big,
+                         const int32_t* counters,
                          const float* prm, float* part, const float* G, const float* out_saved, float* out, int64_t out_rows, hipStream_t st);
 int pnx_pfn_train_blocks(void);
 
@@ -1103,8 +1104,8 @@ size_t pnx_pfn_train_param_floats(int32_t F) { return 4096 + 6 * 64 + 4 * 32 + 3
 size_t pnx_pfn_train_partial_floats(int32_t F, int32_t which) {
   const size_t C0 = (size_t)F + 5, nb = (size_t)pnx_pfn_train_blocks();
   switch (which) {
-    case 0: return nb * (C0 + C0 * C0);         // forward pass 0: per block  [F1 | F2]
-    case 1: return nb * 4 * 64 * 65;            // forward pass 1: per wave   [64][U2 row | U1]
+    case 0: return 2 * nb * (C0 + C0 * C0);     // forward pass 0: per block  [F1 | F2], DOUBLES (two floats each)
+    case 1: return 2 * nb * 4 * 64 * 65;        // forward pass 1: per wave   [64][U2 row | U1], doubles
     case 3: return nb * 4 * 64 * 66;            // backward pass 0: per wave  [64][A row | D1 | D2]
     case 4: return nb * 4 * 32 * (C0 + 2);      // backward pass 1: per wave  [32][B0 row | E1 | E2]
   }
@@ -1130,7 +1131,9 @@ int pnx_pfn_forward_train(int32_t pass, const float* points, int64_t n, int32_t 
     if (rc != PNX_OK) return rc;
     if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   }
-  return pnx_launch_pfn_train(stride - 1, pass, w.rec64, w.pfirst, w.pcnt, w.counters, params, partials, nullptr, nullptr, feat_max, pillar_capacity, st);
+  // w.plist (n + 8 words, otherwise the round-1 voxelizer's) holds the canonical record order that pass 0 writes and every later pass walks,
+  // w.slot (likewise) pass 0's list of the pillars of more than 64 records
+  return pnx_launch_pfn_train(stride - 1, pass, w.rec64, w.pfirst, w.pcnt, reinterpret_cast<uint32_t*>(w.plist), reinterpret_cast<uint32_t*>(w.slot), w.counters, params, partials, nullptr, nullptr, feat_max, pillar_capacity, st);
 }
 
 int pnx_pfn_backward(int32_t pass, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, const float* params, const float* grad_feat_max,
@@ -1140,7 +1143,7 @@ int pnx_pfn_backward(int32_t pass, int64_t n, int32_t stride, int32_t batch, con
   PNX_REQUIRE(stride >= 4 && stride <= 7, PNX_ERR_UNSUPPORTED, "row_stride %d", stride);
   PNX_REQUIRE(workspace_bytes >= pnx_reader_workspace_bytes(n, batch, g), PNX_ERR_WORKSPACE, "workspace too small");
   const ReaderWs w = carve(workspace, n, batch, g);  // the records written by pnx_pfn_forward_train(pass 0) on the same workspace
-  return pnx_launch_pfn_train(stride - 1, pass == 0 ? 3 : 4, w.rec64, w.pfirst, w.pcnt, w.counters, params, partials, grad_feat_max, feat_max, nullptr, 0,
+  return pnx_launch_pfn_train(stride - 1, pass == 0 ? 3 : 4, w.rec64, w.pfirst, w.pcnt, reinterpret_cast<uint32_t*>(w.plist), reinterpret_cast<uint32_t*>(w.slot), w.counters, params, partials, grad_feat_max, feat_max, nullptr, 0,
                               (hipStream_t)stream);
 }
 

@@ -10,6 +10,8 @@ updates the running statistics (momentum 0.01, unbiased variance) and does the B
   backward  D1 = sum dz1, D2 = sum dz1*xhat1, A = sum dz1^T u        ->  dgamma1, dbeta1, dW1 = g1*is1*(A - D1/N U1^T - D2/N Xhat1U)
             E1 = sum dz0, E2 = sum dz0*xhat0, B0 = sum dz0^T f       ->  dgamma0, dbeta0, dW0 likewise, with
             Xhat1U = is1 * (W1 U2 - mu1 U1^T) and Xhat0F = is0 * (W0 F2 - mu0 F1^T)  (x is linear in u / f, so no extra pass)
+The Gram sums F1, F2, U1, U2 arrive as DOUBLES (exact fp32 x fp32 products added in fp64 by the kernels): var = E[x^2] - E[x]^2 is formed here
+in fp64 and must not carry the rounding of an fp32 sum (a pillar of thousands of points adds thousands of equal terms to one wave's sum).
 Parameter gradients are the LOCAL sums (DistributedDataParallel averages them), statistics are global -- as in SyncBatchNorm."""
 import ctypes
 
@@ -52,7 +54,7 @@ class FusedPFNTrain(torch.autograd.Function):
         coords = torch.empty((cap, 3), dtype=torch.int32, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
         out = torch.empty((cap, 64), dtype=torch.float32, device=dev)
-        nb = int(L.pnx_pfn_train_partial_floats(F, 0)) // (C0 + C0 * C0)
+        nb = int(L.pnx_pfn_train_partial_floats(F, 0)) // (2 * (C0 + C0 * C0))  # the Gram sums of passes 0 and 1 arrive as doubles
 
         def fwd(pass_, prm, part):
             check(L.pnx_pfn_forward_train(pass_, ptr(points), n, stride, batch, ctypes.byref(geom), ptr(prm), ptr(part), ptr(out), cap, ptr(coords),
@@ -62,7 +64,7 @@ class FusedPFNTrain(torch.autograd.Function):
         pa = torch.empty(int(L.pnx_pfn_train_partial_floats(F, 0)), dtype=torch.float32, device=dev)
         fwd(0, None, pa)
         P, n_kept = (int(v) for v in counts.tolist())  # the output shape is data dependent (as in the reference): one sync
-        sa = pa.view(nb, C0 + C0 * C0).sum(0, dtype=torch.float64)
+        sa = pa.view(torch.float64).view(nb, C0 + C0 * C0).sum(0)
         F1, F2 = sa[:C0], sa[C0:].view(C0, C0)
         st0 = torch.cat([w0d @ F1, ((w0d @ F2) * w0d).sum(1), torch.tensor([float(n_kept)], dtype=torch.float64, device=dev)])
         st0 = _all_reduce(st0, group)
@@ -74,7 +76,7 @@ class FusedPFNTrain(torch.autograd.Function):
         nw = nb * 4
         pb = torch.empty(int(L.pnx_pfn_train_partial_floats(F, 1)), dtype=torch.float32, device=dev)
         fwd(1, prm, pb)
-        sb = pb.view(nw, 64, 65).sum(0, dtype=torch.float64)
+        sb = pb.view(torch.float64).view(nw, 64, 65).sum(0)
         U2, U1 = sb[:, :64], sb[:, 64]
         st1 = _all_reduce(torch.cat([w1d @ U1, ((w1d @ U2) * w1d).sum(1)]), group)
         mu1 = st1[:64] / N
@@ -100,6 +102,12 @@ class FusedPFNTrain(torch.autograd.Function):
         L = lib()
         points, w0, g0, b0, w1, g1, b1, fm = ctx.saved_tensors
         ws, geom, batch, group, N, mu0, is0, mu1, is1, F1, F2, U1, U2, nb = ctx.misc
+        if fm.shape[0] == 0:  # no pillar (no point, or none inside the range): nothing was routed anywhere; an empty gradient has no data pointer to hand over
+            if group is not False:  # the other ranks wait in the two all-reduces of their backward: join them with this rank's sums, which are zero
+                _all_reduce(torch.zeros(128, dtype=torch.float64, device=points.device), group)
+                _all_reduce(torch.zeros(64, dtype=torch.float64, device=points.device), group)
+            ctx.misc = None
+            return (None,) + tuple(torch.zeros_like(p) for p in (w0, g0, b0, w1, g1, b1)) + (None, None)
         n, stride = points.shape
         F, C0 = stride - 1, stride + 4
         dev = points.device

@@ -35,3 +35,11 @@ def test_fused_reader_syncbn_world2_on_one_gpu():
     torch.cuda.empty_cache()  # the two ranks share this process's GPU: hand back what earlier tests left in the caching allocator
     r = _run(["--backend", "gloo", "--one-gpu"])
     assert r.returncode == 0 and "DDP PARITY OK" in r.stdout, r.stdout[-4000:]
+
+
+def test_fused_reader_syncbn_with_a_rank_without_pillars():
+    """Rank 1's points all lie outside the range: its backward has nothing to route, and must still join the two all-reduces the other rank
+    waits in (a missing one hangs the step); statistics, outputs and gradients equal the joint-batch run."""
+    torch.cuda.empty_cache()
+    r = _run(["--backend", "gloo", "--one-gpu", "--empty-rank", "1"], timeout=240)
+    assert r.returncode == 0 and "DDP PARITY OK" in r.stdout, r.stdout[-4000:]

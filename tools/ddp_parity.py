@@ -39,6 +39,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--one-gpu", action="store_true", help="all ranks share cuda:0; no DistributedDataParallel, gradients averaged by hand")
+    ap.add_argument("--empty-rank", type=int, default=-1, help="this rank's points all lie outside the range: it has no pillar, and must still join every exchange")
     a = ap.parse_args()
     rank, world, local = dist_utils.init(a.backend)
     assert world > 1, "run under torchrun / torch.distributed.run with >= 2 ranks"
@@ -56,6 +57,8 @@ def main():
         model = dist_utils.wrap_ddp(net, device_ids=[local], sync_batchnorm=True)
     assert net.reader.sync and net.reader._fused_supported(), "the reader must run its fused, synchronised training passes"
     clouds = [synth.make_batch("C1", B, "sweep", n=12_000 + 900 * r, frame0=r * B) for r in range(world)]  # unequal point counts per rank
+    if 0 <= a.empty_rank < world:
+        clouds[a.empty_rank][:, 1] += 1000.0
     y = model(torch.from_numpy(clouds[rank]).to(dev), B)
     # per-rank loss = sum over the local batch / global element count: the global loss is the plain SUM of the rank losses; DDP
     # averages gradients (so scale by world there), the hand-rolled path sums them
