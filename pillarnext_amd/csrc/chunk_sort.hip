@@ -15,7 +15,7 @@
 // (Round 3's chain -- k_keys, k_pack_scan, 2 x k_scan_blocks, k_bin_count, k_scan_local, k_bin_scatter -- read the points three
 // times, looked a rank up with a random 8-byte read per point and scattered 32-byte records: 244 us per 12 C2 frames.)
 #include "pnx_common.h"
-#include "spans.h"
+#include "reader_ws.h"
 
 namespace {
 
@@ -310,34 +310,32 @@ __global__ __launch_bounds__(1024) void k_span_carve(const uint32_t* __restrict_
 
 size_t pnx_chunk_sort_lds(const SpanGeom& sg) { return (size_t)kChunk * 32 + (size_t)(sg.tabw / 2) * 4 + 64; }
 
-// keys + chunk sort + slab totals + span carve.  counters / frame_lo / frame_hi must be zero; bytemap (optional, B * gy * gx bytes)
-// must be zero and receives a 1 for every occupied cell.
-int pnx_launch_chunk_sort(const float* points, int64_t n, int stride, const PnxGeomDev& g, const SpanGeom& sg, uint4* recs, uint16_t* tab,
-                          int32_t* rowframe, uint32_t* rowbase, int32_t* counters, int32_t* frame_lo, int32_t* frame_hi, uint8_t* bytemap,
-                          uint32_t* slab_tot, uint2* span_desc, int32_t* nspan, hipStream_t st, hipEvent_t sorted) {
+// keys + chunk sort + slab totals + span carve over the workspace's span tables.  w.counters / w.frame_lo / w.frame_hi must be zero;
+// bytemap (optional, B * gy * gx bytes) must be zero and receives a 1 for every occupied cell.
+int pnx_launch_chunk_sort(const ReaderWs& w, const float* points, int64_t n, int stride, const PnxGeomDev& g, uint8_t* bytemap, hipStream_t st,
+                          hipEvent_t sorted) {
+  const SpanGeom& sg = w.sg;
   PNX_REQUIRE(sg.nf <= 32768 && sg.B <= 1024, PNX_ERR_UNSUPPORTED, "%d slabs per frame / %d frames exceed the span tables", sg.nf, sg.B);
   if (sg.nchunks > 0) {
     const size_t lds = pnx_chunk_sort_lds(sg);
     const bool v2 = (reinterpret_cast<uintptr_t>(points) & 7) == 0;
-    uint32_t* tab32 = reinterpret_cast<uint32_t*>(tab);
-#define PNX_CS(S_, V_)                                                                                                                          \
-  {                                                                                                                                            \
-    static size_t lds_set = 0;                                                                                                                  \
-    if (lds > lds_set) {                                                                                                                        \
-      PNX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chunk_sort<S_, V_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      lds_set = lds;                                                                                                                            \
-    }                                                                                                                                           \
-    k_chunk_sort<S_, V_><<<sg.nchunks, kCsBlock, lds, st>>>(points, n, g, sg, recs, tab32, rowframe, rowbase, counters, frame_lo, frame_hi, bytemap); \
-  }
-    switch (stride) {
-      case 4: if (v2) PNX_CS(4, true) else PNX_CS(4, false) break;
-      case 5: PNX_CS(5, false) break;
-      case 6: if (v2) PNX_CS(6, true) else PNX_CS(6, false) break;
-      case 7: PNX_CS(7, false) break;
-      default: pnx_set_error("row_stride %d", stride); return PNX_ERR_UNSUPPORTED;
-    }
-#undef PNX_CS
-    PNX_LAUNCH_CHECK();
+    // the row stride is 1 + the point-feature count; the 8-byte loads exist for the even strides only
+    const int rc = pnx_with_features(stride - 1, [&](auto f) -> int {
+      constexpr int S = decltype(f)::value + 1;
+      auto go = [&](auto v) -> int {
+        constexpr auto kern = &k_chunk_sort<S, decltype(v)::value>;
+        if (const int rc = pnx_lds_optin<kern>(lds); rc != PNX_OK) return rc;
+        kern<<<sg.nchunks, kCsBlock, lds, st>>>(points, n, g, sg, w.srecs, reinterpret_cast<uint32_t*>(w.stab), w.srowframe, w.srowbase, w.counters, w.frame_lo,
+                                                w.frame_hi, bytemap);
+        PNX_LAUNCH_CHECK();
+        return PNX_OK;
+      };
+      if constexpr (S % 2 == 0) {
+        if (v2) return go(std::true_type{});
+      }
+      return go(std::false_type{});
+    });
+    if (rc != PNX_OK) return rc;
   }
 #ifdef PNX_BINS_TIMERS
   if (getenv("PNX_BINS_TIMERS_PRINT")) {
@@ -350,8 +348,9 @@ int pnx_launch_chunk_sort(const float* points, int64_t n, int stride, const PnxG
   }
 #endif
   if (sorted != nullptr) PNX_CHECK_HIP(hipEventRecord(sorted, st));  // the occupancy bytes are complete: the zero-fill may start
-  k_slab_totals<<<dim3((unsigned)((sg.nf + 63) / 64), (unsigned)sg.B), 64 * kTotGroups, 0, st>>>(tab, rowframe, frame_lo, frame_hi, counters, sg, slab_tot);
-  k_span_carve<<<sg.B, 1024, 0, st>>>(slab_tot, sg, span_desc, nspan);
+  k_slab_totals<<<dim3((unsigned)((sg.nf + 63) / 64), (unsigned)sg.B), 64 * kTotGroups, 0, st>>>(w.stab, w.srowframe, w.frame_lo, w.frame_hi, w.counters, sg,
+                                                                                                 w.slab_tot);
+  k_span_carve<<<sg.B, 1024, 0, st>>>(w.slab_tot, sg, w.span_desc, w.nspan);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -1500,13 +1500,9 @@ int launch_s2(const void* x, const void* wfrag, const float* bias, const uint8_t
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   int64_t nb = (int64_t)B * ((Ho + S2_TH - 1) / S2_TH) * ((Wo + 31) / 32);
   if (nb > 512) nb = 512;  // resident workgroups: 2 per CU (LDS and registers)
-  auto kern = k_conv3x3_s2<CIN, COUT, NP>;
+  constexpr auto kern = k_conv3x3_s2<CIN, COUT, NP>;
   constexpr int lds = S2_NSTAGE * 16;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PNX_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
+  if (const int rc = pnx_lds_optin<kern>(lds); rc != PNX_OK) return rc;
   kern<<<(unsigned)nb, 256, lds, st>>>((const uint16_t*)x, (const uint16_t*)x2, (const uint4*)wfrag, (const uint4*)wfrag2, bias, mask, (uint16_t*)y, B, H, W, Ho,
                                        Wo, relu, row_dirty, slot, (const uint16_t*)x3, (const uint4*)wfrag3);
   PNX_LAUNCH_CHECK();
@@ -1746,13 +1742,9 @@ int launch(const void* x, const void* wfrag, const float* bias, const void* res,
   const int64_t n_tiles = (int64_t)B * ((Ho + NT - 1) / NT) * ((Wo + 31) / 32);
   int64_t nb = (n_tiles + 3) / 4;
   if (nb > 512) nb = 512;  // persistent: 2 workgroups per CU
-  auto kern = k_conv3x3<CIN, COUT, STRIDE, W_LDS>;
+  constexpr auto kern = k_conv3x3<CIN, COUT, STRIDE, W_LDS>;
   if (W_LDS) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      PNX_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wbytes));
-      attr_done = true;
-    }
+    if (const int rc = pnx_lds_optin<kern>(wbytes); rc != PNX_OK) return rc;
   }
   kern<<<(unsigned)nb, 256, W_LDS ? wbytes : 0, st>>>((const uint16_t*)x, (const uint4*)wfrag, bias, (const uint16_t*)res, mask, (uint16_t*)y, B, H, W,
                                                     Ho, Wo, relu, row_dirty);
@@ -2218,11 +2210,7 @@ extern "C" int PNX_CONV_FN(pnx_sephead_lazy)(const PnxLazyTask* tasks, int32_t n
     a.class_task[c] = (signed char)class_task[c];
   }
   a.nc_total = nc_total, a.pre_max = pre_max, a.bps = (pre_max + kLzG - 1) / kLzG;
-  static bool attr = false;
-  if (!attr) {
-    PNX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sephead_lazy), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLzLds));
-    attr = true;
-  }
+  if (const int rc = pnx_lds_optin<&k_sephead_lazy>(kLzLds); rc != PNX_OK) return rc;
   const unsigned nb = (unsigned)((int64_t)batch * nc_total * a.bps);
   k_sephead_lazy<<<nb, 512, kLzLds, (hipStream_t)stream>>>(a, local, seg_len, out);
   PNX_LAUNCH_CHECK();

@@ -186,12 +186,8 @@ int launch_dgrad_s2(const void* g, const void* g2, const void* wt, const void* w
   int64_t nb = (int64_t)B * ((Ho + G::TG - 1) / G::TG) * ((Wo + 31) / 32);
   const int per_cu = G::LDS_BYTES <= 75 * 1024 ? 2 : 1;
   if (nb > 256 * per_cu) nb = 256 * per_cu;
-  auto kern = k_dgrad_s2<CO, CI, NP>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PNX_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-    attr_done = true;
-  }
+  constexpr auto kern = k_dgrad_s2<CO, CI, NP>;
+  if (const int rc = pnx_lds_optin<kern>(G::LDS_BYTES); rc != PNX_OK) return rc;
   const int slot = next_sched_slot();
   kern<<<(unsigned)nb, 512, G::LDS_BYTES, st>>>((const uint16_t*)g, (const uint16_t*)g2, (const uint4*)wt, (const uint4*)wt2, mask_in, dx, B, H, W, Ho, Wo, slot,
                                                 (const uint16_t*)g3, (const uint4*)wt3);

@@ -329,11 +329,7 @@ int launch_wgrad(const void* x, const void* dy, const uint8_t* mask, float* dw, 
   const int64_t n_tiles = (int64_t)batch * ((ho + Geo::TH - 1) / Geo::TH) * ((wo + 31) / 32);
   PNX_REQUIRE(n_tiles < 0x7fffffff && (n_tiles + G - 1) / G <= WG_LIST_MAX, PNX_ERR_UNSUPPORTED, "%lld tiles over %d workgroups: more than %d per workgroup",
               (long long)n_tiles, G, WG_LIST_MAX);
-  static bool attr_done = false;
-  if (!attr_done) {
-    PNX_CHECK_HIP(hipFuncSetAttribute((const void*)k_wgrad64<S, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS));
-    attr_done = true;
-  }
+  if (const int rc = pnx_lds_optin<&k_wgrad64<S, NP>>(Geo::LDS); rc != PNX_OK) return rc;
   k_wgrad64<S, NP><<<dim3((unsigned)G, (unsigned)n_pairs), 256, Geo::LDS, st>>>((const uint16_t*)x, (const uint16_t*)dy, mask, (float*)workspace, batch, h, w, ho,
                                                                                  wo, cin, cout, G, (const uint16_t*)x_lo, (const uint16_t*)dy_lo,
                                                                                  (const uint16_t*)x_mid, (const uint16_t*)dy_mid);

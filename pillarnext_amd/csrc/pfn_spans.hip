@@ -23,7 +23,7 @@
 
 #include "pnx_common.h"
 #include "pfn_common.h"
-#include "spans.h"
+#include "reader_ws.h"
 
 namespace {
 
@@ -863,8 +863,7 @@ int launch_spans(const SpanPfnArgs& A0, const Pfn3Out& out, const PnxGeomDev& g,
   const bool pack = out.g1 == nullptr && out.canvas != nullptr && out.dt != PNX_F32;
   // two workgroups per CU: 160 KiB / 2 minus room for the zero-fill workgroup that shares the CU -- LDS is handed out in 1280-byte granules:
   // 2 x 63 granules (80 000 B) + 1 for the fill = 127 of 128; at 81 000 B (2 x 64) the fill no longer fits and the reader takes 840 instead of 620 us
-  const char* l_env = getenv("PNX_BINS_LDS");
-  const size_t budget = l_env ? (size_t)atoi(l_env) : 80000;
+  const size_t budget = (size_t)pnx_env_int("PNX_BINS_LDS", 80000);
   const size_t fixed = span_pfn_lds_bytes(0, pack, A.sg.B);
   PNX_REQUIRE(fixed + (size_t)(kClassSlack + 64) * kRecW * 4 <= budget, PNX_ERR_UNSUPPORTED, "the span tables of %d frames do not fit the LDS budget", A.sg.B);
   int cap = (int)((budget - fixed) / (kRecW * 4));
@@ -872,45 +871,32 @@ int launch_spans(const SpanPfnArgs& A0, const Pfn3Out& out, const PnxGeomDev& g,
   if (c_env && atoi(c_env) >= 32 && atoi(c_env) + kClassSlack < cap) cap = atoi(c_env) + kClassSlack;
   A.cap = cap;
   const size_t lds = span_pfn_lds_bytes(cap, pack, A.sg.B);
-  const char* b_env = getenv("PNX_PFN_BLOCKS");
-  const int nb = n > 0 ? (b_env ? atoi(b_env) : 512) : 0;  // 256 CUs x 2 workgroups, persistent
-  const int grid = nb;
+  const int grid = n > 0 ? pnx_pfn_blocks() : 0;  // 256 CUs x 2 workgroups, persistent
   if (grid <= 0) return PNX_OK;
-#define PNX_GO(DT_, PACK_)                                                                                                               \
-  {                                                                                                                                     \
-    static size_t lds_set = 0;                                                                                                          \
-    if (lds > lds_set) {                                                                                                                \
-      PNX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_span_pfn<F, DT_, PACK_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      lds_set = lds;                                                                                                                    \
-    }                                                                                                                                   \
-    k_span_pfn<F, DT_, PACK_><<<grid, kSpBlock, lds, st>>>(A, out, g);                                                                      \
-  }
-  if (out.dt == PNX_F32) {
-    PNX_GO(PNX_F32, false)
-  } else if (out.dt == PNX_BF16) {
-    if (pack) PNX_GO(PNX_BF16, true) else PNX_GO(PNX_BF16, false)
-  } else {
-    if (pack) PNX_GO(PNX_F16, true) else PNX_GO(PNX_F16, false)
-  }
-#undef PNX_GO
-  PNX_LAUNCH_CHECK();
-  return PNX_OK;
+  return pnx_with_dtype_pack(out.dt, pack, [&](auto d, auto p) -> int {
+    constexpr auto kern = &k_span_pfn<F, decltype(d)::value, decltype(p)::value>;
+    if (const int rc = pnx_lds_optin<kern>(lds); rc != PNX_OK) return rc;
+    kern<<<grid, kSpBlock, lds, st>>>(A, out, g);
+    PNX_LAUNCH_CHECK();
+    return PNX_OK;
+  });
 }
 
 }  // namespace
 
-// The span grouping + PFN launch.  tick[0] must be zero (the reader's memset), tables as left by pnx_launch_chunk_sort.
-// wcomb / wblk (the reader's key-order bitmap prefix) select the rank outputs: g1 rows by global pillar rank, coords, row_of.
-int pnx_launch_span_pfn(int F, const SpanTables& T, const SpanGeom& sg, int32_t* counters, int32_t* tick, uint32_t* rec64,
-                        uint32_t* pfirst, uint32_t* pcnt, int32_t* cell_of_pillar, int32_t* row_of, int32_t* biglist, int64_t bigcap, int64_t idcap,
-                        const uint2* wcomb, const uint32_t* wblk, int32_t* coords, int64_t pillar_capacity, const float* folded, float* g1,
+// The span grouping + PFN launch.  w.tick[0] must be zero (the reader's memset), the span tables as left by pnx_launch_chunk_sort.
+// ranked (the reader's key-order bitmap prefix w.wcomb / w.wblk is there) selects the rank outputs: g1 rows by global pillar rank,
+// coords, w.row_of.
+int pnx_launch_span_pfn(const ReaderWs& w, int F, bool ranked, int32_t* coords, int64_t pillar_capacity, const float* folded, float* g1,
                         int64_t g1_rows, void* canvas, int canvas_dt, int canvas_nt, int64_t n_points, const PnxGeomDev& geom, hipStream_t st) {
   SpanPfnArgs A;
-  A.T = T, A.sg = sg, A.counters = counters, A.tick = tick, A.rec64 = rec64, A.pfirst = pfirst, A.pcnt = pcnt;
-  A.cell_of_pillar = cell_of_pillar, A.row_of = row_of, A.biglist = biglist;
-  A.bigcap = (int)(bigcap > 0x7fffffff ? 0x7fffffff : bigcap);
-  A.idcap = (int)(idcap > 0x7fffffff ? 0x7fffffff : idcap);
-  A.wcomb = wcomb, A.wblk = wblk, A.coords = coords, A.pillar_capacity = pillar_capacity, A.P = folded, A.cap = 0;
+  A.T.recs = w.srecs, A.T.tab = w.stab, A.T.rowframe = w.srowframe, A.T.rowbase = w.srowbase, A.T.frame_lo = w.frame_lo, A.T.frame_hi = w.frame_hi;
+  A.T.span_desc = w.span_desc, A.T.nspan = w.nspan;
+  A.sg = w.sg, A.counters = w.counters, A.tick = w.tick, A.rec64 = w.rec64, A.pfirst = w.pfirst, A.pcnt = w.pcnt;
+  A.cell_of_pillar = w.cell, A.row_of = w.row_of, A.biglist = w.biglist;
+  A.bigcap = (int)(w.bigcap > 0x7fffffff ? 0x7fffffff : w.bigcap);
+  A.idcap = (int)(w.pcap > 0x7fffffff ? 0x7fffffff : w.pcap);
+  A.wcomb = ranked ? w.wcomb : nullptr, A.wblk = w.wblk, A.coords = coords, A.pillar_capacity = pillar_capacity, A.P = folded, A.cap = 0;
   A.timers = nullptr;
 #ifdef PNX_BINS_TIMERS
   static unsigned long long* d_tim = nullptr;
@@ -921,13 +907,7 @@ int pnx_launch_span_pfn(int F, const SpanTables& T, const SpanGeom& sg, int32_t*
   Pfn3Out out;
   out.g1 = g1, out.g1_rows = g1_rows, out.canvas = canvas, out.dt = canvas_dt;
   out.row_of = nullptr, out.nt = canvas_nt;
-  int rc;
-  switch (F) {
-    case 3: rc = launch_spans<3>(A, out, geom, n_points, st); break;
-    case 4: rc = launch_spans<4>(A, out, geom, n_points, st); break;
-    case 5: rc = launch_spans<5>(A, out, geom, n_points, st); break;
-    default: pnx_set_error("the span PFN is built for 3..5 point features, got %d", F); return PNX_ERR_UNSUPPORTED;
-  }
+  const int rc = pnx_with_features<5>(F, [&](auto f) { return launch_spans<decltype(f)::value>(A, out, geom, n_points, st); });  // built for 3..5
 #ifdef PNX_BINS_TIMERS
   if (rc == PNX_OK && getenv("PNX_BINS_TIMERS_PRINT")) {
     unsigned long long h_tim[16];

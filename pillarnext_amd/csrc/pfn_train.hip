@@ -35,6 +35,7 @@
 // training step is dominated by the dense backbone (profiles/r02_train_step_c2_b4.log), what matters here is that the reader's
 // activations and their gradients never touch HBM.
 #include "pnx_common.h"
+#include "reader_ws.h"
 
 namespace {
 
@@ -433,18 +434,17 @@ int launch_train(int mode, const uint32_t* rec, const uint32_t* pfirst, const ui
 
 }  // namespace
 
-// pass: 0 gram0, 1 gram1, 2 output, 3 backward-1, 4 backward-0 (see the header of this file)
-int pnx_launch_pfn_train(int F, int pass, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, uint32_t* canon, uint32_t* big,
-                         const int32_t* counters,
-                         const float* prm, float* part, const float* G, const float* out_saved, float* out, int64_t out_rows, hipStream_t st) {
-  switch (F) {
-    case 3: return launch_train<8>(pass, rec64, pfirst, pcnt, canon, big, counters, prm, part, G, out_saved, out, out_rows, st);
-    case 4: return launch_train<9>(pass, rec64, pfirst, pcnt, canon, big, counters, prm, part, G, out_saved, out, out_rows, st);
-    case 5: return launch_train<10>(pass, rec64, pfirst, pcnt, canon, big, counters, prm, part, G, out_saved, out, out_rows, st);
-    case 6: return launch_train<11>(pass, rec64, pfirst, pcnt, canon, big, counters, prm, part, G, out_saved, out, out_rows, st);
-  }
-  pnx_set_error("num_point_features %d not in 3..6", F);
-  return PNX_ERR_UNSUPPORTED;
+// pass: 0 gram0, 1 gram1, 2 output, 3 backward-1, 4 backward-0 (see the header of this file), over the records that the binned grouping
+// left in w.rec64 / w.pfirst / w.pcnt.  Two arrays of the round-1 voxelizer (n + 8 words each, idle in training) are used under other
+// names: w.plist holds the canonical record order that pass 0 writes and every later pass walks, w.slot pass 0's list of the pillars of
+// more than 64 records.
+int pnx_launch_pfn_train(const ReaderWs& w, int F, int pass, const float* prm, float* part, const float* G, const float* out_saved, float* out,
+                         int64_t out_rows, hipStream_t st) {
+  uint32_t* canon = reinterpret_cast<uint32_t*>(w.plist);
+  uint32_t* big = reinterpret_cast<uint32_t*>(w.slot);
+  return pnx_with_features(F, [&](auto f) {
+    return launch_train<decltype(f)::value + 5>(pass, w.rec64, w.pfirst, w.pcnt, canon, big, w.counters, prm, part, G, out_saved, out, out_rows, st);
+  });
 }
 
 int pnx_pfn_train_blocks(void) { return kTrainBlocks; }

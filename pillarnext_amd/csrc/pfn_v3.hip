@@ -31,6 +31,7 @@
 #include "pnx_dppscan.h"
 #include "pnx_fill.h"
 #include "pfn_common.h"
+#include "reader_ws.h"
 
 namespace {
 
@@ -525,38 +526,29 @@ __global__ __launch_bounds__(256) void k_pfn3_tail(const uint4* __restrict__ rec
 }
 
 template <int F>
-int launch3(const uint4* rec, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* cell_of_pillar, int32_t* counters, int32_t* tick, int32_t* biglist,
-            int64_t bigcap, const float* folded, const Pfn3Out& out, int64_t n, int n_fill, const PnxGeomDev& g, const PnxFillJob& fj, hipStream_t st) {
+int launch3(const ReaderWs& w, const float* folded, const Pfn3Out& out, int64_t n, int n_fill, const PnxGeomDev& g, const PnxFillJob& fj, hipStream_t st) {
   constexpr int R = 256;
-  const char* b_env = getenv("PNX_PFN_BLOCKS");
-  const int max_blocks = b_env ? atoi(b_env) : 512;  // 256 CUs x 2 blocks x 4 waves = 2 waves per SIMD
+  const uint4* rec = reinterpret_cast<const uint4*>(w.rec64);
+  const int max_blocks = pnx_pfn_blocks();
   int64_t nb = ((n + R - 1) / R + 3) / 4;
   if (nb > max_blocks) nb = max_blocks;
   if (n <= 0) nb = 0;
-  const int bc = (int)(bigcap > 0x7fffffff ? 0x7fffffff : bigcap);
+  const int bc = (int)(w.bigcap > 0x7fffffff ? 0x7fffffff : w.bigcap);
   const int n_bigb = nb > 0 ? kBigBlocks : 0;
   if (nb + n_fill > 0) {
     const int grid = (int)(nb + n_fill + n_bigb);
     const bool pack = out.g1 == nullptr && out.canvas != nullptr && out.dt != PNX_F32;
-    const char* h_env = getenv("PNX_PFN_F16X3");  // 0: plain fp32 MFMA layer 1
-    const bool h16 = !(h_env && h_env[0] == '0');
-#define PNX_GO(DT_, PACK_)                                                                                                                        \
-  {                                                                                                                                               \
-    if (h16) k_pfn3<F, R, DT_, PACK_, true><<<grid, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bc, folded, out, n_fill, n_bigb, g, fj); \
-    else k_pfn3<F, R, DT_, PACK_, false><<<grid, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bc, folded, out, n_fill, n_bigb, g, fj);    \
-  }
-    if (out.dt == PNX_F32) {
-      PNX_GO(PNX_F32, false)
-    } else if (out.dt == PNX_BF16) {
-      if (pack) PNX_GO(PNX_BF16, true) else PNX_GO(PNX_BF16, false)
-    } else {
-      if (pack) PNX_GO(PNX_F16, true) else PNX_GO(PNX_F16, false)
-    }
-#undef PNX_GO
+    const bool h16 = pnx_pfn_f16x3();  // false: plain fp32 MFMA layer 1
+    pnx_with_dtype_pack(out.dt, pack, [&](auto d, auto p) {
+      constexpr int DT = decltype(d)::value;
+      constexpr bool PACK = decltype(p)::value;
+      if (h16) k_pfn3<F, R, DT, PACK, true><<<grid, 256, 0, st>>>(rec, w.pfirst, w.pcnt, w.cell, w.counters, w.tick, w.biglist, bc, folded, out, n_fill, n_bigb, g, fj);
+      else k_pfn3<F, R, DT, PACK, false><<<grid, 256, 0, st>>>(rec, w.pfirst, w.pcnt, w.cell, w.counters, w.tick, w.biglist, bc, folded, out, n_fill, n_bigb, g, fj);
+    });
     PNX_LAUNCH_CHECK();
   }
   if (n > 0) {
-    k_pfn3_tail<F><<<64, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, biglist, bc, folded, out);
+    k_pfn3_tail<F><<<64, 256, 0, st>>>(rec, w.pfirst, w.pcnt, w.cell, w.counters, w.biglist, bc, folded, out);
     PNX_LAUNCH_CHECK();
   }
   return PNX_OK;
@@ -564,46 +556,25 @@ int launch3(const uint4* rec, const uint32_t* pfirst, const uint32_t* pcnt, cons
 
 }  // namespace
 
-// n_fill > 0: blocks [0, n_fill) of the launch take the zero-fill tiles of `fj` (pnx_fill.h) concurrently with the PFN.
-int pnx_launch_pfn_v3(int F, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* cell_of_pillar,
-                      int32_t* counters, int32_t* tick, int32_t* biglist, int64_t bigcap, const float* folded, float* g1, int64_t g1_rows,
-                      void* canvas, int canvas_dt, int64_t n_points, int n_fill, const PnxGeomDev& geom, const PnxFillJob& fj, hipStream_t st) {
+int pnx_launch_pfn_v3(const ReaderWs& w, int F, const float* folded, float* g1, int64_t g1_rows, void* canvas, int canvas_dt, int64_t n_points,
+                      int n_fill, const PnxGeomDev& geom, const PnxFillJob& fj, hipStream_t st) {
   Pfn3Out out;
-  out.g1 = g1;
-  out.g1_rows = g1_rows;
-  out.canvas = canvas;
-  out.dt = canvas_dt;
-  const uint4* rec = reinterpret_cast<const uint4*>(rec64);
-  switch (F) {
-    case 3: return launch3<3>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bigcap, folded, out, n_points, n_fill, geom, fj, st);
-    case 4: return launch3<4>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bigcap, folded, out, n_points, n_fill, geom, fj, st);
-    case 5: return launch3<5>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bigcap, folded, out, n_points, n_fill, geom, fj, st);
-    case 6: return launch3<6>(rec, pfirst, pcnt, cell_of_pillar, counters, tick, biglist, bigcap, folded, out, n_points, n_fill, geom, fj, st);
-  }
-  pnx_set_error("num_point_features %d not in 3..6", F);
-  return PNX_ERR_UNSUPPORTED;
+  out.g1 = g1, out.g1_rows = g1_rows, out.canvas = canvas, out.dt = canvas_dt;
+  return pnx_with_features(F, [&](auto f) { return launch3<decltype(f)::value>(w, folded, out, n_points, n_fill, geom, fj, st); });
 }
 
 // k_pfn3_tail alone, for the LDS-sorted path (pfn_spans.hip): the pillars it spilled to the 64-byte record stream -- more than 32
 // points (biglist[0, bigcap), counters[3]) or a tile outside the fp16x3 range (biglist[bigcap, 2 bigcap), counters[4]).
-int pnx_launch_pfn3_tail(int F, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* cell_of_pillar, int32_t* counters,
-                         const int32_t* biglist, int64_t bigcap, const float* folded, float* g1, int64_t g1_rows, void* canvas, int canvas_dt, int blocks,
-                         hipStream_t st, const int32_t* row_of) {
+int pnx_launch_pfn3_tail(const ReaderWs& w, int F, bool ranked, const float* folded, float* g1, int64_t g1_rows, void* canvas, int canvas_dt,
+                         int blocks, hipStream_t st) {
   Pfn3Out out;
-  out.g1 = g1;
-  out.g1_rows = g1_rows;
-  out.canvas = canvas;
-  out.dt = canvas_dt;
-  out.row_of = row_of;
-  const uint4* rec = reinterpret_cast<const uint4*>(rec64);
-  const int bc = (int)(bigcap > 0x7fffffff ? 0x7fffffff : bigcap);
-  switch (F) {
-    case 3: k_pfn3_tail<3><<<blocks, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, biglist, bc, folded, out, 1); break;
-    case 4: k_pfn3_tail<4><<<blocks, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, biglist, bc, folded, out, 1); break;
-    case 5: k_pfn3_tail<5><<<blocks, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, biglist, bc, folded, out, 1); break;
-    case 6: k_pfn3_tail<6><<<blocks, 256, 0, st>>>(rec, pfirst, pcnt, cell_of_pillar, counters, biglist, bc, folded, out, 1); break;
-    default: pnx_set_error("num_point_features %d not in 3..6", F); return PNX_ERR_UNSUPPORTED;
-  }
-  PNX_LAUNCH_CHECK();
-  return PNX_OK;
+  out.g1 = g1, out.g1_rows = g1_rows, out.canvas = canvas, out.dt = canvas_dt;
+  out.row_of = ranked ? w.row_of : nullptr;
+  const uint4* rec = reinterpret_cast<const uint4*>(w.rec64);
+  const int bc = (int)(w.bigcap > 0x7fffffff ? 0x7fffffff : w.bigcap);
+  return pnx_with_features(F, [&](auto f) -> int {
+    k_pfn3_tail<decltype(f)::value><<<blocks, 256, 0, st>>>(rec, w.pfirst, w.pcnt, w.cell, w.counters, w.biglist, bc, folded, out, 1);
+    PNX_LAUNCH_CHECK();
+    return PNX_OK;
+  });
 }

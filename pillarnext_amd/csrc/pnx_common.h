@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "../../include/pnx.h"
 
 void pnx_set_error(const char* fmt, ...);
@@ -33,6 +36,28 @@ void pnx_set_error(const char* fmt, ...);
       return PNX_ERR_HIP;                                                          \
     }                                                                              \
   } while (0)
+
+// The opt-in a kernel needs before a launch may ask for more than 64 KiB of dynamic LDS: raises the limit of `Kernel` on the current
+// device to at least `bytes`.  The HIP runtime keeps the attribute per kernel and per device, so the largest size granted so far is
+// remembered the same way: one table per kernel (= per instantiation of this template), one slot per device.  Once a size is granted
+// a call costs hipGetDevice and one atomic load; the slow path is serialised, so two host threads can neither skip the attribute nor
+// lower it behind each other's back.
+constexpr int kPnxMaxDevices = 16;
+inline std::mutex g_pnx_lds_mutex;
+template <auto Kernel>
+int pnx_lds_optin(size_t bytes) {
+  static std::atomic<size_t> granted[kPnxMaxDevices];
+  int dev = 0;
+  PNX_CHECK_HIP(hipGetDevice(&dev));
+  PNX_REQUIRE(dev >= 0 && dev < kPnxMaxDevices, PNX_ERR_UNSUPPORTED, "device index %d", dev);
+  if (bytes <= granted[dev].load(std::memory_order_acquire)) return PNX_OK;
+  std::lock_guard<std::mutex> lock(g_pnx_lds_mutex);
+  if (bytes > granted[dev].load(std::memory_order_relaxed)) {
+    PNX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    granted[dev].store(bytes, std::memory_order_release);
+  }
+  return PNX_OK;
+}
 
 static inline size_t pnx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -25,7 +25,7 @@
 #include "pnx_common.h"
 #include "pnx_scan.h"
 #include "pnx_fill.h"
-#include "spans.h"
+#include "reader_ws.h"
 
 namespace {
 
@@ -551,49 +551,6 @@ inline void prof_mark(int which, hipStream_t st) {
   if (g_prof.on && g_prof.n < g_prof.cap) (void)hipEventRecord(g_prof.ev[g_prof.n * kEv + which], st);
 }
 
-struct ReaderWs {
-  int32_t* counters;  // [0]=P [1]=N'
-  int32_t* tick;      // 16 ticket words in separate lines (pfn_v3.hip), zeroed with the counters
-  uint32_t *bitmap, *wpre, *wblk;
-  uint8_t* bytemap;
-  int32_t* owner;
-  uint32_t* rec;
-  int32_t* biglist;  // pillars with more than 32 points (handled by k_pfn_big)
-  int32_t* cell;     // canvas cell of every pillar
-  int64_t bigcap;
-  size_t zero_bytes, zero_bytes2;  // counters | tick | bytemap [| count] are contiguous: one memset per call
-  int32_t *key, *rank, *slot;
-  uint32_t *count, *cpre, *cblk;
-  int32_t* plist;
-  uint32_t *kpre, *kblk;
-  float* mean;
-  float* g1;
-  int64_t nwords, pcap;
-  int nblk_w, nblk_c, nblk_k;
-  // binned path (reader_bins.h): bins of 2^sh pillars, K1 bins, points handled in `nwg` chunks of `chunk`
-  int sh, K1, chunk, nwg, nblk_m;
-  int gthreads;  // threads per workgroup of k_bin_count / k_bin_scatter
-  int64_t matlen;
-  uint32_t *histmat, *hpre, *hblk;
-  uint32_t* rec64;               // pillar-sorted decorated records, 64 B per kept point
-  uint32_t *pfirst, *pcnt;       // first sorted slot / number of points of every pillar
-  uint2* wcomb;                  // {bitmap word, popcount prefix} pairs
-  // span path (chunk_sort.hip + pfn_spans.hip, PNX_READER_IMPL=4, default)
-  SpanGeom sg;
-  uint4* srecs;                  // chunk-sorted 32-byte records
-  uint16_t* stab;                // run table
-  int32_t* srowframe;
-  uint32_t* srowbase;
-  int32_t *frame_lo, *frame_hi;
-  uint32_t* slab_tot;
-  uint2* span_desc;
-  int32_t* nspan;
-  int32_t* row_of;               // feat_max row per spill id
-  uint8_t* cbytes;               // occupancy bytes in canvas order (when the caller passes no occupancy output)
-  size_t zero_bytes_span;        // counters | tick | frame_lo | frame_hi
-  size_t bytes;
-};
-
 // PNX_READER_IMPL: 4 (default) = chunk sort + span PFN (chunk_sort.hip, pfn_spans.hip); 2 = the round-2 pipeline kept as the one
 // cross-check: binned grouping (reader_bins.h) + k_bin_sort + k_pfn3 (64-byte pillar-sorted records through HBM, pfn_v3.hip) -- the
 // records the fused training passes (pfn_train.hip) consume, and the path of 6 point features / PNX_PFN_F16X3=0.
@@ -601,6 +558,8 @@ int reader_impl() {
   const char* e = getenv("PNX_READER_IMPL");
   return e && atoi(e) == 2 ? 2 : 4;
 }
+
+}  // namespace
 
 int64_t cells_padded(const pnx_geom* g, int32_t batch) {
   const int64_t gyp = (g->gy + 31) / 32 * 32;
@@ -694,8 +653,6 @@ ReaderWs carve(void* ws, int64_t n, int32_t batch, const pnx_geom* g) {
   return w;
 }
 
-inline int64_t cells_of(const GeomDev& g) { return (int64_t)g.B * g.gx * g.gyp; }
-
 GeomDev make_geom(const pnx_geom* g, int32_t batch) {
   GeomDev d;
   d.minx = g->pc_min[0]; d.miny = g->pc_min[1]; d.minz = g->pc_min[2];
@@ -704,6 +661,10 @@ GeomDev make_geom(const pnx_geom* g, int32_t batch) {
   d.B = batch;
   return d;
 }
+
+namespace {
+
+inline int64_t cells_of(const GeomDev& g) { return (int64_t)g.B * g.gx * g.gyp; }
 
 inline int nblocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
@@ -761,11 +722,7 @@ int run_voxelize(const float* points, int64_t n, int32_t stride, const GeomDev& 
 template <int F>
 int launch_bin_sort(const GeomDev& gd, const ReaderWs& w, int32_t* coords, int64_t pillar_capacity, const PnxFillJob& fj, int fill_blocks, hipStream_t st) {
   const size_t lds = bin_sort_lds(w.sh);
-  static size_t lds_set = 0;
-  if (lds > lds_set) {  // more than the 64 KiB a launch gets by default
-    PNX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bin_sort<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lds_set = lds;
-  }
+  if (const int rc = pnx_lds_optin<&k_bin_sort<F>>(lds); rc != PNX_OK) return rc;  // more than the 64 KiB a launch gets by default
   const int bc = (int)(w.bigcap > 0x7fffffff ? 0x7fffffff : w.bigcap);
   k_bin_sort<F><<<w.K1 + (fj.quota > 0 ? fill_blocks : 0), kSortBlock, lds, st>>>(w.rec, gd, w.sh, w.nwg, w.matlen, w.hpre, w.hblk, w.counters, w.rec64,
                                                                                  w.pfirst, w.pcnt, w.cell, coords, pillar_capacity, w.biglist, bc,
@@ -796,13 +753,7 @@ int run_voxelize2(const float* points, int64_t n, int32_t stride, const GeomDev&
   k_bin_scatter<<<w.nwg + (f1.quota > 0 ? fill_blocks : 0), w.gthreads, hl, st>>>(points, stride, w.key, w.rank, n, w.chunk, w.sh, w.K1, w.nwg, w.hpre, w.hblk,
                                                                              w.rec, gd, f1);
   PNX_LAUNCH_CHECK();
-  int rc = PNX_OK;
-  switch (stride - 1) {
-    case 3: rc = launch_bin_sort<3>(gd, w, coords, pillar_capacity, f2, fill_blocks / 2, st); break;
-    case 4: rc = launch_bin_sort<4>(gd, w, coords, pillar_capacity, f2, fill_blocks / 2, st); break;
-    case 5: rc = launch_bin_sort<5>(gd, w, coords, pillar_capacity, f2, fill_blocks / 2, st); break;
-    default: rc = launch_bin_sort<6>(gd, w, coords, pillar_capacity, f2, fill_blocks / 2, st); break;
-  }
+  const int rc = pnx_with_features(stride - 1, [&](auto f) { return launch_bin_sort<decltype(f)::value>(gd, w, coords, pillar_capacity, f2, fill_blocks / 2, st); });
   if (rc != PNX_OK) return rc;
   if (unq_inv) {
     k_scan_local<SCAN_KEPT><<<w.nblk_k, kBlock, 0, st>>>(reinterpret_cast<const uint32_t*>(w.key), n, w.kpre, w.kblk);
@@ -813,45 +764,19 @@ int run_voxelize2(const float* points, int64_t n, int32_t stride, const GeomDev&
   return PNX_OK;
 }
 
-template <int DT>
-int launch_canvas(const ReaderWs& w, const float* g1, int64_t g1_rows, const GeomDev& gd, void* canvas, uint8_t* occ, int layout, hipStream_t st) {
+int launch_canvas(const ReaderWs& w, const float* g1, int64_t g1_rows, const GeomDev& gd, void* canvas, int dtype, uint8_t* occ, int layout, hipStream_t st) {
   const int tiles = ((gd.gx + 31) / 32) * (gd.gyp / 32) * gd.B;
-  if (layout == PNX_NHWC)
-    k_canvas_nhwc<DT><<<tiles, kBlock, 0, st>>>(w.bitmap, w.wpre, w.wblk, g1, g1_rows, gd, canvas, occ);
-  else
-    k_canvas_nchw<DT><<<tiles, kBlock, 0, st>>>(w.bitmap, w.wpre, w.wblk, g1, g1_rows, gd, canvas, occ);
+  pnx_with_dtype(dtype, [&](auto d) {
+    constexpr int DT = decltype(d)::value;
+    if (layout == PNX_NHWC)
+      k_canvas_nhwc<DT><<<tiles, kBlock, 0, st>>>(w.bitmap, w.wpre, w.wblk, g1, g1_rows, gd, canvas, occ);
+    else
+      k_canvas_nchw<DT><<<tiles, kBlock, 0, st>>>(w.bitmap, w.wpre, w.wblk, g1, g1_rows, gd, canvas, occ);
+  });
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
 
-}  // namespace
-
-// implemented in pfn_v3.hip: PFN over the pillar-sorted records of the binned path, optionally fused with the canvas zero-fill
-int pnx_launch_pfn_v3(int F, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* cell_of_pillar,
-                      int32_t* counters, int32_t* tick, int32_t* biglist, int64_t bigcap, const float* folded, float* g1, int64_t g1_rows,
-                      void* canvas, int canvas_dt, int64_t n_points, int n_fill, const PnxGeomDev& geom, const PnxFillJob& fj, hipStream_t st);
-
-// implemented in pfn_v3.hip: the one-wave-per-pillar kernel for what the span kernel (pfn_spans.hip) spills
-int pnx_launch_pfn3_tail(int F, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, const int32_t* cell_of_pillar, int32_t* counters,
-                         const int32_t* biglist, int64_t bigcap, const float* folded, float* g1, int64_t g1_rows, void* canvas, int canvas_dt, int blocks,
-                         hipStream_t st, const int32_t* row_of = nullptr);
-
-// implemented in pfn_train.hip
-int pnx_launch_pfn_train(int F, int pass, const uint32_t* rec64, const uint32_t* pfirst, const uint32_t* pcnt, uint32_t* canon, uint32_t* big,
-                         const int32_t* counters,
-                         const float* prm, float* part, const float* G, const float* out_saved, float* out, int64_t out_rows, hipStream_t st);
-int pnx_pfn_train_blocks(void);
-
-// implemented in chunk_sort.hip / pfn_spans.hip: the one-pass grouping front end and its consumer (spans.h)
-int pnx_launch_chunk_sort(const float* points, int64_t n, int stride, const PnxGeomDev& g, const SpanGeom& sg, uint4* recs, uint16_t* tab,
-                          int32_t* rowframe, uint32_t* rowbase, int32_t* counters, int32_t* frame_lo, int32_t* frame_hi, uint8_t* bytemap,
-                          uint32_t* slab_tot, uint2* span_desc, int32_t* nspan, hipStream_t st, hipEvent_t sorted);
-int pnx_launch_span_pfn(int F, const SpanTables& T, const SpanGeom& sg, int32_t* counters, int32_t* tick, uint32_t* rec64,
-                        uint32_t* pfirst, uint32_t* pcnt, int32_t* cell_of_pillar, int32_t* row_of, int32_t* biglist, int64_t bigcap, int64_t idcap,
-                        const uint2* wcomb, const uint32_t* wblk, int32_t* coords, int64_t pillar_capacity, const float* folded, float* g1,
-                        int64_t g1_rows, void* canvas, int canvas_dt, int canvas_nt, int64_t n_points, const PnxGeomDev& geom, hipStream_t st);
-
-namespace {
 // The zero-fill's own stream and its fork / join events: one set per host thread and device (calls of a thread are issued in order, so
 // the record / wait pairs of consecutive calls cannot interleave).
 struct FillSide {
@@ -859,10 +784,10 @@ struct FillSide {
   hipEvent_t fork = nullptr, join = nullptr;
 };
 int fill_side(FillSide** out) {
-  static thread_local FillSide sides[16];
+  static thread_local FillSide sides[kPnxMaxDevices];
   int dev = 0;
   PNX_CHECK_HIP(hipGetDevice(&dev));
-  PNX_REQUIRE(dev >= 0 && dev < 16, PNX_ERR_UNSUPPORTED, "device index %d", dev);
+  PNX_REQUIRE(dev >= 0 && dev < kPnxMaxDevices, PNX_ERR_UNSUPPORTED, "device index %d", dev);
   FillSide& f = sides[dev];
   if (f.stream == nullptr) {
     PNX_CHECK_HIP(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
@@ -870,6 +795,48 @@ int fill_side(FillSide** out) {
     PNX_CHECK_HIP(hipEventCreateWithFlags(&f.join, hipEventDisableTiming));
   }
   *out = &f;
+  return PNX_OK;
+}
+
+// What both pipelines settle before their first launch.
+struct ReaderPlan {
+  bool direct;  // NHWC canvas: the PFN stores each pillar straight into its cell, the zero-fill writes every other cell (no (P,64) fp32 intermediate)
+  float* g1;    // the PFN's (P,64) fp32 rows: feat_max itself when it can hold every possible pillar, else workspace; null when nobody reads them
+  int64_t g1_rows;
+  bool fill_nt;
+  int fill_blocks;
+};
+ReaderPlan reader_plan(const ReaderWs& w, const GeomDev& gd, void* canvas, int32_t canvas_dtype, int32_t canvas_layout, float* feat_max,
+                       int64_t pillar_capacity) {
+  ReaderPlan p;
+  p.direct = canvas != nullptr && canvas_layout == PNX_NHWC;
+  p.g1 = nullptr, p.g1_rows = 0;
+  if (feat_max != nullptr || (canvas != nullptr && !p.direct)) {
+    p.g1 = (feat_max && pillar_capacity >= w.pcap) ? feat_max : w.g1;
+    p.g1_rows = (p.g1 == feat_max) ? pillar_capacity : w.pcap;
+  }
+  p.fill_nt = pnx_fill_nt((size_t)gd.B * gd.gx * gd.gy * 64 * (canvas_dtype == PNX_F32 ? 4 : 2));
+  p.fill_blocks = pnx_fill_blocks();
+  return p;
+}
+
+// Behind the PFN of either pipeline: feat_max when the PFN wrote its rows elsewhere, and the canvas in the layouts the PFN does not write itself.
+int reader_outputs(const ReaderWs& w, const GeomDev& gd, const ReaderPlan& p, void* canvas, int32_t canvas_dtype, int32_t canvas_layout,
+                   uint8_t* occupancy, float* feat_max, int64_t pillar_capacity, hipStream_t st) {
+  prof_mark(5, st);
+  prof_mark(2, st);
+  if (feat_max && p.g1 != feat_max) {  // caller's buffer is smaller than the worst case: copy what fits (P is unknown on the host)
+    PNX_CHECK_HIP(hipMemcpyAsync(feat_max, p.g1, (size_t)(pillar_capacity < w.pcap ? pillar_capacity : w.pcap) * 64 * sizeof(float),
+                                 hipMemcpyDeviceToDevice, st));
+  }
+  if (canvas != nullptr && !p.direct) return launch_canvas(w, p.g1, p.g1_rows, gd, canvas, canvas_dtype, occupancy, canvas_layout, st);
+  return PNX_OK;
+}
+// The last step of a call: {P, N'} for the caller, the profile sample.
+int reader_done(const ReaderWs& w, int32_t* counts, hipStream_t st) {
+  if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  prof_mark(3, st);
+  if (g_prof.on && g_prof.n < g_prof.cap) g_prof.n++;
   return PNX_OK;
 }
 
@@ -883,26 +850,16 @@ int reader_forward_spans(const float* points, int64_t n, int32_t stride, const G
                          int32_t canvas_dtype, int32_t canvas_layout, uint8_t* occupancy, float* feat_max, int32_t* coords, int64_t pillar_capacity,
                          int64_t* unq_inv, int32_t* pillar_of_point, int32_t* counts, hipStream_t st) {
   const int F = stride - 1;
-  const bool direct = canvas != nullptr && canvas_layout == PNX_NHWC;
+  const ReaderPlan plan = reader_plan(w, gd, canvas, canvas_dtype, canvas_layout, feat_max, pillar_capacity);
+  const bool direct = plan.direct, fill_nt = plan.fill_nt;
   const bool ranked = feat_max != nullptr || coords != nullptr || unq_inv != nullptr || pillar_of_point != nullptr || (canvas != nullptr && !direct);
-  float* g1 = nullptr;
-  int64_t g1_rows = 0;
-  if (feat_max != nullptr || (canvas != nullptr && !direct)) {
-    g1 = (feat_max && pillar_capacity >= w.pcap) ? feat_max : w.g1;
-    g1_rows = (g1 == feat_max) ? pillar_capacity : w.pcap;
-  }
-  const size_t canvas_bytes = (size_t)gd.B * gd.gx * gd.gy * 64 * (canvas_dtype == PNX_F32 ? 4 : 2);
-  const char* nt_env = getenv("PNX_FILL_NT");
-  const bool fill_nt = nt_env ? nt_env[0] == '1' : canvas_bytes >= ((size_t)3 << 29);
   uint8_t* cbytes = direct ? (occupancy != nullptr ? occupancy : w.cbytes) : nullptr;
   const int64_t ncb = cbytes != nullptr ? (int64_t)gd.B * w.sg.cpf : 0;
   int rc;
   prof_mark(0, st);
   const int all_tiles = direct ? pnx_fill_tiles_bytes(gd) : 0;
   auto launch_fill_kernel = [&](const PnxByteFillJob& job, int blocks, hipStream_t fs) -> int {
-    if (canvas_dtype == PNX_F32) k_canvas_fill_bytes<PNX_F32><<<blocks, kBlock, 0, fs>>>(job, gd);
-    else if (canvas_dtype == PNX_BF16) k_canvas_fill_bytes<PNX_BF16><<<blocks, kBlock, 0, fs>>>(job, gd);
-    else k_canvas_fill_bytes<PNX_F16><<<blocks, kBlock, 0, fs>>>(job, gd);
+    pnx_with_dtype(canvas_dtype, [&](auto d) { k_canvas_fill_bytes<decltype(d)::value><<<blocks, kBlock, 0, fs>>>(job, gd); });
     PNX_LAUNCH_CHECK();
     return PNX_OK;
   };
@@ -923,20 +880,15 @@ int reader_forward_spans(const float* points, int64_t n, int32_t stride, const G
     k_scan_blocks<<<1, kBlock, 0, st>>>(w.wblk, w.nblk_w, w.counters + 0);
     PNX_LAUNCH_CHECK();
   }
-  const char* fb_env = getenv("PNX_FILL_BLOCKS");
-  const int n_fill = all_tiles > 0 ? (fb_env ? atoi(fb_env) : 256) : 0;  // one workgroup per CU (0: timing experiments, the canvas is wrong)
+  const int n_fill = all_tiles > 0 ? plan.fill_blocks : 0;
   const bool side = n > 0 && n_fill > 0;
   FillSide* fs = nullptr;
   if (side && (rc = fill_side(&fs)) != PNX_OK) return rc;
-  rc = pnx_launch_chunk_sort(points, n, stride, gd, w.sg, w.srecs, w.stab, w.srowframe, w.srowbase, w.counters, w.frame_lo, w.frame_hi, cbytes, w.slab_tot,
-                             w.span_desc, w.nspan, st, side ? fs->fork : nullptr);
+  rc = pnx_launch_chunk_sort(w, points, n, stride, gd, cbytes, st, side ? fs->fork : nullptr);
   if (rc != PNX_OK) return rc;
   prof_mark(6, st);
   PnxByteFillJob fj;
   fj.bytemap = cbytes, fj.canvas = canvas, fj.counter = w.tick + 16 * 32, fj.tiles = all_tiles, fj.nt = fill_nt ? 1 : 0, fj.base = 0;
-  SpanTables T;
-  T.recs = w.srecs, T.tab = w.stab, T.rowframe = w.srowframe, T.rowbase = w.srowbase, T.frame_lo = w.frame_lo, T.frame_hi = w.frame_hi;
-  T.span_desc = w.span_desc, T.nspan = w.nspan;
   prof_mark(4, st);
   prof_mark(1, st);
   if (side) {  // few instructions, all of them stores: the fill's waves issue ahead of the span kernel's (s_setprio in the kernel)
@@ -952,14 +904,9 @@ int reader_forward_spans(const float* points, int64_t n, int32_t stride, const G
   }
   // From here on the fill may be writing the caller's canvas on the side stream: EVERY return path joins it back into `st` first, so that whatever
   // the caller does with the canvas next (reuse, free after an error) is ordered behind the fill.
-  rc = pnx_launch_span_pfn(F, T, w.sg, w.counters, w.tick, w.rec64, w.pfirst, w.pcnt, w.cell, w.row_of, w.biglist, w.bigcap, w.pcap,
-                           ranked ? w.wcomb : nullptr, w.wblk, coords, pillar_capacity, pfn_folded, g1, g1_rows, direct ? canvas : nullptr, canvas_dtype,
+  rc = pnx_launch_span_pfn(w, F, ranked, coords, pillar_capacity, pfn_folded, plan.g1, plan.g1_rows, direct ? canvas : nullptr, canvas_dtype,
                            fill_nt ? 1 : 0, n, gd, st);
-  if (rc == PNX_OK && n > 0) {
-    const int tb = 128;
-    rc = pnx_launch_pfn3_tail(F, w.rec64, w.pfirst, w.pcnt, w.cell, w.counters, w.biglist, w.bigcap, pfn_folded, g1, g1_rows, direct ? canvas : nullptr,
-                              canvas_dtype, tb, st, ranked ? w.row_of : nullptr);
-  }
+  if (rc == PNX_OK && n > 0) rc = pnx_launch_pfn3_tail(w, F, ranked, pfn_folded, plan.g1, plan.g1_rows, direct ? canvas : nullptr, canvas_dtype, 128, st);
   if (side) {
     const hipError_t je = hipStreamWaitEvent(st, fs->join, 0);
     if (rc == PNX_OK && je != hipSuccess) {
@@ -968,18 +915,8 @@ int reader_forward_spans(const float* points, int64_t n, int32_t stride, const G
     }
   }
   if (rc != PNX_OK) return rc;
-  prof_mark(5, st);
-  prof_mark(2, st);
-  if (feat_max && g1 != feat_max) {  // caller's buffer is smaller than the worst case: copy what fits (P is unknown on the host)
-    PNX_CHECK_HIP(hipMemcpyAsync(feat_max, g1, (size_t)(pillar_capacity < w.pcap ? pillar_capacity : w.pcap) * 64 * sizeof(float),
-                                 hipMemcpyDeviceToDevice, st));
-  }
-  if (canvas != nullptr && !direct) {
-    if (canvas_dtype == PNX_F32) rc = launch_canvas<PNX_F32>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    else if (canvas_dtype == PNX_BF16) rc = launch_canvas<PNX_BF16>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    else rc = launch_canvas<PNX_F16>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    if (rc != PNX_OK) return rc;
-  }
+  rc = reader_outputs(w, gd, plan, canvas, canvas_dtype, canvas_layout, occupancy, feat_max, pillar_capacity, st);
+  if (rc != PNX_OK) return rc;
   if (n > 0 && (unq_inv != nullptr || pillar_of_point != nullptr)) {
     k_point_rank<<<nblocks(n), kBlock, 0, st>>>(w.key, n, w.wcomb, w.wblk, w.rank, pillar_of_point);
     if (unq_inv) {
@@ -989,10 +926,46 @@ int reader_forward_spans(const float* points, int64_t n, int32_t stride, const G
     }
     PNX_LAUNCH_CHECK();
   }
-  if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  prof_mark(3, st);
-  if (g_prof.on && g_prof.n < g_prof.cap) g_prof.n++;
-  return PNX_OK;
+  return reader_done(w, counts, st);
+}
+
+// PNX_READER_IMPL=2 (also 6 point features and PNX_PFN_F16X3=0): the binned pipeline, reader_bins.h + pfn_v3.hip.
+int reader_forward_bins(const float* points, int64_t n, int32_t stride, const GeomDev& gd, const ReaderWs& w, const float* pfn_folded, void* canvas,
+                        int32_t canvas_dtype, int32_t canvas_layout, uint8_t* occupancy, float* feat_max, int32_t* coords, int64_t pillar_capacity,
+                        int64_t* unq_inv, int32_t* pillar_of_point, int32_t* counts, hipStream_t st) {
+  PNX_REQUIRE(w.K1 <= 16384, PNX_ERR_UNSUPPORTED, "too many points for the binned grouping");
+  ReaderPlan plan = reader_plan(w, gd, canvas, canvas_dtype, canvas_layout, feat_max, pillar_capacity);
+  const bool direct = plan.direct;
+  if (plan.g1 == nullptr && !direct) plan.g1 = w.g1, plan.g1_rows = w.pcap;  // a call without canvas and feat_max: this PFN has always written its rows
+  // The zero-fill's 32x32-cell tiles are dealt to the launches that leave HBM idle (pnx_fill.h): extra blocks of k_bin_count /
+  // k_bin_scatter / k_bin_sort take `split` percent each (PNX_FILL_SPLIT="a,b,c", default 0,0,24), the PFN launch the rest.
+  PnxFillJob fjob[4];
+  {
+    int split[3];
+    pnx_reader_fill_split(split);
+    const int tiles = pnx_fill_tiles(gd);
+    int base = 0;
+    for (int k = 0; k < 4; k++) {
+      int q = k < 3 ? (int)((int64_t)tiles * split[k] / 100) : tiles - base;
+      if (!direct || n <= 0) q = k < 3 ? 0 : (direct ? tiles : 0);
+      if (q > tiles - base) q = tiles - base;
+      fjob[k].bitmap = w.bitmap, fjob[k].canvas = canvas, fjob[k].occ = occupancy, fjob[k].counter = w.tick + (16 + k) * 32;
+      fjob[k].base = base, fjob[k].quota = q, fjob[k].dt = canvas_dtype, fjob[k].nt = plan.fill_nt ? 1 : 0, fjob[k].n_main = 0;
+      base += q;
+    }
+  }
+  prof_mark(0, st);
+  int rc = run_voxelize2(points, n, stride, gd, w, coords, pillar_capacity, unq_inv, pillar_of_point, fjob, plan.fill_blocks, st);
+  if (rc != PNX_OK) return rc;
+  prof_mark(6, st);
+  prof_mark(4, st);
+  prof_mark(1, st);
+  rc = pnx_launch_pfn_v3(w, stride - 1, pfn_folded, plan.g1, plan.g1_rows, direct ? canvas : nullptr, canvas_dtype, n, direct ? plan.fill_blocks : 0, gd,
+                         fjob[3], st);
+  if (rc != PNX_OK) return rc;
+  rc = reader_outputs(w, gd, plan, canvas, canvas_dtype, canvas_layout, occupancy, feat_max, pillar_capacity, st);
+  if (rc != PNX_OK) return rc;
+  return reader_done(w, counts, st);
 }
 }  // namespace
 
@@ -1033,69 +1006,12 @@ int pnx_reader_forward(const float* points, int64_t n, int32_t stride, int32_t b
   const GeomDev gd = make_geom(g, batch);
 
   const int F = stride - 1;
-  {
-    const char* h16_env = getenv("PNX_PFN_F16X3");
-    const int64_t rows = (int64_t)w.sg.nchunks * batch;
-    if (reader_impl() == 4 && F <= 5 && !(h16_env && h16_env[0] == '0') && w.sg.nf <= 32768 && batch <= 1024 && rows < ((int64_t)1 << 30))
-      return reader_forward_spans(points, n, stride, gd, w, pfn_folded, canvas, canvas_dtype, canvas_layout, occupancy, feat_max, coords, pillar_capacity,
-                                  unq_inv, pillar_of_point, counts, st);
-  }
-  // ---- the binned pipeline (PNX_READER_IMPL=2; 6 point features; PNX_PFN_F16X3=0): reader_bins.h + pfn_v3.hip
-  PNX_REQUIRE(w.K1 <= 16384, PNX_ERR_UNSUPPORTED, "too many points for the binned grouping");
-  // Direct mode (NHWC canvas): the PFN kernel stores each pillar straight into its canvas cell and fill blocks write the zeros of every
-  // other cell -- no (P,64) fp32 intermediate, every canvas byte written exactly once.
-  const bool direct = canvas != nullptr && canvas_layout == PNX_NHWC;
-  float* g1 = (feat_max && pillar_capacity >= w.pcap) ? feat_max : w.g1;  // feat_max doubles as the PFN output buffer when it can hold every possible pillar
-  if (direct && feat_max == nullptr) g1 = nullptr;
-  const int64_t g1_rows = (g1 == feat_max) ? pillar_capacity : w.pcap;
-  const size_t canvas_bytes = (size_t)gd.B * gd.gx * gd.gy * 64 * (canvas_dtype == PNX_F32 ? 4 : 2);
-  const char* nt_env = getenv("PNX_FILL_NT");
-  const bool fill_nt = nt_env ? nt_env[0] == '1' : canvas_bytes >= ((size_t)3 << 29);  // >= 1.5 GiB: far beyond what the Infinity Cache absorbs
-  // The zero-fill's 32x32-cell tiles are dealt to the launches that leave HBM idle (pnx_fill.h): extra blocks of k_bin_count /
-  // k_bin_scatter / k_bin_sort take `split` percent each (PNX_FILL_SPLIT="a,b,c", default 0,0,24), the PFN launch the rest.
-  PnxFillJob fjob[4];
-  {
-    int split[3];
-    pnx_reader_fill_split(split);
-    const int tiles = pnx_fill_tiles(gd);
-    int base = 0;
-    for (int k = 0; k < 4; k++) {
-      int q = k < 3 ? (int)((int64_t)tiles * split[k] / 100) : tiles - base;
-      if (!direct || n <= 0) q = k < 3 ? 0 : (direct ? tiles : 0);
-      if (q > tiles - base) q = tiles - base;
-      fjob[k].bitmap = w.bitmap, fjob[k].canvas = canvas, fjob[k].occ = occupancy, fjob[k].counter = w.tick + (16 + k) * 32;
-      fjob[k].base = base, fjob[k].quota = q, fjob[k].dt = canvas_dtype, fjob[k].nt = fill_nt ? 1 : 0, fjob[k].n_main = 0;
-      base += q;
-    }
-  }
-  const char* fb_env = getenv("PNX_FILL_BLOCKS");
-  const int fill_blocks = fb_env ? atoi(fb_env) : 256;
-  prof_mark(0, st);
-  rc = run_voxelize2(points, n, stride, gd, w, coords, pillar_capacity, unq_inv, pillar_of_point, fjob, fill_blocks, st);
-  if (rc != PNX_OK) return rc;
-  prof_mark(6, st);
-  prof_mark(4, st);
-  prof_mark(1, st);
-  rc = pnx_launch_pfn_v3(F, w.rec64, w.pfirst, w.pcnt, w.cell, w.counters, w.tick, w.biglist, w.bigcap, pfn_folded, g1, g1_rows,
-                         direct ? canvas : nullptr, canvas_dtype, n, direct ? fill_blocks : 0, gd, fjob[3], st);
-  if (rc != PNX_OK) return rc;
-  prof_mark(5, st);
-  prof_mark(2, st);
-  if (feat_max && g1 != feat_max) {
-    // caller's buffer is smaller than the worst case: copy what fits (P is unknown on the host)
-    PNX_CHECK_HIP(hipMemcpyAsync(feat_max, g1, (size_t)(pillar_capacity < w.pcap ? pillar_capacity : w.pcap) * 64 * sizeof(float),
-                                 hipMemcpyDeviceToDevice, st));
-  }
-  if (canvas != nullptr && !direct) {
-    if (canvas_dtype == PNX_F32) rc = launch_canvas<PNX_F32>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    else if (canvas_dtype == PNX_BF16) rc = launch_canvas<PNX_BF16>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    else rc = launch_canvas<PNX_F16>(w, g1, g1_rows, gd, canvas, occupancy, canvas_layout, st);
-    if (rc != PNX_OK) return rc;
-  }
-  if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  prof_mark(3, st);
-  if (g_prof.on && g_prof.n < g_prof.cap) g_prof.n++;
-  return PNX_OK;
+  const int64_t rows = (int64_t)w.sg.nchunks * batch;
+  if (reader_impl() == 4 && F <= 5 && pnx_pfn_f16x3() && w.sg.nf <= 32768 && batch <= 1024 && rows < ((int64_t)1 << 30))
+    return reader_forward_spans(points, n, stride, gd, w, pfn_folded, canvas, canvas_dtype, canvas_layout, occupancy, feat_max, coords, pillar_capacity,
+                                unq_inv, pillar_of_point, counts, st);
+  return reader_forward_bins(points, n, stride, gd, w, pfn_folded, canvas, canvas_dtype, canvas_layout, occupancy, feat_max, coords, pillar_capacity,
+                             unq_inv, pillar_of_point, counts, st);
 }
 
 // ---- training-mode PFN (pfn_train.hip).  Parameter block: W1 (4096) | mu1 is1 gamma1 beta1 m1 m2 (6 x 64) | mu0 is0 gamma0 beta0
@@ -1131,9 +1047,7 @@ int pnx_pfn_forward_train(int32_t pass, const float* points, int64_t n, int32_t 
     if (rc != PNX_OK) return rc;
     if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   }
-  // w.plist (n + 8 words, otherwise the round-1 voxelizer's) holds the canonical record order that pass 0 writes and every later pass walks,
-  // w.slot (likewise) pass 0's list of the pillars of more than 64 records
-  return pnx_launch_pfn_train(stride - 1, pass, w.rec64, w.pfirst, w.pcnt, reinterpret_cast<uint32_t*>(w.plist), reinterpret_cast<uint32_t*>(w.slot), w.counters, params, partials, nullptr, nullptr, feat_max, pillar_capacity, st);
+  return pnx_launch_pfn_train(w, stride - 1, pass, params, partials, nullptr, nullptr, feat_max, pillar_capacity, st);
 }
 
 int pnx_pfn_backward(int32_t pass, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, const float* params, const float* grad_feat_max,
@@ -1143,8 +1057,7 @@ int pnx_pfn_backward(int32_t pass, int64_t n, int32_t stride, int32_t batch, con
   PNX_REQUIRE(stride >= 4 && stride <= 7, PNX_ERR_UNSUPPORTED, "row_stride %d", stride);
   PNX_REQUIRE(workspace_bytes >= pnx_reader_workspace_bytes(n, batch, g), PNX_ERR_WORKSPACE, "workspace too small");
   const ReaderWs w = carve(workspace, n, batch, g);  // the records written by pnx_pfn_forward_train(pass 0) on the same workspace
-  return pnx_launch_pfn_train(stride - 1, pass == 0 ? 3 : 4, w.rec64, w.pfirst, w.pcnt, reinterpret_cast<uint32_t*>(w.plist), reinterpret_cast<uint32_t*>(w.slot), w.counters, params, partials, grad_feat_max, feat_max, nullptr, 0,
-                              (hipStream_t)stream);
+  return pnx_launch_pfn_train(w, stride - 1, pass == 0 ? 3 : 4, params, partials, grad_feat_max, feat_max, nullptr, 0, (hipStream_t)stream);
 }
 
 void pnx_reader_fill_split(int32_t* percent3) {
@@ -1208,12 +1121,10 @@ int pnx_voxelize(const float* points, int64_t n, int32_t stride, int32_t batch, 
   if (rc != PNX_OK) return rc;
   if (features && n > 0) {
     k_pillar_mean<<<nblocks(w.pcap), kBlock, 0, st>>>(points, stride, w.plist, w.count, w.cpre, w.cblk, w.counters, w.mean);
-    switch (stride - 1) {
-      case 3: k_decorate<3><<<nblocks(n), kBlock, 0, st>>>(points, n, gd, w.rank, w.kpre, w.kblk, w.mean, features); break;
-      case 4: k_decorate<4><<<nblocks(n), kBlock, 0, st>>>(points, n, gd, w.rank, w.kpre, w.kblk, w.mean, features); break;
-      case 5: k_decorate<5><<<nblocks(n), kBlock, 0, st>>>(points, n, gd, w.rank, w.kpre, w.kblk, w.mean, features); break;
-      default: k_decorate<6><<<nblocks(n), kBlock, 0, st>>>(points, n, gd, w.rank, w.kpre, w.kblk, w.mean, features); break;
-    }
+    pnx_with_features(stride - 1, [&](auto f) {
+      k_decorate<decltype(f)::value><<<nblocks(n), kBlock, 0, st>>>(points, n, gd, w.rank, w.kpre, w.kblk, w.mean, features);
+      return PNX_OK;
+    });
     PNX_LAUNCH_CHECK();
   }
   if (counts) PNX_CHECK_HIP(hipMemcpyAsync(counts, w.counters, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -1232,9 +1143,9 @@ int pnx_scatter_canvas(const float* feat_max, const int32_t* coords, const int32
   k_zero16<<<2048, kBlock, 0, st>>>(reinterpret_cast<uint4*>(canvas), bytes / 16);
   if (pillar_capacity > 0) {
     const int nb = nblocks(pillar_capacity * 64);
-    if (canvas_dtype == PNX_F32) k_scatter_list<PNX_F32><<<nb, kBlock, 0, st>>>(feat_max, coords, num_pillars_dev, pillar_capacity, batch, gy, gx, canvas_layout, canvas);
-    else if (canvas_dtype == PNX_BF16) k_scatter_list<PNX_BF16><<<nb, kBlock, 0, st>>>(feat_max, coords, num_pillars_dev, pillar_capacity, batch, gy, gx, canvas_layout, canvas);
-    else k_scatter_list<PNX_F16><<<nb, kBlock, 0, st>>>(feat_max, coords, num_pillars_dev, pillar_capacity, batch, gy, gx, canvas_layout, canvas);
+    pnx_with_dtype(canvas_dtype, [&](auto d) {
+      k_scatter_list<decltype(d)::value><<<nb, kBlock, 0, st>>>(feat_max, coords, num_pillars_dev, pillar_capacity, batch, gy, gx, canvas_layout, canvas);
+    });
   }
   PNX_LAUNCH_CHECK();
   return PNX_OK;
