@@ -696,6 +696,67 @@ int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, in
 int pnx_sp3_dense_backward(const float* dout, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* dfeat,
                            pnx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * GT-database paste and the four global augmentations (csrc/augment.hip): det3d/datasets/base.py:72-99 of the reference, i.e.
+ * DataBaseSamplerV2.sample_all / sample_class_v2 with box_collision_test and points_in_rbbox (sample_ops.py, box_np_ops.py), then Rotation,
+ * Scaling, Translation, Flip of pipelines/augmentation.py, in that order.  Choosing the candidates (BatchSampler) and drawing the random
+ * parameters stay host code; everything that touches a box or a point runs here, on one stream, without a host sync.
+ *
+ * Layouts
+ *   boxes       (B, K, D) fp32, D = 7 [x y z dx dy dz yaw] or 9 [x y z dx dy dz vx vy yaw]; classes (B, K) int32; num_gt (B) int32 or NULL (= K).
+ *   candidates  (B, S) per frame, padded: cand_bank int32 (object id in the bank, < 0 = padding), cand_boxes (B, S, D), cand_cls (B, S) int32,
+ *               cand_group (B, S) int32 in [0, n_groups): the position of the candidate's class in the sampler's group list.
+ *   bank        bank_points (bank_rows, F) fp32 rows relative to the object's centre, bank_offsets (n_obj + 1) int64: object o owns rows
+ *               [bank_offsets[o], bank_offsets[o + 1]).  A candidate whose id is >= n_obj counts as padding.
+ *   points      (N, 1 + F) fp32 rows [batch index, x, y, z, F - 3 more columns]; rows with a batch index outside [0, B) are dropped, so the
+ *               output of pnx_merge_sweeps can be passed whole.
+ *   xform       (B, 6) fp64 per frame, or NULL (= no augmentation): cos a, sin a, a, scale (already rounded to fp32), t, flags.  flags is a
+ *               small integer stored as a double: PNX_AUG_ROTATE | PNX_AUG_SCALE | PNX_AUG_TRANSLATE | PNX_AUG_FLIP_X | PNX_AUG_FLIP_Y.
+ *
+ * pnx_paste_select: one workgroup per frame.  BEV corners in fp64 from the fp32 boxes, clockwise (-,-) (-,+) (+,+) (+,-); the directed
+ * collision test of box_np_ops.py:216-302 (strict stand-up overlap, then a properly crossing edge pair or strict containment) for every
+ * candidate against every gt box and every candidate; the greedy pass of sample_ops.py:202-235 in group order: a candidate is rejected when
+ * it collides with a gt box, with an accepted candidate of an earlier group, or with a candidate of its own group that has not been rejected
+ * yet (later, unvisited ones included).  Outputs: accept (B, S) uint8; paste_offset (B, S) int32 = first row of the object inside the frame's
+ * pasted rows, in acceptance order, -1 if rejected; boxes_out (B, K + S, D) / classes_out (B, K + S) = [gt, accepted] (zeros / -1 beyond
+ * num_out[b]); num_out (B); pasted_rows (B) = bank rows the frame's accepted objects bring.  K + S <= PNX_PASTE_MAX_BOXES, otherwise
+ * PNX_ERR_UNSUPPORTED before any launch.  cand_bank == NULL or S == 0: no candidates, the gt boxes are copied.
+ *
+ * pnx_paste_augment_points: out (capacity, 1 + F) = per frame b (frames in index order) [pasted rows of the accepted objects in acceptance
+ * order: bank row + fp32 box centre (fp32 adds), surviving scene rows in input order], every row transformed; rows [n_out, capacity) get batch
+ * index -1 and zeros.  A scene row is removed when, for an accepted box, |z - cz| <= dz/2, |lx| <= dx/2 and |ly| <= dy/2 all hold (inclusive),
+ * lx = sx cos + sy sin, ly = -sx sin + sy cos, evaluated in fp64 on the fp32 inputs (points_in_boxes_jit).  n_out (1) and frame_rows (B) int32
+ * stay on the device.  Rows that would land at or beyond `capacity` are not written; n_out still reports the full count.  cand_bank == NULL:
+ * augment only.  The scene rows are cut into chunks of pnx_paste_chunk_rows() rows, one workgroup each.
+ *
+ * pnx_augment_boxes: the box side of the four transforms, in place on (B, M, D), rows [0, num[b]) (num NULL = M).
+ *
+ * Exactness contract.  Every step rounds to fp32 before the next.  Rotation: x' = fp32(x cos a - y sin a), y' = fp32(x sin a + y cos a), products
+ * and sum separate fp64 operations (no FMA), on points, box centres and (vx, vy); yaw += fp32(a) in fp32.  Scaling: fp32 multiply of xyz and of
+ * box columns 0 .. D-2.  Translation: ONE scalar t added to x, y and z in fp64, rounded once.  Flip x: y, yaw, vy negated; flip y: x, vx
+ * negated, yaw = -yaw + fp32(pi); after each flip the yaw is wrapped once by -+fp32(2 pi) if it is > fp32(pi) or < -fp32(pi).  A NaN box element
+ * enters each stage as 0 and is NaN again after it.  Acceptance and removal decisions are those of the fp64 statement
+ * (tests/paste_augment_ref.py) except where a corner or a point lies within rounding distance of an edge or a face.  No atomics: the outputs are
+ * bit-identical from run to run. */
+#define PNX_PASTE_MAX_BOXES 512 /* gt + candidates per frame (the collision bits of one frame stay in LDS) */
+#define PNX_PASTE_MAX_BATCH 64  /* frames per call */
+#define PNX_AUG_ROTATE 1
+#define PNX_AUG_SCALE 2
+#define PNX_AUG_TRANSLATE 4
+#define PNX_AUG_FLIP_X 8
+#define PNX_AUG_FLIP_Y 16
+int32_t pnx_paste_chunk_rows(void);
+int pnx_paste_select(const float* gt_boxes, const int32_t* gt_cls, const int32_t* num_gt, int32_t batch, int32_t k, int32_t box_dim,
+                     const int32_t* cand_bank, const float* cand_boxes, const int32_t* cand_cls, const int32_t* cand_group, int32_t s, int32_t n_groups,
+                     const int64_t* bank_offsets, int32_t n_obj, uint8_t* accept, int32_t* paste_offset, float* boxes_out, int32_t* classes_out, int32_t* num_out,
+                     int32_t* pasted_rows, pnx_stream_t stream);
+size_t pnx_paste_augment_workspace_bytes(int64_t n_points, int32_t batch);
+int pnx_paste_augment_points(const float* points, int64_t n_points, int32_t point_dim, int32_t batch, const int32_t* cand_bank, const float* cand_boxes,
+                             const int32_t* paste_offset, const int32_t* pasted_rows, int32_t s, int32_t box_dim, const float* bank_points,
+                             const int64_t* bank_offsets, int32_t n_obj, int64_t bank_rows, const double* xform, float* out, int64_t capacity, int32_t* n_out, int32_t* frame_rows,
+                             void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+int pnx_augment_boxes(float* boxes, const int32_t* num, int32_t batch, int32_t m, int32_t box_dim, const double* xform, pnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

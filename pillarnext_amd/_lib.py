@@ -27,6 +27,8 @@ class PnxGroupGeom(ctypes.Structure):   # include/pnx.h: pnx_group_geom
 
 
 PNX_ASSIGN_MAX_TASKS, PNX_ASSIGN_MAX_CLASSES = 8, 32
+PNX_PASTE_MAX_BOXES, PNX_PASTE_MAX_BATCH = 512, 64
+PNX_AUG_ROTATE, PNX_AUG_SCALE, PNX_AUG_TRANSLATE, PNX_AUG_FLIP_X, PNX_AUG_FLIP_Y = 1, 2, 4, 8, 16
 
 
 class PnxAssignDesc(ctypes.Structure):   # include/pnx.h: pnx_assign_desc -- the config's fp64 values, not PnxGeom's fp32 casts
@@ -131,6 +133,12 @@ PROTOTYPES = {
     "pnx_center_loss_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pnx_assign_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "pnx_assign_labels": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, ctypes.POINTER(PnxAssignDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pnx_paste_chunk_rows": (_i32, []),
+    "pnx_paste_select": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pnx_paste_augment_workspace_bytes": (_sz, [_i64, _i32]),
+    "pnx_paste_augment_points": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                                _sz, _vp]),
+    "pnx_augment_boxes": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "pnx_boxes_overlap_bev": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "pnx_boxes_iou_bev": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "pnx_boxes_aligned_overlap_bev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),

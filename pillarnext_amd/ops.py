@@ -1036,3 +1036,107 @@ def assign_labels(gt_boxes, gt_classes, num_gt, desc, out, counts, ws):
     check(lib().pnx_assign_labels(ptr(gt_boxes), ptr(gt_classes), ptr(num_gt), B, K, ctypes.byref(desc), *arrs, ptr(counts), ptr(ws),
                                   ws.numel() * ws.element_size(), stream_ptr()), "pnx_assign_labels")
     return out
+
+
+# --------------------------------------------------------------------------------------------- GT paste and global augmentation
+def paste_chunk_rows():
+    """Scene rows per workgroup of the point pass (tests aim at the seams with it)."""
+    return int(lib().pnx_paste_chunk_rows())
+
+
+def _typed(t, name, dtype, shape):
+    _need_cuda(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise PnxError(f"{name} must be {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
+
+
+def paste_select(gt_boxes, gt_classes, num_gt, cand, bank_offsets, n_groups, out):
+    """pnx_paste_select.  gt_boxes (B, K, D) fp32 with D 7 or 9, gt_classes (B, K) int32, num_gt (B) int32 or None.  cand: None (no candidates)
+    or a dict {bank (B, S) int32, boxes (B, S, D) fp32, cls (B, S) int32, group (B, S) int32}; bank_offsets (n_obj + 1) int64.
+    out: {accept (B, S) uint8, paste_offset (B, S) int32 (both may be None without candidates), boxes (B, K + S, D) fp32, classes (B, K + S)
+    int32, num (B) int32, pasted_rows (B) int32}.  Returns out."""
+    _need_cuda(gt_boxes, "gt_boxes")
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[2] not in (7, 9):
+        raise PnxError(f"gt_boxes must be (B, K, 7 or 9) fp32, got {tuple(gt_boxes.shape)} {gt_boxes.dtype}")
+    B, K, D = (int(v) for v in gt_boxes.shape)
+    _typed(gt_classes, "gt_classes", torch.int32, (B, K))
+    if num_gt is not None:
+        _typed(num_gt, "num_gt", torch.int32, (B,))
+    S, n_obj = 0, 0
+    if cand is not None:
+        S = int(cand["bank"].shape[1])
+        _typed(cand["bank"], "cand.bank", torch.int32, (B, S))
+        _typed(cand["boxes"], "cand.boxes", torch.float32, (B, S, D))
+        _typed(cand["cls"], "cand.cls", torch.int32, (B, S))
+        _typed(cand["group"], "cand.group", torch.int32, (B, S))
+        _need_cuda(bank_offsets, "bank_offsets")
+        if bank_offsets.dtype != torch.int64 or bank_offsets.dim() != 1 or bank_offsets.numel() < 2:
+            raise PnxError("bank_offsets must be (n_obj + 1) int64 with n_obj >= 1")
+        n_obj = int(bank_offsets.numel()) - 1
+        _typed(out["accept"], "out.accept", torch.uint8, (B, S))
+        _typed(out["paste_offset"], "out.paste_offset", torch.int32, (B, S))
+    _typed(out["boxes"], "out.boxes", torch.float32, (B, K + S, D))
+    _typed(out["classes"], "out.classes", torch.int32, (B, K + S))
+    _typed(out["num"], "out.num", torch.int32, (B,))
+    _typed(out["pasted_rows"], "out.pasted_rows", torch.int32, (B,))
+    c = cand or {}
+    check(lib().pnx_paste_select(ptr(gt_boxes), ptr(gt_classes), ptr(num_gt), B, K, D, ptr(c.get("bank")), ptr(c.get("boxes")), ptr(c.get("cls")),
+                                 ptr(c.get("group")), S, int(n_groups), ptr(bank_offsets) if cand is not None else None, n_obj, ptr(out.get("accept")) if S else None,
+                                 ptr(out.get("paste_offset")) if S else None, ptr(out["boxes"]), ptr(out["classes"]), ptr(out["num"]), ptr(out["pasted_rows"]),
+                                 stream_ptr()), "pnx_paste_select")
+    return out
+
+
+def paste_augment_workspace_bytes(n_points, batch):
+    return int(lib().pnx_paste_augment_workspace_bytes(int(n_points), int(batch)))
+
+
+def paste_augment_points(points, batch, cand, paste_offset, pasted_rows, bank_points, bank_offsets, xform, out, n_out, frame_rows, ws):
+    """pnx_paste_augment_points.  points (N, 1 + F) fp32 [batch index, x, y, z, ..]; cand / paste_offset / pasted_rows as paste_select takes and
+    leaves them (cand None: augment only); bank_points (P, F) fp32, bank_offsets (n_obj + 1) int64; xform (B, 6) fp64 or None; out
+    (capacity, 1 + F) fp32, n_out (1) int32, frame_rows (B) int32; ws: uint8 buffer of paste_augment_workspace_bytes(N, B).  Returns out."""
+    _need_cuda(points, "points")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 4:
+        raise PnxError(f"points must be (N, 1 + F) fp32 with F >= 3, got {tuple(points.shape)} {points.dtype}")
+    N, F, B = int(points.shape[0]), int(points.shape[1]) - 1, int(batch)
+    S, D, n_obj, P = 0, 0, 0, 0
+    if cand is not None:
+        S, D = int(cand["boxes"].shape[1]), int(cand["boxes"].shape[2])
+        _typed(cand["bank"], "cand.bank", torch.int32, (B, S))
+        _typed(cand["boxes"], "cand.boxes", torch.float32, (B, S, D))
+        _typed(paste_offset, "paste_offset", torch.int32, (B, S))
+        _typed(pasted_rows, "pasted_rows", torch.int32, (B,))
+        _need_cuda(bank_points, "bank_points")
+        _need_cuda(bank_offsets, "bank_offsets")
+        if bank_points.dtype != torch.float32 or bank_points.dim() != 2 or int(bank_points.shape[1]) != F:
+            raise PnxError(f"bank_points must be (P, {F}) fp32 (the scene rows have {F} columns after the batch index), got {tuple(bank_points.shape)} {bank_points.dtype}")
+        if bank_offsets.dtype != torch.int64 or bank_offsets.dim() != 1 or bank_offsets.numel() < 2:
+            raise PnxError("bank_offsets must be (n_obj + 1) int64 with n_obj >= 1")
+        n_obj, P = int(bank_offsets.numel()) - 1, int(bank_points.shape[0])
+    if xform is not None:
+        _typed(xform, "xform", torch.float64, (B, 6))
+    _need_cuda(out, "out")
+    if out.dtype != torch.float32 or out.dim() != 2 or int(out.shape[1]) != F + 1:
+        raise PnxError(f"out must be (capacity, {F + 1}) fp32, got {tuple(out.shape)} {out.dtype}")
+    _typed(n_out, "n_out", torch.int32, (1,))
+    _typed(frame_rows, "frame_rows", torch.int32, (B,))
+    _need_cuda(ws, "workspace")
+    c = cand or {}
+    check(lib().pnx_paste_augment_points(ptr(points), N, F, B, ptr(c.get("bank")), ptr(c.get("boxes")), ptr(paste_offset) if S else None,
+                                         ptr(pasted_rows) if S else None, S, D, ptr(bank_points) if S else None, ptr(bank_offsets) if S else None, n_obj, P,
+                                         ptr(xform), ptr(out), int(out.shape[0]), ptr(n_out), ptr(frame_rows), ptr(ws), ws.numel() * ws.element_size(),
+                                         stream_ptr()), "pnx_paste_augment_points")
+    return out
+
+
+def augment_boxes_(boxes, num, xform):
+    """pnx_augment_boxes, in place: boxes (B, M, 7 or 9) fp32, num (B) int32 or None (= M), xform (B, 6) fp64."""
+    _need_cuda(boxes, "boxes")
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[2] not in (7, 9):
+        raise PnxError(f"boxes must be (B, M, 7 or 9) fp32, got {tuple(boxes.shape)} {boxes.dtype}")
+    B, M, D = (int(v) for v in boxes.shape)
+    if num is not None:
+        _typed(num, "num", torch.int32, (B,))
+    _typed(xform, "xform", torch.float64, (B, 6))
+    check(lib().pnx_augment_boxes(ptr(boxes), ptr(num), B, M, D, ptr(xform), stream_ptr()), "pnx_augment_boxes")
+    return boxes

@@ -210,3 +210,31 @@ def make_gt_boxes(config="C2", batch=1, seed=0, max_gt=200, n_classes=10):
         boxes[b, :n, 8] = rng.uniform(-np.pi, np.pi, n)
         classes[b, :n] = np.where(rng.random(n) < 0.02, -1, c)
     return boxes, classes, num_gt
+
+
+def make_object_bank(class_names, n_per_class=50, seed=0, point_dim=5, min_points=5, max_points=2000, box_dim=9, config="C2"):
+    """A seeded synthetic GT database for DataBaseSamplerV2(db_infos=...): {name: [info, ..]} with n_per_class objects per class.  An info holds
+    name, box3d_lidar (box_dim,) fp32 (centre inside the x/y range, the class's typical size +-15 %, class i uses GT_CLASS_SIZES[i % 10]),
+    num_points_in_gt, difficulty and `points` (r, point_dim) fp32: min_points <= r <= max_points rows (log-uniform), xyz RELATIVE to the box
+    centre and inside the box, the remaining columns in [0, 1)."""
+    cfg = CONFIGS[config]
+    lo, hi = np.asarray(cfg["pc_range"][:3], np.float64), np.asarray(cfg["pc_range"][3:], np.float64)
+    rng = np.random.default_rng(7000 + seed)
+    bank = {}
+    for ci, name in enumerate(class_names):
+        infos = []
+        for _ in range(n_per_class):
+            box = np.zeros(box_dim, np.float32)
+            box[0:2] = rng.uniform(lo[:2] * 0.9, hi[:2] * 0.9)
+            box[2] = rng.uniform(lo[2] + 1.0, min(hi[2], lo[2] + 5.0))
+            box[3:6] = GT_CLASS_SIZES[ci % 10] * rng.uniform(0.85, 1.15, 3)
+            box[-1] = rng.uniform(-np.pi, np.pi)
+            r = int(np.exp(rng.uniform(np.log(max(min_points, 5)), np.log(max(max_points, min_points, 5)))))
+            local = rng.uniform(-0.5, 0.5, (r, 3)) * box[3:6].astype(np.float64)
+            c, s = np.cos(float(box[-1])), np.sin(float(box[-1]))
+            pts = np.zeros((r, point_dim), np.float32)
+            pts[:, 0], pts[:, 1], pts[:, 2] = local[:, 0] * c - local[:, 1] * s, local[:, 0] * s + local[:, 1] * c, local[:, 2]
+            pts[:, 3:] = rng.random((r, point_dim - 3))
+            infos.append({"name": name, "box3d_lidar": box, "num_points_in_gt": r, "difficulty": 0, "points": pts})
+        bank[name] = infos
+    return bank

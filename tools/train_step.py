@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--find", action="store_true", help="let MIOpen time its solvers per conv problem (cudnn.benchmark): ~2 minutes in step 0, a step about a tenth faster")
     ap.add_argument("--gt-boxes", action="store_true", help="labels from synthetic ground-truth boxes through AssignLabel.assign (csrc/assign.hip) inside every step, "
                     "instead of the fixed random label tensors")
+    ap.add_argument("--augment", action="store_true", help="with --gt-boxes: the four global augmentations (rotation, scaling, translation, flip; the reference's "
+                    "augmentation.yaml values) on the points and the boxes inside every step, before assign (csrc/augment.hip)")
+    ap.add_argument("--gt-paste", action="store_true", help="with --gt-boxes: GT-database paste from a synthetic object bank inside every step, before the augmentations")
     ap.add_argument("--yaml", default="", help="build the detector from this YAML (configs/pillarnext_b_waymo.yaml) instead of the nuScenes PillarNeXt-B")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = bool(a.find)
@@ -90,14 +93,36 @@ def main():
         assert assigner.map_size == [(ny // 4, nx // 4)] * len(tasks)
         gt_boxes, gt_classes, num_gt = (torch.from_numpy(v).to(dev) for v in synth.make_gt_boxes(a.config, a.batch, 100 + rank, n_classes=len(assigner.class_names)))
         ex = {}
+        stage = None
+        if a.augment or a.gt_paste:
+            import numpy as np
+
+            from pillarnext_amd import augment as A
+
+            np.random.seed(100 + rank)
+            sampler = None
+            if a.gt_paste:
+                names = assigner.class_names
+                bank = synth.make_object_bank(names, 40, seed=rank, point_dim=pts.shape[1] - 1, max_points=500, config=a.config)
+                sampler = A.DataBaseSamplerV2(groups=[{n: 4} for n in names], rate=1.0, db_infos=bank, class_names=names)
+            aug = {"rotation": A.Rotation([-0.78539816, 0.78539816]), "scaling": A.Scaling([0.9, 1.1]), "translation": A.Translation(0.5),
+                   "flip": A.Flip([0.5, 0.5])} if a.augment else None
+            stage = A.PasteAugment(sampler, aug)
+            host_classes = [gt_classes[b, :int(num_gt[b])].cpu().numpy() for b in range(a.batch)]    # once, before the loop: the annotations come from the host
     else:
+        assert not (a.augment or a.gt_paste), "--augment / --gt-paste work on ground-truth boxes: add --gt-boxes"
         ex = synthetic_labels(tasks, a.batch, ny // 4, nx // 4, 500, dev, 100 + rank)
     ex.update(points=pts, batch_size=a.batch)
     for it in range(a.steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if a.gt_boxes:
-            labels = assigner.assign(gt_boxes, gt_classes, num_gt)
+            if stage is not None:    # raw points and boxes -> pasted, augmented points and boxes; no host round trip, no sync
+                step_pts, _, step_boxes, step_classes, step_num = stage(pts, gt_boxes, gt_classes, num_gt, host_classes=host_classes)
+                ex["points"] = step_pts
+                labels = assigner.assign(step_boxes, step_classes, step_num)
+            else:
+                labels = assigner.assign(gt_boxes, gt_classes, num_gt)
             ex.update({k: labels[k] for k in ("hm", "ind", "mask", "cat", "anno_box", "gt_boxes")})
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.amp):
             loss, _ = model(ex)
