@@ -1494,17 +1494,17 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restric
   sched_done(slot);
 }
 
-template <int CIN, int COUT, int NP = 1>
-int launch_s2(const void* x, const void* wfrag, const float* bias, const uint8_t* mask, void* y, int B, int H, int W, int Ho, int Wo, int relu,
-              uint8_t* row_dirty, hipStream_t st, const void* x2 = nullptr, const void* wfrag2 = nullptr, const void* x3 = nullptr, const void* wfrag3 = nullptr) {
+template <int CIN, int COUT, int NP>
+int launch_s2(PnxPieces<NP> x, PnxPieces<NP> wfrag, const float* bias, const uint8_t* mask, void* y, int B, int H, int W, int Ho, int Wo, int relu,
+              uint8_t* row_dirty, hipStream_t st) {
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   int64_t nb = (int64_t)B * ((Ho + S2_TH - 1) / S2_TH) * ((Wo + 31) / 32);
   if (nb > 512) nb = 512;  // resident workgroups: 2 per CU (LDS and registers)
   constexpr auto kern = k_conv3x3_s2<CIN, COUT, NP>;
   constexpr int lds = S2_NSTAGE * 16;
   if (const int rc = pnx_lds_optin<kern>(lds); rc != PNX_OK) return rc;
-  kern<<<(unsigned)nb, 256, lds, st>>>((const uint16_t*)x, (const uint16_t*)x2, (const uint4*)wfrag, (const uint4*)wfrag2, bias, mask, (uint16_t*)y, B, H, W, Ho,
-                                       Wo, relu, row_dirty, slot, (const uint16_t*)x3, (const uint4*)wfrag3);
+  kern<<<(unsigned)nb, 256, lds, st>>>((const uint16_t*)x.hi, (const uint16_t*)x.slot2(), (const uint4*)wfrag.hi, (const uint4*)wfrag.slot2(), bias, mask,
+                                       (uint16_t*)y, B, H, W, Ho, Wo, relu, row_dirty, slot, (const uint16_t*)x.slot3(), (const uint4*)wfrag.slot3());
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
@@ -1871,9 +1871,9 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
     if (cin == 64 && cout == 448) return launch_lds<448>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
   }
   if (stride == 2 && residual == nullptr && getenv("PNX_CONV_DIRECT") == nullptr) {
-    if (cin == 64 && cout == 128) return launch_s2<64, 128>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
-    if (cin == 128 && cout == 256) return launch_s2<128, 256>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
-    if (cin == 256 && cout == 256) return launch_s2<256, 256>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
+    if (cin == 64 && cout == 128) return launch_s2<64, 128, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
+    if (cin == 128 && cout == 256) return launch_s2<128, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
+    if (cin == 256 && cout == 256) return launch_s2<256, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
   }
 #define PNX_CONV_CASE(CI, CO)                                                                                          \
   if (cin == CI && cout == CO) {                                                                                       \
@@ -1892,50 +1892,64 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
 }  // extern "C"
 namespace {
 #include "conv_dgrad_s2.h"
+
+// The stride-2 data gradient and the fp32 forward come with 1, 2 or 3 bf16 pieces per operand (PnxPieces<NP>).  Each family has ONE implementation that holds
+// its checks and its shape ladder; the entry points below fill the piece structs and pass their own NP and their name (for the messages).
+template <int NP>
+int dgrad_s2_impl(const char* name, PnxPieces<NP> g, PnxPieces<NP> wfrag_t, const uint8_t* mask_in, void* dx, int32_t batch, int32_t h, int32_t w, int32_t cin,
+                  int32_t cout, pnx_stream_t stream) {
+  PNX_REQUIRE(g.complete() && wfrag_t.complete() && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "%s: bad arguments", name);
+  PNX_REQUIRE(((g.bits() | wfrag_t.bits() | (uintptr_t)dx) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  hipStream_t st = (hipStream_t)stream;
+  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, NP>(g, wfrag_t, mask_in, dx, batch, h, w, st);
+  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, NP>(g, wfrag_t, mask_in, dx, batch, h, w, st);
+  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, NP>(g, wfrag_t, mask_in, dx, batch, h, w, st);
+  pnx_set_error("%s: no kernel for %d -> %d channels", name, cin, cout);
+  return PNX_ERR_UNSUPPORTED;
 }
+
+template <int NP>
+int conv3x3_f32_impl(const char* name, PnxPieces<NP> x, PnxPieces<NP> wfrag, const float* bias, const uint8_t* mask, float* y, int32_t batch, int32_t h, int32_t w,
+                     int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream) {
+  PNX_REQUIRE(x.complete() && wfrag.complete() && y, PNX_ERR_INVALID, "null pointer");
+  PNX_REQUIRE(batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "bad shape");
+  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
+  PNX_REQUIRE(((x.bits() | wfrag.bits() | (uintptr_t)y | (uintptr_t)bias) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  hipStream_t st = (hipStream_t)stream;
+  if (stride == 1) {
+    if (cin == 64 && cout == 64) return launch_pc_f32<64, 64, NP>(x, wfrag, bias, mask, y, batch, h, w, st);
+    if (cin == 128 && cout == 128) return launch_pc_f32<128, 128, NP>(x, wfrag, bias, mask, y, batch, h, w, st);
+    if (cin == 256 && cout == 256) return launch_pc_f32<256, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, st);
+  } else {
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    if (cin == 64 && cout == 128) return launch_s2<64, 128, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
+    if (cin == 128 && cout == 256) return launch_s2<128, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
+    if (cin == 256 && cout == 256) return launch_s2<256, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
+  }
+  pnx_set_error("%s: no kernel for %d -> %d channels, stride %d", name, cin, cout, stride);
+  return PNX_ERR_UNSUPPORTED;
+}
+
+}  // namespace
 extern "C" {
 
 // Data gradient of a stride-2 SparseConv2d layer (conv_dgrad_s2.h): g (batch, ho, wo, cout) NHWC bf16, wfrag_t = pnx_conv3x3_pack_weights(transposed = 1) of the
 // layer's (cout, cin, 3, 3) weights, mask_in = active sites of the layer's INPUT (batch, h, w); dx (batch, h, w, cin) bf16, zeros at inactive sites, every site written.
 int pnx_conv3x3_dgrad_s2_bf16(const void* g, const void* wfrag_t, const uint8_t* mask_in, void* dx, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout,
                               pnx_stream_t stream) {
-  PNX_REQUIRE(g && wfrag_t && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_dgrad_s2_bf16: bad arguments");
-  PNX_REQUIRE((((uintptr_t)g | (uintptr_t)wfrag_t | (uintptr_t)dx) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
-  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
-  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 1>(g, nullptr, wfrag_t, nullptr, mask_in, dx, batch, h, w, st);
-  pnx_set_error("pnx_conv3x3_dgrad_s2_bf16: no kernel for %d -> %d channels", cin, cout);
-  return PNX_ERR_UNSUPPORTED;
+  return dgrad_s2_impl<1>("pnx_conv3x3_dgrad_s2_bf16", {g}, {wfrag_t}, mask_in, dx, batch, h, w, cin, cout, stream);
 }
 
 // The same from the bf16 halves of an fp32 gradient and of the fp32 weights (pnx_split_f32), fp32 out: the stride-2 companion of pnx_conv3x3_x3.
 int pnx_conv3x3_dgrad_s2_x3(const void* g_hi, const void* g_lo, const void* wfrag_t_hi, const void* wfrag_t_lo, const uint8_t* mask_in, float* dx, int32_t batch,
                             int32_t h, int32_t w, int32_t cin, int32_t cout, pnx_stream_t stream) {
-  PNX_REQUIRE(g_hi && g_lo && wfrag_t_hi && wfrag_t_lo && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_dgrad_s2_x3: bad arguments");
-  PNX_REQUIRE((((uintptr_t)g_hi | (uintptr_t)g_lo | (uintptr_t)wfrag_t_hi | (uintptr_t)wfrag_t_lo | (uintptr_t)dx) & 15) == 0, PNX_ERR_INVALID,
-              "16-byte alignment required");
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
-  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
-  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 2>(g_hi, g_lo, wfrag_t_hi, wfrag_t_lo, mask_in, dx, batch, h, w, st);
-  pnx_set_error("pnx_conv3x3_dgrad_s2_x3: no kernel for %d -> %d channels", cin, cout);
-  return PNX_ERR_UNSUPPORTED;
+  return dgrad_s2_impl<2>("pnx_conv3x3_dgrad_s2_x3", {g_hi, g_lo}, {wfrag_t_hi, wfrag_t_lo}, mask_in, dx, batch, h, w, cin, cout, stream);
 }
 
 // Three bf16 pieces of g and of the weights (pnx_split3_f32), six products, fp32 out: the stride-2 companion of pnx_conv3x3_x6.
 int pnx_conv3x3_dgrad_s2_x6(const void* g_hi, const void* g_mid, const void* g_lo, const void* wfrag_t_hi, const void* wfrag_t_mid, const void* wfrag_t_lo,
                             const uint8_t* mask_in, float* dx, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, pnx_stream_t stream) {
-  PNX_REQUIRE(g_hi && g_mid && g_lo && wfrag_t_hi && wfrag_t_mid && wfrag_t_lo && mask_in && dx && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID,
-              "pnx_conv3x3_dgrad_s2_x6: bad arguments");
-  PNX_REQUIRE((((uintptr_t)g_hi | (uintptr_t)g_mid | (uintptr_t)g_lo | (uintptr_t)wfrag_t_hi | (uintptr_t)wfrag_t_mid | (uintptr_t)wfrag_t_lo | (uintptr_t)dx) & 15) == 0,
-              PNX_ERR_INVALID, "16-byte alignment required");
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 64 && cout == 128) return launch_dgrad_s2<128, 64, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
-  if (cin == 128 && cout == 256) return launch_dgrad_s2<256, 128, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
-  if (cin == 256 && cout == 256) return launch_dgrad_s2<256, 256, 3>(g_hi, g_mid, wfrag_t_hi, wfrag_t_mid, mask_in, dx, batch, h, w, st, g_lo, wfrag_t_lo);
-  pnx_set_error("pnx_conv3x3_dgrad_s2_x6: no kernel for %d -> %d channels", cin, cout);
-  return PNX_ERR_UNSUPPORTED;
+  return dgrad_s2_impl<3>("pnx_conv3x3_dgrad_s2_x6", {g_hi, g_mid, g_lo}, {wfrag_t_hi, wfrag_t_mid, wfrag_t_lo}, mask_in, dx, batch, h, w, cin, cout, stream);
 }
 
 // fp32 convolution out of three bf16 products: x = x_hi + x_lo and W = W_hi + W_lo (bf16 halves of fp32 values, pnx_split_f32; both weight halves in
@@ -1944,24 +1958,7 @@ int pnx_conv3x3_dgrad_s2_x6(const void* g_hi, const void* g_mid, const void* g_l
 // accumulators; no activation: this is the convolution of the fp32 training graph (forward, and the stride-1 data gradient with transposed weights).
 int pnx_conv3x3_x3(const void* x_hi, const void* x_lo, const void* wfrag_hi, const void* wfrag_lo, const float* bias, const uint8_t* mask, float* y,
                    int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream) {
-  PNX_REQUIRE(x_hi && x_lo && wfrag_hi && wfrag_lo && y, PNX_ERR_INVALID, "null pointer");
-  PNX_REQUIRE(batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "bad shape");
-  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
-  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_lo | (uintptr_t)y | (uintptr_t)wfrag_hi | (uintptr_t)wfrag_lo | (uintptr_t)bias) & 15) == 0, PNX_ERR_INVALID,
-              "16-byte alignment required");
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {
-    if (cin == 64 && cout == 64) return launch_pc_x3<64, 64>(x_hi, x_lo, wfrag_hi, wfrag_lo, bias, mask, y, batch, h, w, st);
-    if (cin == 128 && cout == 128) return launch_pc_x3<128, 128>(x_hi, x_lo, wfrag_hi, wfrag_lo, bias, mask, y, batch, h, w, st);
-    if (cin == 256 && cout == 256) return launch_pc_x3<256, 256>(x_hi, x_lo, wfrag_hi, wfrag_lo, bias, mask, y, batch, h, w, st);
-  } else {
-    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    if (cin == 64 && cout == 128) return launch_s2<64, 128, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
-    if (cin == 128 && cout == 256) return launch_s2<128, 256, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
-    if (cin == 256 && cout == 256) return launch_s2<256, 256, 2>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_lo, wfrag_lo);
-  }
-  pnx_set_error("pnx_conv3x3_x3: no kernel for %d -> %d channels, stride %d", cin, cout, stride);
-  return PNX_ERR_UNSUPPORTED;
+  return conv3x3_f32_impl<2>("pnx_conv3x3_x3", {x_hi, x_lo}, {wfrag_hi, wfrag_lo}, bias, mask, y, batch, h, w, cin, cout, stride, stream);
 }
 
 // fp32 convolution out of six bf16 products: x = x_hi + x_mid + x_lo and W = W_hi + W_mid + W_lo (pnx_split3_f32, exact for |x| >= 2^-100), y = the
@@ -1969,27 +1966,7 @@ int pnx_conv3x3_x3(const void* x_hi, const void* x_lo, const void* wfrag_hi, con
 // rounding) accumulated in fp32 inside ONE launch, low-order products first and hi.hi last.  Otherwise exactly pnx_conv3x3_x3: shapes, mask, bias, output.
 int pnx_conv3x3_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* wfrag_hi, const void* wfrag_mid, const void* wfrag_lo, const float* bias,
                    const uint8_t* mask, float* y, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, pnx_stream_t stream) {
-  PNX_REQUIRE(x_hi && x_mid && x_lo && wfrag_hi && wfrag_mid && wfrag_lo && y, PNX_ERR_INVALID, "null pointer");
-  PNX_REQUIRE(batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "bad shape");
-  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
-  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_mid | (uintptr_t)x_lo | (uintptr_t)y | (uintptr_t)wfrag_hi | (uintptr_t)wfrag_mid | (uintptr_t)wfrag_lo |
-                (uintptr_t)bias) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {
-    if (cin == 64 && cout == 64) return launch_pc_x6<64, 64>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
-    if (cin == 128 && cout == 128) return launch_pc_x6<128, 128>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
-    if (cin == 256 && cout == 256) return launch_pc_x6<256, 256>(x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, batch, h, w, st);
-  } else {
-    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    if (cin == 64 && cout == 128)
-      return launch_s2<64, 128, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
-    if (cin == 128 && cout == 256)
-      return launch_s2<128, 256, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
-    if (cin == 256 && cout == 256)
-      return launch_s2<256, 256, 3>(x_hi, wfrag_hi, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st, x_mid, wfrag_mid, x_lo, wfrag_lo);
-  }
-  pnx_set_error("pnx_conv3x3_x6: no kernel for %d -> %d channels, stride %d", cin, cout, stride);
-  return PNX_ERR_UNSUPPORTED;
+  return conv3x3_f32_impl<3>("pnx_conv3x3_x6", {x_hi, x_mid, x_lo}, {wfrag_hi, wfrag_mid, wfrag_lo}, bias, mask, y, batch, h, w, cin, cout, stride, stream);
 }
 #endif
 

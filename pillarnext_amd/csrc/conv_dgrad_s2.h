@@ -179,8 +179,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_s2(const uint16_t* __restrict_
 }
 
 template <int CO, int CI, int NP>
-int launch_dgrad_s2(const void* g, const void* g2, const void* wt, const void* wt2, const uint8_t* mask_in, void* dx, int B, int H, int W, hipStream_t st,
-                    const void* g3 = nullptr, const void* wt3 = nullptr) {
+int launch_dgrad_s2(PnxPieces<NP> g, PnxPieces<NP> wt, const uint8_t* mask_in, void* dx, int B, int H, int W, hipStream_t st) {
   using G = Dg2Geo<CO, CI, NP>;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   int64_t nb = (int64_t)B * ((Ho + G::TG - 1) / G::TG) * ((Wo + 31) / 32);
@@ -189,8 +188,8 @@ int launch_dgrad_s2(const void* g, const void* g2, const void* wt, const void* w
   constexpr auto kern = k_dgrad_s2<CO, CI, NP>;
   if (const int rc = pnx_lds_optin<kern>(G::LDS_BYTES); rc != PNX_OK) return rc;
   const int slot = next_sched_slot();
-  kern<<<(unsigned)nb, 512, G::LDS_BYTES, st>>>((const uint16_t*)g, (const uint16_t*)g2, (const uint4*)wt, (const uint4*)wt2, mask_in, dx, B, H, W, Ho, Wo, slot,
-                                                (const uint16_t*)g3, (const uint4*)wt3);
+  kern<<<(unsigned)nb, 512, G::LDS_BYTES, st>>>((const uint16_t*)g.hi, (const uint16_t*)g.slot2(), (const uint4*)wt.hi, (const uint4*)wt.slot2(), mask_in, dx, B, H, W,
+                                                Ho, Wo, slot, (const uint16_t*)g.slot3(), (const uint4*)wt.slot3());
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

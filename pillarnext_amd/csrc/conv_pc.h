@@ -408,32 +408,18 @@ int launch_pc(const void* x, const void* wfrag, const float* bias, const void* r
   return PNX_OK;
 }
 
-// fp32 product of bf16 pairs (pnx_conv3x3_x3): x = x_hi + x_lo, W = W_hi + W_lo, y = x_hi W_hi + x_hi W_lo + x_lo W_hi in one launch, fp32 out.
-template <int CIN, int COUT>
-int launch_pc_x3(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias, const uint8_t* mask, float* y, int B, int H, int W,
-                 hipStream_t st) {
+// The fp32 forms (pnx_conv3x3_x3 / _x6): NP bf16 pieces per operand, fp32 out, one launch.  NP = 2: x = x_hi + x_lo, W = W_hi + W_lo,
+// y = x_hi W_hi + x_hi W_lo + x_lo W_hi.  NP = 3: x = x_hi + x_mid + x_lo, W likewise, y = hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi (x.W),
+// hi.hi last; the launch shape of NP = 2 with 1.5 x its fills and 2 x its MFMAs.
+template <int CIN, int COUT, int NP>
+int launch_pc_f32(PnxPieces<NP> x, PnxPieces<NP> w, const float* bias, const uint8_t* mask, float* y, int B, int H, int W, hipStream_t st) {
   constexpr int TH = CIN == 64 ? 16 : 8;
   int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
   if (nb > 256) nb = 256;
   const int slot = mask != nullptr ? next_sched_slot() : -1;
-  k_conv3x3_pc<CIN, COUT, false, 2><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x_hi, (const uint16_t*)x_lo, (const uint4*)w_hi, (const uint4*)w_lo,
-                                                                  bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr);
-  PNX_LAUNCH_CHECK();
-  return PNX_OK;
-}
-
-// Three pieces per operand (pnx_conv3x3_x6): x = x_hi + x_mid + x_lo, W likewise, y = hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi (x.W) in one
-// launch, hi.hi last, fp32 out.  Same launch shape as launch_pc_x3; 1.5 x its fills, 2 x its MFMAs.
-template <int CIN, int COUT>
-int launch_pc_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* w_hi, const void* w_mid, const void* w_lo, const float* bias,
-                 const uint8_t* mask, float* y, int B, int H, int W, hipStream_t st) {
-  constexpr int TH = CIN == 64 ? 16 : 8;
-  int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
-  if (nb > 256) nb = 256;
-  const int slot = mask != nullptr ? next_sched_slot() : -1;
-  k_conv3x3_pc<CIN, COUT, false, 3><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x_hi, (const uint16_t*)x_mid, (const uint4*)w_hi, (const uint4*)w_mid,
-                                                                  bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr,
-                                                                  (const uint16_t*)x_lo, (const uint4*)w_lo);
+  k_conv3x3_pc<CIN, COUT, false, NP><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x.hi, (const uint16_t*)x.slot2(), (const uint4*)w.hi, (const uint4*)w.slot2(),
+                                                                   bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr,
+                                                                   (const uint16_t*)x.slot3(), (const uint4*)w.slot3());
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

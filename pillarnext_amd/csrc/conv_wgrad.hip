@@ -320,9 +320,8 @@ extern "C" size_t pnx_conv3x3_wgrad_workspace_bytes(int32_t cin, int32_t cout) {
   return (size_t)(cin >> 6) * (cout >> 6) * groups_per_pair(cin, cout) * 9 * 4096 * sizeof(float) + 256;
 }
 
-template <int S, int NP = 1>
-int launch_wgrad(const void* x, const void* dy, const uint8_t* mask, float* dw, int batch, int h, int w, int cin, int cout, void* workspace, hipStream_t st,
-                 const void* x_lo = nullptr, const void* dy_lo = nullptr, const void* x_mid = nullptr, const void* dy_mid = nullptr) {
+template <int S, int NP>
+int launch_wgrad(PnxPieces<NP> x, PnxPieces<NP> dy, const uint8_t* mask, float* dw, int batch, int h, int w, int cin, int cout, void* workspace, hipStream_t st) {
   using Geo = WgGeo<S>;
   const int ho = (h - 1) / S + 1, wo = (w - 1) / S + 1;
   const int G = groups_per_pair(cin, cout), n_pairs = (cin >> 6) * (cout >> 6);
@@ -330,26 +329,33 @@ int launch_wgrad(const void* x, const void* dy, const uint8_t* mask, float* dw, 
   PNX_REQUIRE(n_tiles < 0x7fffffff && (n_tiles + G - 1) / G <= WG_LIST_MAX, PNX_ERR_UNSUPPORTED, "%lld tiles over %d workgroups: more than %d per workgroup",
               (long long)n_tiles, G, WG_LIST_MAX);
   if (const int rc = pnx_lds_optin<&k_wgrad64<S, NP>>(Geo::LDS); rc != PNX_OK) return rc;
-  k_wgrad64<S, NP><<<dim3((unsigned)G, (unsigned)n_pairs), 256, Geo::LDS, st>>>((const uint16_t*)x, (const uint16_t*)dy, mask, (float*)workspace, batch, h, w, ho,
-                                                                                 wo, cin, cout, G, (const uint16_t*)x_lo, (const uint16_t*)dy_lo,
-                                                                                 (const uint16_t*)x_mid, (const uint16_t*)dy_mid);
+  k_wgrad64<S, NP><<<dim3((unsigned)G, (unsigned)n_pairs), 256, Geo::LDS, st>>>((const uint16_t*)x.hi, (const uint16_t*)dy.hi, mask, (float*)workspace, batch, h, w,
+                                                                                 ho, wo, cin, cout, G, (const uint16_t*)x.lo, (const uint16_t*)dy.lo,
+                                                                                 (const uint16_t*)x.mid, (const uint16_t*)dy.mid);
   PNX_LAUNCH_CHECK();
   k_wgrad_reduce<<<(unsigned)((n_pairs * 9 * 4096 + 31) / 32), 256, 0, st>>>((const float*)workspace, dw, cin, cout, G);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
 
-extern "C" int pnx_conv3x3_wgrad_bf16(const void* x, const void* dy, const uint8_t* mask, float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin,
-                                      int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
-  PNX_REQUIRE(x && dy && mask && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_wgrad_bf16: bad arguments");
+// The weight gradient of every piece count: the checks and the stride ladder once; the entry points pass their own NP and name (for the messages).
+template <int NP>
+static int wgrad_impl(const char* name, PnxPieces<NP> x, PnxPieces<NP> dy, const uint8_t* mask, float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin,
+                      int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
+  PNX_REQUIRE(x.complete() && dy.complete() && mask && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "%s: bad arguments", name);
   PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
   PNX_REQUIRE(cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0 && cin <= 512 && cout <= 512, PNX_ERR_UNSUPPORTED,
               "weight gradient for %d -> %d channels (multiples of 64 up to 512)", cin, cout);
-  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  PNX_REQUIRE(((x.bits() | dy.bits() | (uintptr_t)workspace) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
   PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) return launch_wgrad<1>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);
-  return launch_wgrad<2>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);
+  if (stride == 1) return launch_wgrad<1, NP>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);
+  return launch_wgrad<2, NP>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);
+}
+
+extern "C" int pnx_conv3x3_wgrad_bf16(const void* x, const void* dy, const uint8_t* mask, float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin,
+                                      int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
+  return wgrad_impl<1>("pnx_conv3x3_wgrad_bf16", {x}, {dy}, mask, dw, batch, h, w, cin, cout, stride, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pnx_conv3x3_pack_weights(const void* w, int32_t dtype, int32_t cout, int32_t cin, int32_t transposed, void* wfrag, pnx_stream_t stream) {
@@ -369,16 +375,7 @@ extern "C" int pnx_conv3x3_pack_weights(const void* w, int32_t dtype, int32_t co
 extern "C" int pnx_conv3x3_wgrad_x3(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, const uint8_t* mask, float* dw, int32_t batch,
                                     int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, void* workspace, size_t workspace_bytes,
                                     pnx_stream_t stream) {
-  PNX_REQUIRE(x_hi && x_lo && dy_hi && dy_lo && mask && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_wgrad_x3: bad arguments");
-  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
-  PNX_REQUIRE(cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0 && cin <= 512 && cout <= 512, PNX_ERR_UNSUPPORTED,
-              "weight gradient for %d -> %d channels (multiples of 64 up to 512)", cin, cout);
-  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_lo | (uintptr_t)dy_hi | (uintptr_t)dy_lo | (uintptr_t)workspace) & 15) == 0, PNX_ERR_INVALID,
-              "16-byte alignment required");
-  PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) return launch_wgrad<1, 2>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
-  return launch_wgrad<2, 2>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo);
+  return wgrad_impl<2>("pnx_conv3x3_wgrad_x3", {x_hi, x_lo}, {dy_hi, dy_lo}, mask, dw, batch, h, w, cin, cout, stride, workspace, workspace_bytes, stream);
 }
 
 // fp32 weight gradient from three bf16 pieces of x and of the upstream gradient (pnx_split3_f32): the six products of piece orders 0..2 in ONE pass over the
@@ -386,15 +383,6 @@ extern "C" int pnx_conv3x3_wgrad_x3(const void* x_hi, const void* x_lo, const vo
 extern "C" int pnx_conv3x3_wgrad_x6(const void* x_hi, const void* x_mid, const void* x_lo, const void* dy_hi, const void* dy_mid, const void* dy_lo,
                                     const uint8_t* mask, float* dw, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride,
                                     void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
-  PNX_REQUIRE(x_hi && x_mid && x_lo && dy_hi && dy_mid && dy_lo && mask && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID,
-              "pnx_conv3x3_wgrad_x6: bad arguments");
-  PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
-  PNX_REQUIRE(cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0 && cin <= 512 && cout <= 512, PNX_ERR_UNSUPPORTED,
-              "weight gradient for %d -> %d channels (multiples of 64 up to 512)", cin, cout);
-  PNX_REQUIRE((((uintptr_t)x_hi | (uintptr_t)x_mid | (uintptr_t)x_lo | (uintptr_t)dy_hi | (uintptr_t)dy_mid | (uintptr_t)dy_lo | (uintptr_t)workspace) & 15) == 0,
-              PNX_ERR_INVALID, "16-byte alignment required");
-  PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) return launch_wgrad<1, 3>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo, x_mid, dy_mid);
-  return launch_wgrad<2, 3>(x_hi, dy_hi, mask, dw, batch, h, w, cin, cout, workspace, st, x_lo, dy_lo, x_mid, dy_mid);
+  return wgrad_impl<3>("pnx_conv3x3_wgrad_x6", {x_hi, x_mid, x_lo}, {dy_hi, dy_mid, dy_lo}, mask, dw, batch, h, w, cin, cout, stride, workspace, workspace_bytes,
+                       stream);
 }

@@ -59,6 +59,24 @@ int pnx_lds_optin(size_t bytes) {
   return PNX_OK;
 }
 
+// The bf16 pieces of one operand of the training convolutions, most significant first (host side only).  NP = 1: the bf16 operand itself;
+// 2: (hi, lo) of pnx_split_f32; 3: (hi, mid, lo) of pnx_split3_f32.  A constructor with another number of pointers than NP does not compile.
+// The piece-to-slot mapping of the kernels is stated HERE and nowhere else.  k_conv3x3_pc, k_conv3x3_s2 and k_dgrad_s2 take their pieces
+// positionally: the first slot (x, wfrag, g, wt) is hi, the second (x2, wfrag2, g2, wt2) is slot2() = lo for NP 2 but MID for NP 3, and the
+// trailing third (x3, wfrag3, g3, wt3) is slot3() = lo for NP 3, null otherwise.  k_wgrad64 takes them by name (x_lo, dy_lo, x_mid, dy_mid).
+template <int NP>
+struct PnxPieces {
+  static_assert(NP >= 1 && NP <= 3, "1, 2 or 3 pieces");
+  const void *hi, *mid = nullptr, *lo = nullptr;
+  PnxPieces(const void* h) : hi(h) { static_assert(NP == 1, "one pointer: NP = 1"); }
+  PnxPieces(const void* h, const void* l) : hi(h), lo(l) { static_assert(NP == 2, "(hi, lo): NP = 2"); }
+  PnxPieces(const void* h, const void* m, const void* l) : hi(h), mid(m), lo(l) { static_assert(NP == 3, "(hi, mid, lo): NP = 3"); }
+  const void* slot2() const { return NP == 2 ? lo : mid; }
+  const void* slot3() const { return NP == 3 ? lo : nullptr; }
+  bool complete() const { return hi && (NP < 2 || lo) && (NP < 3 || mid); }
+  uintptr_t bits() const { return (uintptr_t)hi | (uintptr_t)mid | (uintptr_t)lo; }  // for alignment checks
+};
+
 static inline size_t pnx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Bump allocator over the caller's workspace.

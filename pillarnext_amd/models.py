@@ -287,7 +287,7 @@ def _zero_bias(c, device):
 
 def _hip_dgrad_s2(weight):
     """(cin, cout) of the stride-2 data-gradient kernels; PNX_TRAIN_HIP_DGRAD_S2=0: MIOpen / CK."""
-    return (weight.shape[1], weight.shape[0]) in {(64, 128), (128, 256), (256, 256)} and os.environ.get("PNX_TRAIN_HIP_DGRAD_S2", "1") != "0"
+    return (weight.shape[1], weight.shape[0]) in ops.CONV3X3_X3_SHAPES[2] and os.environ.get("PNX_TRAIN_HIP_DGRAD_S2", "1") != "0"
 
 
 class _MaskedConv3x3Fn(torch.autograd.Function):
@@ -351,10 +351,8 @@ class _MaskedConv3x3Fn(torch.autograd.Function):
 
 
 def _split_pack(weight, transposed=False, pieces=2):
-    """fp32 (Cout,Cin,3,3) -> the packed bf16 pieces pnx_conv3x3_x3 ((W_hi, W_lo), pieces=2) or pnx_conv3x3_x6 ((W_hi, W_mid, W_lo), pieces=3) takes."""
-    w = weight.detach().contiguous()
-    parts = ops.split_f32(w) if pieces == 2 else ops.split3_f32(w)
-    return tuple(ops.conv3x3_pack_weights(p, transposed=transposed) for p in parts)
+    """fp32 (Cout,Cin,3,3) -> its `pieces` packed bf16 pieces, (W_hi, W_lo) or (W_hi, W_mid, W_lo): what ops.conv3x3_f32 and ops.conv3x3_dgrad_s2 take."""
+    return tuple(ops.conv3x3_pack_weights(p, transposed=transposed) for p in ops.split_f32(weight.detach().contiguous(), pieces=pieces))
 
 
 def train_f32_pieces():
@@ -367,9 +365,8 @@ def train_f32_pieces():
 
 
 def split_f32_pieces(x, mask=None, pieces=None):
-    """x split into the bf16 pieces the fp32 node uses (train_f32_pieces() unless given): ops.split_f32 (2) or ops.split3_f32 (3)."""
-    n = train_f32_pieces() if pieces is None else pieces
-    return ops.split_f32(x, mask) if n == 2 else ops.split3_f32(x, mask)
+    """x split into the bf16 pieces the fp32 node uses (train_f32_pieces() unless given): ops.split_f32 into 2 or 3."""
+    return ops.split_f32(x, mask, train_f32_pieces() if pieces is None else pieces)
 
 
 _ONES_MASK = {}
@@ -408,65 +405,31 @@ class _MaskedConv3x3F32Fn(torch.autograd.Function):
             raise ops.PnxError(f"_MaskedConv3x3F32Fn: {len(pieces)} pieces of x given, PNX_TRAIN_F32_PIECES={n}")
         ctx.pieces = n
         b = None if bias is None else bias.detach().contiguous()
-        if n == 3:
-            y = ops.conv3x3_x6(pieces, _split_pack(weight, pieces=3), weight.shape[0], stride, mask_out, bias=b)
-            ctx.save_for_backward(*pieces, weight, mask_in, mask_out)
-            ctx.stride = stride
-            return y
-        xh, xl = pieces
-        wh, wl = _split_pack(weight)
-        y = ops.conv3x3_x3(xh, xl, wh, wl, weight.shape[0], stride, mask_out, bias=b)
-        ctx.save_for_backward(xh, xl, weight, mask_in, mask_out)
+        y = ops.conv3x3_f32(pieces, _split_pack(weight, pieces=n), weight.shape[0], stride, mask_out, bias=b)
+        ctx.save_for_backward(*pieces, weight, mask_in, mask_out)
         ctx.stride = stride
         return y
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.pieces == 3:
-            return _MaskedConv3x3F32Fn._backward6(ctx, g)
-        xh, xl, weight, mask_in, mask_out = ctx.saved_tensors
+        n = ctx.pieces
+        *xp, weight, mask_in, mask_out = ctx.saved_tensors   # read once: a checkpointed region (ASPPNeck) lets its saved tensors be unpacked one time only
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         g = g.contiguous(memory_format=torch.channels_last)
         s = ctx.stride
         dx = dw = db = None
         if need_w or need_x:
-            gh, gl = ops.split_f32(g, mask_out)   # the upstream gradient is zero outside mask_out (the BatchNorm node's backward writes zeros there)
+            gp = ops.split_f32(g, mask_out, n)   # the upstream gradient is zero outside mask_out (the BatchNorm node's backward writes zeros there)
         if need_x:
             if s == 1:
-                wth, wtl = _split_pack(weight, transposed=True)
-                dx = ops.conv3x3_x3(gh, gl, wth, wtl, weight.shape[1], 1, mask_in)
+                dx = ops.conv3x3_f32(gp, _split_pack(weight, transposed=True, pieces=n), weight.shape[1], 1, mask_in)
             elif mask_in is not None and _hip_dgrad_s2(weight):
-                wth, wtl = _split_pack(weight, transposed=True)
-                dx = ops.conv3x3_dgrad_s2(gh, wth, weight.shape[1], xh.shape[2:], mask_in, g_lo=gl, wfrag_t_lo=wtl)
-            else:
-                dx = torch.nn.grad.conv2d_input(xh.shape, weight, g, stride=s, padding=1)
+                dx = ops.conv3x3_dgrad_s2(gp, _split_pack(weight, transposed=True, pieces=n), weight.shape[1], xp[0].shape[2:], mask_in)
+            else:   # a stride-2 layer outside the kernels' shapes: MIOpen
+                dx = torch.nn.grad.conv2d_input(xp[0].shape, weight, g, stride=s, padding=1)
         if need_w:
             m = mask_out if mask_out is not None else _ones_mask(g.shape[0], g.shape[2], g.shape[3], g.device)
-            dw = ops.conv3x3_wgrad_x3(xh, xl, gh, gl, m, stride=s)
-        if need_b:
-            db = g.sum(dim=(0, 2, 3))
-        return dx, dw, db, None, None, None, None
-
-    @staticmethod
-    def _backward6(ctx, g):
-        """backward of the three-piece form: the same kernels' six-product twins (the stride-2 data gradient outside their shapes on MIOpen, as above)"""
-        xh, xm, xl, weight, mask_in, mask_out = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        g = g.contiguous(memory_format=torch.channels_last)
-        s = ctx.stride
-        dx = dw = db = None
-        if need_w or need_x:
-            gp = ops.split3_f32(g, mask_out)   # zero outside mask_out, as above
-        if need_x:
-            if s == 1:
-                dx = ops.conv3x3_x6(gp, _split_pack(weight, transposed=True, pieces=3), weight.shape[1], 1, mask_in)
-            elif mask_in is not None and _hip_dgrad_s2(weight):
-                dx = ops.conv3x3_dgrad_s2_x6(gp, _split_pack(weight, transposed=True, pieces=3), weight.shape[1], xh.shape[2:], mask_in)
-            else:
-                dx = torch.nn.grad.conv2d_input(xh.shape, weight, g, stride=s, padding=1)
-        if need_w:
-            m = mask_out if mask_out is not None else _ones_mask(g.shape[0], g.shape[2], g.shape[3], g.device)
-            dw = ops.conv3x3_wgrad_x6((xh, xm, xl), gp, m, stride=s)
+            dw = ops.conv3x3_wgrad(xp, gp, m, stride=s)
         if need_b:
             db = g.sum(dim=(0, 2, 3))
         return dx, dw, db, None, None, None, None
@@ -518,23 +481,23 @@ def smallk_conv(conv, x):
     return conv(x)
 
 
-_X3_DENSE = {(64, 64), (128, 128), (256, 256)}   # stride-1 shapes of pnx_conv3x3_x3
+def _dense3x3_ok(x, weight, stride, padding, dilation, groups, training):
+    """What x3_ok and bf16_dense_ok share: a training-mode CUDA 3x3 / stride 1 / pad 1 convolution of a shape the masked stride-1 kernels serve."""
+    return (training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)
+            and (weight.shape[1], weight.shape[0]) in ops.CONV3X3_X3_SHAPES[1] and x.shape[1] == weight.shape[1]
+            and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1) and groups == 1)
 
 
 def x3_ok(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1, training=True):
     """Does a DENSE 3x3 convolution of the fp32 training graph (neck / head: det3d/models/utils/conv.py, centerhead.py:24-41) run on the three-product node?"""
-    return (training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32
-            and not torch.is_autocast_enabled() and tuple(weight.shape[2:]) == (3, 3) and (weight.shape[1], weight.shape[0]) in _X3_DENSE
-            and x.shape[1] == weight.shape[1] and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1) and groups == 1
-            and os.environ.get("PNX_TRAIN_F32_HIP", "1") != "0")
+    return (_dense3x3_ok(x, weight, stride, padding, dilation, groups, training) and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and os.environ.get("PNX_TRAIN_F32_HIP", "1") != "0")
 
 
 def bf16_dense_ok(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1, training=True):
     """x3_ok's twin under bf16 autocast: the same dense layers on the bf16 masked kernels with every site active (_MaskedConv3x3Fn)."""
-    return (training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+    return (_dense3x3_ok(x, weight, stride, padding, dilation, groups, training) and x.dtype in (torch.float32, torch.bfloat16)
             and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            and tuple(weight.shape[2:]) == (3, 3) and (weight.shape[1], weight.shape[0]) in _X3_DENSE
-            and x.shape[1] == weight.shape[1] and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1) and groups == 1
             and os.environ.get("PNX_TRAIN_HIPCONV", "1") != "0" and os.environ.get("PNX_TRAIN_DENSE_HIP", "1") != "0")
 
 
@@ -549,23 +512,18 @@ def x3_conv(conv, x, pieces=None):
     return conv(x)
 
 
-# (Cin, Cout, stride) served by the LDS-staged kernels of csrc/conv3x3.hip (every 3x3 layer of the PillarNeXt-B backbone)
-_HIP_TRAIN_CONVS = {(64, 64, 1), (128, 128, 1), (256, 256, 1), (64, 128, 2), (128, 256, 2), (256, 256, 2)}
-
-
 def masked_conv(conv, x, mask_out, mask_in):
-    """conv(x) of a backbone block; in training the 3x3 layers run on the product's masked kernels: _MaskedConv3x3Fn under bf16 autocast
-    (PNX_TRAIN_HIPCONV=0 keeps every layer on MIOpen), _MaskedConv3x3F32Fn in the fp32 graph (PNX_TRAIN_F32_HIP=0: MIOpen)."""
+    """conv(x) of a backbone block; in training the 3x3 layers of ops.CONV3X3_X3_SHAPES (every 3x3 layer of the PillarNeXt-B backbone) run on the
+    product's masked kernels: _MaskedConv3x3Fn under bf16 autocast (PNX_TRAIN_HIPCONV=0 keeps every layer on MIOpen), _MaskedConv3x3F32Fn in the fp32
+    graph (PNX_TRAIN_F32_HIP=0: MIOpen)."""
     if (conv.training and torch.is_grad_enabled() and x.is_cuda and conv.kernel_size == (3, 3) and conv.bias is None
-            and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            and os.environ.get("PNX_TRAIN_HIPCONV", "1") != "0"
-            and (conv.in_channels, conv.out_channels, conv.stride[0]) in _HIP_TRAIN_CONVS):
-        return _MaskedConv3x3Fn.apply(x, conv.weight, _mask_u8(mask_out), _mask_u8(mask_in), conv.stride[0])
-    if (conv.training and torch.is_grad_enabled() and x.is_cuda and conv.kernel_size == (3, 3) and conv.bias is None
-            and not torch.is_autocast_enabled() and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
-            and os.environ.get("PNX_TRAIN_F32_HIP", "1") != "0"
-            and (conv.in_channels, conv.out_channels, conv.stride[0]) in _HIP_TRAIN_CONVS):
-        return _MaskedConv3x3F32Fn.apply(x, conv.weight, None, _mask_u8(mask_out), _mask_u8(mask_in), conv.stride[0], None)
+            and (conv.in_channels, conv.out_channels) in ops.CONV3X3_X3_SHAPES.get(conv.stride[0], ())):
+        s = conv.stride[0]
+        if torch.is_autocast_enabled():
+            if torch.get_autocast_dtype("cuda") == torch.bfloat16 and os.environ.get("PNX_TRAIN_HIPCONV", "1") != "0":
+                return _MaskedConv3x3Fn.apply(x, conv.weight, _mask_u8(mask_out), _mask_u8(mask_in), s)
+        elif x.dtype == torch.float32 and conv.weight.dtype == torch.float32 and os.environ.get("PNX_TRAIN_F32_HIP", "1") != "0":
+            return _MaskedConv3x3F32Fn.apply(x, conv.weight, None, _mask_u8(mask_out), _mask_u8(mask_in), s, None)
     return conv(x)
 
 

@@ -518,32 +518,44 @@ def sephead_lazy(tasks, class_task, batch, local, seg_len, pre_max):
 _WGRAD_WS = {}
 
 
-def conv3x3_wgrad(x, dy, mask, stride=1):
-    """Weight gradient (Cout, Cin, 3, 3) fp32 of the masked 3x3 convolution (pad 1, stride 1 or 2): sum over the sites of `mask` (B,Ho,Wo uint8,
-    the OUTPUT's active set) of dy[p] (x) x[stride * p + tap]; x, dy channels_last bf16 (csrc/conv_wgrad.hip).  Deterministic."""
-    for tns, what in ((x, "x"), (dy, "dy")):
-        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)):
-            raise PnxError(f"conv3x3_wgrad: {what} must be a channels_last bf16 CUDA tensor")
-    B, ci, H, W = x.shape
-    co = dy.shape[1]
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if stride not in (1, 2) or tuple(dy.shape) != (B, co, Ho, Wo) or tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8:
-        raise PnxError("conv3x3_wgrad: stride 1 or 2, dy (B,Cout,Ho,Wo) and a uint8 (B,Ho,Wo) mask of the output sites")
-    nbytes = int(lib().pnx_conv3x3_wgrad_workspace_bytes(ci, co))
-    if nbytes == 0:
-        raise PnxError(f"conv3x3_wgrad: no kernel for {ci} -> {co} channels")
-    key = (nbytes, x.device, torch.cuda.current_stream().cuda_stream)   # the partials of a call live until its reduction ran: one buffer per stream
+def _wgrad_workspace(nbytes, device):
+    """The weight-gradient kernels' partial sums live until their reduction ran: one uint8 buffer per (size, device, stream), kept."""
+    key = (nbytes, device, torch.cuda.current_stream().cuda_stream)
     ws = _WGRAD_WS.get(key)
     if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)
-    check(lib().pnx_conv3x3_wgrad_bf16(ptr(x), ptr(dy), ptr(mask), ptr(dw), B, H, W, ci, co, stride, ptr(ws), ws.numel(), stream_ptr()), "pnx_conv3x3_wgrad_bf16")
-    return dw
+        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
 
 
-def split_f32(x, mask=None):
-    """fp32 tensor -> (hi, lo) bf16 tensors of the same shape and memory layout: hi = RNE(x), lo = RNE(x - hi) (pnx_split_f32).
+# The training convolutions run on 1, 2 or 3 bf16 pieces per operand: one bf16 tensor (bf16 autocast), or the (hi, lo) / (hi, mid, lo) pieces of an fp32
+# tensor (split_f32), most significant first.  The number of pieces picks the entry point; pieces give fp32 results.
+_PIECES_TAG = {1: "bf16", 2: "x3", 3: "x6"}   # suffix of the entry points by pieces per operand (x3 / x6: the number of bf16 products)
+
+
+def _pieces(t):
+    return (t,) if isinstance(t, torch.Tensor) else tuple(t)
+
+
+def _bf16_maps(tensors, what):
+    """Validator: channels_last bf16 CUDA pieces of one shape."""
+    for tns in tensors:
+        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)
+                and tns.shape == tensors[0].shape):
+            raise PnxError(f"{what} needs channels_last bf16 CUDA pieces of one shape")
+
+
+def _bf16_packs(wfrags, n, what):
+    """Validator: n packed bf16 weight pieces (conv3x3_pack_weights) of one size."""
+    if len(wfrags) != n or any(w.dtype != torch.bfloat16 or w.numel() != wfrags[0].numel() for w in wfrags):
+        raise PnxError(f"{what}: the weights must be {n} packed bf16 piece(s) of one size, one per piece of the other operand")
+
+
+def split_f32(x, mask=None, pieces=2):
+    """fp32 tensor -> `pieces` bf16 tensors of the same shape and memory layout, most significant first.  2: (hi, lo), hi = RNE(x), lo = RNE(x - hi)
+    (pnx_split_f32).  3: (hi, mid, lo), mid = RNE(x - hi), lo = RNE(x - hi - mid) (pnx_split3_f32; hi + mid + lo == x exactly for finite |x| >= 2^-100).
     mask: uint8 (B,H,W) for a channels_last (B,C,H,W) x that is zero where mask is 0 -- those sites are not read."""
+    if pieces not in (2, 3):
+        raise PnxError(f"split_f32: 2 or 3 pieces, got {pieces!r}")
     if not (x.is_cuda and x.dtype == torch.float32 and x.numel() % 8 == 0):
         raise PnxError("split_f32 needs an fp32 CUDA tensor with a multiple of 8 elements")
     if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))):
@@ -554,163 +566,81 @@ def split_f32(x, mask=None):
                 and tuple(mask.shape) == (x.shape[0], x.shape[2], x.shape[3]) and x.shape[1] % 8 == 0):
             raise PnxError("split_f32: mask needs a channels_last (B,C,H,W) tensor with C % 8 == 0 and a contiguous uint8 (B,H,W) mask")
         c = x.shape[1]
-    hi, lo = torch.empty_like(x, dtype=torch.bfloat16), torch.empty_like(x, dtype=torch.bfloat16)
-    check(lib().pnx_split_f32(ptr(x), ptr(hi), ptr(lo), x.numel(), ptr(mask), c, stream_ptr()), "pnx_split_f32")
-    return hi, lo
+    out = tuple(torch.empty_like(x, dtype=torch.bfloat16) for _ in range(pieces))
+    name = "pnx_split_f32" if pieces == 2 else "pnx_split3_f32"
+    check(getattr(lib(), name)(ptr(x), *map(ptr, out), x.numel(), ptr(mask), c, stream_ptr()), name)
+    return out
 
 
-def split3_f32(x, mask=None):
-    """fp32 tensor -> (hi, mid, lo) bf16 tensors of the same shape and memory layout: hi = RNE(x), mid = RNE(x - hi), lo = RNE(x - hi - mid)
-    (pnx_split3_f32; hi + mid + lo == x exactly for finite |x| >= 2^-100).  mask: as split_f32."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.numel() % 8 == 0):
-        raise PnxError("split3_f32 needs an fp32 CUDA tensor with a multiple of 8 elements")
-    if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))):
-        raise PnxError("split3_f32 needs a dense tensor (contiguous or channels_last)")
-    c = 0
-    if mask is not None:
-        if not (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and mask.dtype == torch.uint8 and mask.is_contiguous()
-                and tuple(mask.shape) == (x.shape[0], x.shape[2], x.shape[3]) and x.shape[1] % 8 == 0):
-            raise PnxError("split3_f32: mask needs a channels_last (B,C,H,W) tensor with C % 8 == 0 and a contiguous uint8 (B,H,W) mask")
-        c = x.shape[1]
-    hi, mid, lo = (torch.empty_like(x, dtype=torch.bfloat16) for _ in range(3))
-    check(lib().pnx_split3_f32(ptr(x), ptr(hi), ptr(mid), ptr(lo), x.numel(), ptr(mask), c, stream_ptr()), "pnx_split3_f32")
-    return hi, mid, lo
+# stride -> (Cin, Cout) of the masked training kernels, the ONE statement of what they serve: pnx_conv3x3_x3 / _x6 (the fp32 graph) and, for bf16
+# autocast, the LDS-staged kernels of pnx_conv3x3_bf16; stride 2 is also the set of pnx_conv3x3_dgrad_s2_*.  models.py derives its tables from this.
+CONV3X3_X3_SHAPES = {1: {(64, 64), (128, 128), (256, 256)}, 2: {(64, 128), (128, 256), (256, 256)}}
 
 
-CONV3X3_X3_SHAPES = {1: {(64, 64), (128, 128), (256, 256)}, 2: {(64, 128), (128, 256), (256, 256)}}   # stride -> (Cin, Cout) of pnx_conv3x3_x3
-
-
-def conv3x3_x3(x_hi, x_lo, wfrag_hi, wfrag_lo, cout, stride, mask, bias=None):
-    """fp32 (B,Cout,Ho,Wo) channels_last = masked 3x3 convolution of x_hi + x_lo with W_hi + W_lo (three bf16 products accumulated in fp32 in one
-    launch, pnx_conv3x3_x3) [+ bias, fp32 (Cout,)]; mask uint8 (B,Ho,Wo) of the OUTPUT sites or None (dense); zeros at inactive sites."""
+def conv3x3_f32(x_pieces, wfrag_pieces, cout, stride, mask, bias=None):
+    """fp32 (B,Cout,Ho,Wo) channels_last = masked 3x3 convolution of an fp32 x with an fp32 W, each given as 2 or 3 bf16 pieces (split_f32; the weight
+    pieces packed by conv3x3_pack_weights), accumulated in fp32 in one launch [+ bias, fp32 (Cout,)].  2 pieces: the three products hi.hi + hi.lo + lo.hi
+    (pnx_conv3x3_x3); 3 pieces: the six products of piece orders 0..2 (pnx_conv3x3_x6).  mask uint8 (B,Ho,Wo) of the OUTPUT sites or None (dense);
+    zeros at inactive sites."""
+    xs, ws = tuple(x_pieces), tuple(wfrag_pieces)
+    if len(xs) not in (2, 3):
+        raise PnxError(f"conv3x3_f32: 2 or 3 pieces per operand, got {len(xs)}")
     if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()):
-        raise PnxError("conv3x3_x3: bias must be a contiguous fp32 CUDA vector of Cout values")
-    for tns in (x_hi, x_lo):
-        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)):
-            raise PnxError("conv3x3_x3 needs channels_last bf16 CUDA halves")
-    if x_hi.shape != x_lo.shape or wfrag_hi.dtype != torch.bfloat16 or wfrag_lo.dtype != torch.bfloat16:
-        raise PnxError("conv3x3_x3: the two halves must have one shape, the weights must be packed bf16")
-    B, ci, H, W = x_hi.shape
+        raise PnxError("conv3x3_f32: bias must be a contiguous fp32 CUDA vector of Cout values")
+    _bf16_maps(xs, "conv3x3_f32")
+    _bf16_packs(ws, len(xs), "conv3x3_f32")
+    B, ci, H, W = xs[0].shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     if mask is not None and (tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8):
-        raise PnxError("conv3x3_x3: mask must be uint8 (B,Ho,Wo)")
-    y = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x_hi.device, memory_format=torch.channels_last)
-    check(lib().pnx_conv3x3_x3(ptr(x_hi), ptr(x_lo), ptr(wfrag_hi), ptr(wfrag_lo), ptr(bias), ptr(mask), ptr(y), B, H, W, ci, cout, stride, stream_ptr()), "pnx_conv3x3_x3")
+        raise PnxError("conv3x3_f32: mask must be uint8 (B,Ho,Wo)")
+    y = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=xs[0].device, memory_format=torch.channels_last)
+    name = "pnx_conv3x3_" + _PIECES_TAG[len(xs)]
+    check(getattr(lib(), name)(*map(ptr, xs), *map(ptr, ws), ptr(bias), ptr(mask), ptr(y), B, H, W, ci, cout, stride, stream_ptr()), name)
     return y
 
 
-def conv3x3_wgrad_x3(x_hi, x_lo, dy_hi, dy_lo, mask, stride=1):
-    """conv3x3_wgrad of x_hi + x_lo with dy_hi + dy_lo (three products, one pass: pnx_conv3x3_wgrad_x3): (Cout, Cin, 3, 3) fp32."""
-    for tns in (x_hi, x_lo, dy_hi, dy_lo):
-        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)):
-            raise PnxError("conv3x3_wgrad_x3 needs channels_last bf16 CUDA halves")
-    B, ci, H, W = x_hi.shape
-    co = dy_hi.shape[1]
+def conv3x3_wgrad(x, dy, mask, stride=1):
+    """Weight gradient (Cout, Cin, 3, 3) fp32 of the masked 3x3 convolution (pad 1, stride 1 or 2): sum over the sites of `mask` (B,Ho,Wo uint8,
+    the OUTPUT's active set) of dy[p] (x) x[stride * p + tap] (csrc/conv_wgrad.hip).  Deterministic.  x, dy: one channels_last bf16 tensor each
+    (pnx_conv3x3_wgrad_bf16), or equal-length tuples of the 2 or 3 bf16 pieces of fp32 tensors (split_f32): three or six products in one pass
+    (pnx_conv3x3_wgrad_x3 / _x6)."""
+    xs, gs = _pieces(x), _pieces(dy)
+    if len(xs) not in _PIECES_TAG or len(gs) != len(xs):
+        raise PnxError("conv3x3_wgrad: x and dy must be one bf16 tensor each or tuples of 2 or 3 pieces of equal length")
+    _bf16_maps(xs, "conv3x3_wgrad: x")
+    _bf16_maps(gs, "conv3x3_wgrad: dy")
+    B, ci, H, W = xs[0].shape
+    co = gs[0].shape[1]
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if (stride not in (1, 2) or x_lo.shape != x_hi.shape or dy_lo.shape != dy_hi.shape or tuple(dy_hi.shape) != (B, co, Ho, Wo)
-            or tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8):
-        raise PnxError("conv3x3_wgrad_x3: stride 1 or 2, halves of one shape, dy (B,Cout,Ho,Wo) and a uint8 (B,Ho,Wo) mask of the output sites")
+    if stride not in (1, 2) or tuple(gs[0].shape) != (B, co, Ho, Wo) or tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8:
+        raise PnxError("conv3x3_wgrad: stride 1 or 2, dy (B,Cout,Ho,Wo) and a uint8 (B,Ho,Wo) mask of the output sites")
     nbytes = int(lib().pnx_conv3x3_wgrad_workspace_bytes(ci, co))
     if nbytes == 0:
-        raise PnxError(f"conv3x3_wgrad_x3: no kernel for {ci} -> {co} channels")
-    key = (nbytes, x_hi.device, torch.cuda.current_stream().cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=x_hi.device)
-    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x_hi.device)
-    check(lib().pnx_conv3x3_wgrad_x3(ptr(x_hi), ptr(x_lo), ptr(dy_hi), ptr(dy_lo), ptr(mask), ptr(dw), B, H, W, ci, co, stride, ptr(ws), ws.numel(), stream_ptr()),
-          "pnx_conv3x3_wgrad_x3")
+        raise PnxError(f"conv3x3_wgrad: no kernel for {ci} -> {co} channels")
+    ws = _wgrad_workspace(nbytes, xs[0].device)
+    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=xs[0].device)
+    name = "pnx_conv3x3_wgrad_" + _PIECES_TAG[len(xs)]
+    check(getattr(lib(), name)(*map(ptr, xs), *map(ptr, gs), ptr(mask), ptr(dw), B, H, W, ci, co, stride, ptr(ws), ws.numel(), stream_ptr()), name)
     return dw
 
 
-def _bf16_maps(tensors, what):
-    for tns in tensors:
-        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last)
-                and tns.shape == tensors[0].shape):
-            raise PnxError(f"{what} needs channels_last bf16 CUDA pieces of one shape")
-
-
-def conv3x3_x6(x_pieces, wfrag_pieces, cout, stride, mask, bias=None):
-    """fp32 (B,Cout,Ho,Wo) channels_last = masked 3x3 convolution of x_hi + x_mid + x_lo (split3_f32) with W_hi + W_mid + W_lo (each packed by
-    conv3x3_pack_weights): the six products of piece orders 0..2 accumulated in fp32 in one launch (pnx_conv3x3_x6) [+ bias, fp32 (Cout,)];
-    mask uint8 (B,Ho,Wo) of the OUTPUT sites or None (dense); zeros at inactive sites."""
-    x_hi, x_mid, x_lo = x_pieces
-    w_hi, w_mid, w_lo = wfrag_pieces
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()):
-        raise PnxError("conv3x3_x6: bias must be a contiguous fp32 CUDA vector of Cout values")
-    _bf16_maps((x_hi, x_mid, x_lo), "conv3x3_x6")
-    if any(w.dtype != torch.bfloat16 or w.numel() != w_hi.numel() for w in (w_hi, w_mid, w_lo)):
-        raise PnxError("conv3x3_x6: the weights must be three packed bf16 pieces of one size")
-    B, ci, H, W = x_hi.shape
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if mask is not None and (tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8):
-        raise PnxError("conv3x3_x6: mask must be uint8 (B,Ho,Wo)")
-    y = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x_hi.device, memory_format=torch.channels_last)
-    check(lib().pnx_conv3x3_x6(ptr(x_hi), ptr(x_mid), ptr(x_lo), ptr(w_hi), ptr(w_mid), ptr(w_lo), ptr(bias), ptr(mask), ptr(y), B, H, W, ci, cout, stride,
-                               stream_ptr()), "pnx_conv3x3_x6")
-    return y
-
-
-def conv3x3_wgrad_x6(x_pieces, dy_pieces, mask, stride=1):
-    """conv3x3_wgrad of x_hi + x_mid + x_lo with dy_hi + dy_mid + dy_lo (split3_f32 pieces; six products, one pass: pnx_conv3x3_wgrad_x6):
-    (Cout, Cin, 3, 3) fp32, deterministic."""
-    x_hi, x_mid, x_lo = x_pieces
-    dy_hi, dy_mid, dy_lo = dy_pieces
-    _bf16_maps((x_hi, x_mid, x_lo), "conv3x3_wgrad_x6")
-    _bf16_maps((dy_hi, dy_mid, dy_lo), "conv3x3_wgrad_x6")
-    B, ci, H, W = x_hi.shape
-    co = dy_hi.shape[1]
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if stride not in (1, 2) or tuple(dy_hi.shape) != (B, co, Ho, Wo) or tuple(mask.shape) != (B, Ho, Wo) or mask.dtype != torch.uint8:
-        raise PnxError("conv3x3_wgrad_x6: stride 1 or 2, dy (B,Cout,Ho,Wo) and a uint8 (B,Ho,Wo) mask of the output sites")
-    nbytes = int(lib().pnx_conv3x3_wgrad_workspace_bytes(ci, co))
-    if nbytes == 0:
-        raise PnxError(f"conv3x3_wgrad_x6: no kernel for {ci} -> {co} channels")
-    key = (nbytes, x_hi.device, torch.cuda.current_stream().cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=x_hi.device)
-    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x_hi.device)
-    check(lib().pnx_conv3x3_wgrad_x6(ptr(x_hi), ptr(x_mid), ptr(x_lo), ptr(dy_hi), ptr(dy_mid), ptr(dy_lo), ptr(mask), ptr(dw), B, H, W, ci, co, stride,
-                                     ptr(ws), ws.numel(), stream_ptr()), "pnx_conv3x3_wgrad_x6")
-    return dw
-
-
-def conv3x3_dgrad_s2_x6(g_pieces, wfrag_t_pieces, cin, in_hw, mask_in):
-    """conv3x3_dgrad_s2 from three bf16 pieces of the upstream gradient (split3_f32) and of the TRANSPOSED weight pack (pnx_conv3x3_dgrad_s2_x6):
-    six products, fp32 dx (B,cin,H,W) channels_last, zeros at inactive input sites."""
-    g_hi, g_mid, g_lo = g_pieces
-    w_hi, w_mid, w_lo = wfrag_t_pieces
-    _bf16_maps((g_hi, g_mid, g_lo), "conv3x3_dgrad_s2_x6")
-    H, W = in_hw
-    B, co, Ho, Wo = g_hi.shape
-    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1) or tuple(mask_in.shape) != (B, H, W) or mask_in.dtype != torch.uint8 or not mask_in.is_contiguous():
-        raise PnxError("conv3x3_dgrad_s2_x6: g (B,cout,Ho,Wo) with Ho = (H - 1) // 2 + 1 and a contiguous uint8 (B,H,W) mask of the input sites")
-    if any(w.dtype != torch.bfloat16 or w.numel() != w_hi.numel() for w in (w_hi, w_mid, w_lo)):
-        raise PnxError("conv3x3_dgrad_s2_x6: the weights must be three packed bf16 pieces of one size")
-    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=g_hi.device, memory_format=torch.channels_last)
-    check(lib().pnx_conv3x3_dgrad_s2_x6(ptr(g_hi), ptr(g_mid), ptr(g_lo), ptr(w_hi), ptr(w_mid), ptr(w_lo), ptr(mask_in), ptr(dx), B, H, W, cin, co,
-                                        stream_ptr()), "pnx_conv3x3_dgrad_s2_x6")
-    return dx
-
-
-def conv3x3_dgrad_s2(g, wfrag_t, cin, in_hw, mask_in, g_lo=None, wfrag_t_lo=None):
+def conv3x3_dgrad_s2(g, wfrag_t, cin, in_hw, mask_in):
     """Data gradient (B,cin,H,W) channels_last of a stride-2 masked 3x3 convolution from the upstream gradient g (B,cout,Ho,Wo) channels_last bf16 and the
-    TRANSPOSED weight pack (conv3x3_pack_weights(w, transposed=True)); mask_in uint8 (B,H,W): the layer's input active set.  With g_lo / wfrag_t_lo (the
-    bf16 low halves, split_f32) the three-product fp32 form: fp32 out."""
+    TRANSPOSED weight pack (conv3x3_pack_weights(w, transposed=True)); mask_in uint8 (B,H,W): the layer's input active set, zeros outside it.  One tensor
+    each: bf16 out (pnx_conv3x3_dgrad_s2_bf16).  Equal-length tuples of the 2 or 3 bf16 pieces of an fp32 g (split_f32) and of the fp32 weights: the
+    three- or six-product form, fp32 out (pnx_conv3x3_dgrad_s2_x3 / _x6)."""
+    gs, ws = _pieces(g), _pieces(wfrag_t)
+    if len(gs) not in _PIECES_TAG:
+        raise PnxError("conv3x3_dgrad_s2: g must be one bf16 tensor or a tuple of 2 or 3 pieces")
+    _bf16_maps(gs, "conv3x3_dgrad_s2")
+    _bf16_packs(ws, len(gs), "conv3x3_dgrad_s2")
     H, W = in_hw
-    B, co, Ho, Wo = g.shape
-    x3 = g_lo is not None
-    for tns in (g,) + ((g_lo,) if x3 else ()):
-        if not (tns.is_cuda and tns.dtype == torch.bfloat16 and tns.dim() == 4 and tns.is_contiguous(memory_format=torch.channels_last) and tns.shape == g.shape):
-            raise PnxError("conv3x3_dgrad_s2 needs channels_last bf16 CUDA gradients")
+    B, co, Ho, Wo = gs[0].shape
     if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1) or tuple(mask_in.shape) != (B, H, W) or mask_in.dtype != torch.uint8 or not mask_in.is_contiguous():
         raise PnxError("conv3x3_dgrad_s2: g (B,cout,Ho,Wo) with Ho = (H - 1) // 2 + 1 and a contiguous uint8 (B,H,W) mask of the input sites")
-    dx = torch.empty((B, cin, H, W), dtype=torch.float32 if x3 else torch.bfloat16, device=g.device, memory_format=torch.channels_last)
-    if x3:
-        check(lib().pnx_conv3x3_dgrad_s2_x3(ptr(g), ptr(g_lo), ptr(wfrag_t), ptr(wfrag_t_lo), ptr(mask_in), ptr(dx), B, H, W, cin, co, stream_ptr()), "pnx_conv3x3_dgrad_s2_x3")
-    else:
-        check(lib().pnx_conv3x3_dgrad_s2_bf16(ptr(g), ptr(wfrag_t), ptr(mask_in), ptr(dx), B, H, W, cin, co, stream_ptr()), "pnx_conv3x3_dgrad_s2_bf16")
+    dx = torch.empty((B, cin, H, W), dtype=torch.bfloat16 if len(gs) == 1 else torch.float32, device=gs[0].device, memory_format=torch.channels_last)
+    name = "pnx_conv3x3_dgrad_s2_" + _PIECES_TAG[len(gs)]
+    check(getattr(lib(), name)(*map(ptr, gs), *map(ptr, ws), ptr(mask_in), ptr(dx), B, H, W, cin, co, stream_ptr()), name)
     return dx
 
 
@@ -744,10 +674,7 @@ def conv3x3_smallk_wgrad(x, dy, want_bias=True):
         raise PnxError("conv3x3_smallk_wgrad: x (B,64,H,W), dy (B,k,H,W) of the same dtype, k <= 4")
     dyc = dy.permute(0, 2, 3, 1).contiguous()    # NHWC with k channels (a no-op for a channels_last gradient)
     nbytes = int(lib().pnx_conv3x3_smallk_wgrad_workspace_bytes(k))
-    key = (nbytes, x.device, torch.cuda.current_stream().cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _wgrad_workspace(nbytes, x.device)
     dw = torch.empty((k, 64, 3, 3), dtype=torch.float32, device=x.device)
     db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
     check(lib().pnx_conv3x3_smallk_wgrad(ptr(x), ptr(dyc), ptr(dw), ptr(db), B, H, W, 64, k, 0 if x.dtype == torch.float32 else 1, ptr(ws), ws.numel(), stream_ptr()),

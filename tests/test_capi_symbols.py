@@ -82,6 +82,57 @@ def test_conv_entry_points_validate_before_launching():
     assert rc < 0 and b"bad arguments" in L.pnx_last_error()
 
 
+def test_training_conv_entry_points_validate_before_launching():
+    """The eight training-convolution entry points (fp32 forward, stride-2 data gradient, weight gradient; 1, 2 and 3 bf16 pieces per
+    operand) reject bad arguments before any HIP call: return code and message of each case, with the entry's own name where it carries one."""
+    from pillarnext_amd import _lib
+
+    L = _lib.lib()
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    odd = ctypes.c_void_p(p.value + 8)  # 8-byte aligned only
+    big = 1 << 30
+
+    def check(rc, code, msg):
+        err = L.pnx_last_error()
+        assert rc == code and msg in err, (rc, err)
+
+    # fp32 forward, two pieces: (x_hi, x_lo, wfrag_hi, wfrag_lo, bias, mask, y, batch, h, w, cin, cout, stride, stream)
+    check(L.pnx_conv3x3_x3(p, None, p, p, p, p, p, 1, 8, 8, 64, 64, 1, None), -1, b"null pointer")
+    check(L.pnx_conv3x3_x3(p, p, p, p, p, p, p, 1, 8, 8, 64, 64, 3, None), -2, b"stride 3")
+    check(L.pnx_conv3x3_x3(p, odd, p, p, p, p, p, 1, 8, 8, 64, 64, 1, None), -1, b"alignment")
+    check(L.pnx_conv3x3_x3(p, p, p, p, p, p, p, 1, 8, 8, 48, 64, 1, None), -2, b"pnx_conv3x3_x3: no kernel for 48 -> 64 channels, stride 1")
+    check(L.pnx_conv3x3_x3(p, p, p, p, p, p, p, 1, 8, 8, 64, 64, 2, None), -2, b"pnx_conv3x3_x3: no kernel for 64 -> 64 channels, stride 2")
+    # three pieces: (x_hi, x_mid, x_lo, wfrag_hi, wfrag_mid, wfrag_lo, bias, mask, y, ...)
+    check(L.pnx_conv3x3_x6(p, p, None, p, p, p, p, p, p, 1, 8, 8, 64, 64, 1, None), -1, b"null pointer")
+    check(L.pnx_conv3x3_x6(p, p, p, p, p, p, p, p, p, 1, 8, 8, 64, 128, 1, None), -2, b"pnx_conv3x3_x6: no kernel for 64 -> 128")
+    check(L.pnx_conv3x3_x6(p, p, p, p, p, odd, p, p, p, 1, 8, 8, 64, 64, 1, None), -1, b"alignment")
+
+    # stride-2 data gradient: (g.., wfrag_t.., mask_in, dx, batch, h, w, cin, cout, stream)
+    check(L.pnx_conv3x3_dgrad_s2_bf16(p, None, p, p, 1, 8, 8, 64, 128, None), -1, b"pnx_conv3x3_dgrad_s2_bf16: bad arguments")
+    check(L.pnx_conv3x3_dgrad_s2_bf16(p, p, p, p, 1, 8, 8, 64, 64, None), -2, b"pnx_conv3x3_dgrad_s2_bf16: no kernel for 64 -> 64")
+    check(L.pnx_conv3x3_dgrad_s2_x3(p, None, p, p, p, p, 1, 8, 8, 64, 128, None), -1, b"pnx_conv3x3_dgrad_s2_x3: bad arguments")
+    check(L.pnx_conv3x3_dgrad_s2_x3(p, p, p, p, p, p, 1, 8, 8, 128, 128, None), -2, b"pnx_conv3x3_dgrad_s2_x3: no kernel for 128 -> 128")
+    check(L.pnx_conv3x3_dgrad_s2_x6(p, p, p, p, p, None, p, p, 1, 8, 8, 64, 128, None), -1, b"pnx_conv3x3_dgrad_s2_x6: bad arguments")
+    check(L.pnx_conv3x3_dgrad_s2_x6(p, p, p, p, p, p, p, p, 1, 8, 8, 64, 64, None), -2, b"pnx_conv3x3_dgrad_s2_x6: no kernel for 64 -> 64")
+    check(L.pnx_conv3x3_dgrad_s2_x6(p, odd, p, p, p, p, p, p, 1, 8, 8, 64, 128, None), -1, b"alignment")
+
+    # weight gradient: (x.., dy.., mask, dw, batch, h, w, cin, cout, stride, workspace, workspace_bytes, stream)
+    check(L.pnx_conv3x3_wgrad_bf16(p, None, p, p, 1, 8, 8, 64, 64, 1, p, big, None), -1, b"pnx_conv3x3_wgrad_bf16: bad arguments")
+    check(L.pnx_conv3x3_wgrad_bf16(p, p, p, p, 1, 8, 8, 48, 64, 1, p, big, None), -2, b"weight gradient for 48 -> 64")
+    check(L.pnx_conv3x3_wgrad_bf16(p, p, p, p, 1, 8, 8, 64, 64, 3, p, big, None), -2, b"stride 3")
+    check(L.pnx_conv3x3_wgrad_bf16(p, p, p, p, 1, 8, 8, 64, 64, 1, p, 16, None), -3, b"workspace too small")
+    check(L.pnx_conv3x3_wgrad_x3(p, p, p, None, p, p, 1, 8, 8, 64, 64, 1, p, big, None), -1, b"pnx_conv3x3_wgrad_x3: bad arguments")
+    check(L.pnx_conv3x3_wgrad_x3(p, p, p, p, p, p, 1, 8, 8, 576, 64, 1, p, big, None), -2, b"weight gradient for 576 -> 64")
+    check(L.pnx_conv3x3_wgrad_x3(p, p, p, p, p, p, 1, 8, 8, 64, 64, 3, p, big, None), -2, b"stride 3")
+    check(L.pnx_conv3x3_wgrad_x3(p, p, p, p, p, p, 1, 8, 8, 64, 64, 2, p, 16, None), -3, b"workspace too small")
+    check(L.pnx_conv3x3_wgrad_x6(p, p, p, p, p, p, None, p, 1, 8, 8, 64, 64, 1, p, big, None), -1, b"pnx_conv3x3_wgrad_x6: bad arguments")
+    check(L.pnx_conv3x3_wgrad_x6(p, p, p, p, p, p, p, p, 1, 8, 8, 48, 64, 1, p, big, None), -2, b"weight gradient for 48 -> 64")
+    check(L.pnx_conv3x3_wgrad_x6(p, p, p, p, p, p, p, p, 1, 8, 8, 64, 64, 3, p, big, None), -2, b"stride 3")
+    check(L.pnx_conv3x3_wgrad_x6(p, p, p, p, p, p, p, p, 1, 8, 8, 64, 64, 1, p, 16, None), -3, b"workspace too small")
+    check(L.pnx_conv3x3_wgrad_x6(p, p, p, p, odd, p, p, p, 1, 8, 8, 64, 64, 1, p, big, None), -1, b"alignment")
+
+
 def test_round2_entry_points_validate_before_launching():
     """The entry points added in round 2 reject bad arguments before any HIP call (runs without a GPU)."""
     from pillarnext_amd import _lib

@@ -50,7 +50,7 @@ def test_split3_pieces_are_exact():
     gen = torch.Generator(device="cuda").manual_seed(11)
     x = _wide_values((3, 64, 17, 8), gen).contiguous(memory_format=torch.channels_last)
     x[0, 0, 0, :2] = torch.tensor([0.0, -0.0], device="cuda")
-    hi, mid, lo = ops.split3_f32(x)
+    hi, mid, lo = ops.split_f32(x, pieces=3)
     for p in (hi, mid, lo):
         assert p.dtype == torch.bfloat16 and p.is_contiguous(memory_format=torch.channels_last) and p.shape == x.shape
     assert torch.equal(_bits(hi), _bits(x.to(torch.bfloat16)))                          # hi = RNE(x), like torch's cast
@@ -61,18 +61,18 @@ def test_split3_pieces_are_exact():
     m = (torch.rand((3, 17, 8), device="cuda", generator=gen) < 0.4).to(torch.uint8)
     keep = m[:, None].bool().expand_as(x)
     xm = torch.where(keep, x, torch.full_like(x, float("nan")))
-    for got, want in zip(ops.split3_f32(xm, m), (hi, mid, lo)):
+    for got, want in zip(ops.split_f32(xm, m, pieces=3), (hi, mid, lo)):
         assert torch.equal(_bits(got)[keep], _bits(want)[keep]) and bool((_bits(got)[~keep] == 0).all())
     # non-finite values: the convention of pnx_split_f32 (hi = the bf16 cast; the lower pieces of an inf / nan are nan)
     xn = x.clone()
     xn[1, :3, 2, 3] = torch.tensor([float("inf"), -float("inf"), float("nan")], device="cuda")
-    h3, m3, l3 = ops.split3_f32(xn)
+    h3, m3, l3 = ops.split_f32(xn, pieces=3)
     h2, l2 = ops.split_f32(xn)
     bad = ~torch.isfinite(xn)
     assert torch.equal(_bits(h3), _bits(h2))
     assert bool(torch.isnan(m3[bad]).all()) and bool(torch.isnan(l3[bad]).all()) and bool(torch.isnan(l2[bad]).all())
     with pytest.raises(Exception):
-        ops.split3_f32(x.contiguous(), m)           # the mask form is for channels_last maps
+        ops.split_f32(x.contiguous(), m, pieces=3)           # the mask form is for channels_last maps
 
 
 def _run_backbone(cin, cout, stride, subm, shape, monkeypatch, pieces="3", x_scale=None, g_scale=1.0):
@@ -205,14 +205,14 @@ def test_default_is_the_three_product_node(monkeypatch):
         w = r["conv"].weight
         xh, xl = ops.split_f32(r["x0"], mi)
         wh, wl = _split_pack(w)
-        assert torch.equal(r["y"], ops.conv3x3_x3(xh, xl, wh, wl, w.shape[0], r["stride"], mo))
+        assert torch.equal(r["y"], ops.conv3x3_f32((xh, xl), (wh, wl), w.shape[0], r["stride"], mo))
         gh, gl = ops.split_f32(r["g0"], mo)
-        assert torch.equal(r["dw"], ops.conv3x3_wgrad_x3(xh, xl, gh, gl, mo, stride=r["stride"]))
+        assert torch.equal(r["dw"], ops.conv3x3_wgrad((xh, xl), (gh, gl), mo, stride=r["stride"]))
         wth, wtl = _split_pack(w, transposed=True)
         if r["stride"] == 1:
-            dx = ops.conv3x3_x3(gh, gl, wth, wtl, w.shape[1], 1, mi)
+            dx = ops.conv3x3_f32((gh, gl), (wth, wtl), w.shape[1], 1, mi)
         else:
-            dx = ops.conv3x3_dgrad_s2(gh, wth, w.shape[1], r["x0"].shape[2:], mi, g_lo=gl, wfrag_t_lo=wtl)
+            dx = ops.conv3x3_dgrad_s2((gh, gl), (wth, wtl), w.shape[1], r["x0"].shape[2:], mi)
         assert torch.equal(r["dx"], dx)
     # a dense layer (bias)
     gen = torch.Generator(device="cuda").manual_seed(7)
@@ -234,7 +234,7 @@ def test_default_is_the_three_product_node(monkeypatch):
         assert a is b if isinstance(a, type) else torch.equal(a, b)
     xh, xl = ops.split_f32(x0)
     wh, wl = _split_pack(conv.weight)
-    assert torch.equal(outs[0][0], ops.conv3x3_x3(xh, xl, wh, wl, 128, 1, None, bias=conv.bias.detach()))
+    assert torch.equal(outs[0][0], ops.conv3x3_f32((xh, xl), (wh, wl), 128, 1, None, bias=conv.bias.detach()))
     # the six-product form is another computation (closer to fp64)
     monkeypatch.setenv("PNX_TRAIN_F32_PIECES", "3")
     y6 = x3_conv(conv, x0.clone().requires_grad_(True))

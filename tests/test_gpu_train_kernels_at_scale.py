@@ -227,7 +227,7 @@ WGRAD = [(64, 64, 1, (2, 801, 417)), (128, 128, 1, (2, 230, 190)), (256, 256, 1,
 @pytest.mark.parametrize("kind", ["lidar", "dense"])
 @pytest.mark.parametrize("cin,cout,stride,shape", WGRAD)
 def test_wgrad_kernels_over_many_tiles_per_workgroup(cin, cout, stride, shape, kind):
-    """ops.conv3x3_wgrad / _x3 / _x6 (csrc/conv_wgrad.hip) with >= 3 non-empty tiles in every workgroup's list (the k + 1 prefetch and the s_rm[k & 1] row
+    """ops.conv3x3_wgrad on 1, 2 and 3 pieces (csrc/conv_wgrad.hip) with >= 3 non-empty tiles in every workgroup's list (the k + 1 prefetch and the s_rm[k & 1] row
     masks run), partial bottom and right tiles, an upstream gradient that is NOT zero outside the mask: against fp64, bit-identical on a second call,
     exactly zero on an empty mask."""
     import torch.nn.functional as F
@@ -257,10 +257,10 @@ def test_wgrad_kernels_over_many_tiles_per_workgroup(cin, cout, stride, shape, k
             run = lambda mk: ops.conv3x3_wgrad(xs[0], gs[0], mk, stride=stride)  # noqa: E731
         elif prec == "x3":
             xs, gs = ops.split_f32(x0), ops.split_f32(g_all)
-            run = lambda mk: ops.conv3x3_wgrad_x3(xs[0], xs[1], gs[0], gs[1], mk, stride=stride)  # noqa: E731
+            run = lambda mk: ops.conv3x3_wgrad(xs, gs, mk, stride=stride)  # noqa: E731
         else:
-            xs, gs = ops.split3_f32(x0), ops.split3_f32(g_all)
-            run = lambda mk: ops.conv3x3_wgrad_x6(xs, gs, mk, stride=stride)  # noqa: E731
+            xs, gs = ops.split_f32(x0, pieces=3), ops.split_f32(g_all, pieces=3)
+            run = lambda mk: ops.conv3x3_wgrad(xs, gs, mk, stride=stride)  # noqa: E731
         dw = run(mu8)
         assert torch.equal(dw, run(mu8)), (tag, prec, "not bit-identical on a second call")
         assert float(run(empty).abs().max()) == 0.0, (tag, prec, "an empty mask")
@@ -290,8 +290,8 @@ def test_fp32_wgrad_forms_have_no_systematic_offset():
     ref = torch.empty((C, C, 3, 3), dtype=torch.float64, device="cuda")
     for t in range(9):
         ref[:, :, t // 3, t % 3] = g2.t() @ xp[:, t // 3:t // 3 + H, t % 3:t % 3 + W].reshape(-1, C)
-    for prec, dw in (("x3", ops.conv3x3_wgrad_x3(*ops.split_f32(x), *ops.split_f32(g), ones)),
-                     ("x6", ops.conv3x3_wgrad_x6(ops.split3_f32(x), ops.split3_f32(g), ones))):
+    for prec, dw in (("x3", ops.conv3x3_wgrad(ops.split_f32(x), ops.split_f32(g), ones)),
+                     ("x6", ops.conv3x3_wgrad(ops.split_f32(x, pieces=3), ops.split_f32(g, pieces=3), ones))):
         e = dw.double() - ref
         mean, rms, fro = float(e.mean()), float(e.pow(2).mean().sqrt()), _fro(dw, ref)
         print(f"wgrad {prec} 64->64 {B}x{H}x{W} (32 tiles / workgroup): mean error {mean:.2e}, rms {rms:.2e}, relative Frobenius {fro:.2e}")
@@ -451,7 +451,7 @@ def test_ticket_ring_wraps_without_losing_tiles():
     for i in range(132):
         s = i & 1
         xh, xl, mu = pc[s]
-        y = ops.conv3x3_x3(xh, xl, wh, wl, 64, 1, mu)
+        y = ops.conv3x3_f32((xh, xl), (wh, wl), 64, 1, mu)
         g, hw, mi = dg[s]
         dx = ops.conv3x3_dgrad_s2(g, wt, 64, hw, mi)
         if first_pc[s] is None:
