@@ -9,11 +9,12 @@
 // fragments (weights) are pre-arranged on the host in fragment order.  Kernels in this file:
 //   k_conv3x3          direct: B fragments straight from L1/L2 (strided layers; every input line is re-read 9 times)
 //   k_conv3x3_pc       (conv_pc.h, round 6; default for 64 -> 64) producer / consumer form: 4 producer waves stage the NEXT tile by LDS-DMA into a ring of
-//                      slots while 8 consumer waves (row groups x 32-channel groups) run the taps; one workgroup per CU
+//                      slots while 8 consumer waves (row groups x 32-channel groups) run the taps; one workgroup per CU; with a mask, 64 -> 64
+//                      computes the tile's active pixels packed in groups of 32 (PNX_CONV_PACK bit 1, default on; see pc_pix64)
 //   k_conv3x3_lds      stride 1, 64 input channels: 18x34 halo tile staged once in LDS, 1..7 passes of 64 output channels
 //   k_conv3x3_ldsx     stride 1, 128 -> 128 and 256 -> 256: 10x34 tile, 64-channel input slabs through one LDS buffer under live
 //                      accumulators, 128 output channels per pass; with a mask, 128 -> 128 and 256 -> 256 compute the tile's active pixels
-//                      packed in groups of 32 (PNX_CONV_PACK, default on; see conv_pix_x)
+//                      packed in groups of 32 (PNX_CONV_PACK bit 0, default on; see conv_pix_x)
 //   k_sephead_out      block-diagonal 16-output convolution closing the merged SepHead branches (16x16x32 MFMA)
 // Rows/tiles without an active site skip their MFMAs (and, with row_dirty, their HBM traffic) -- that is where the sparsity of
 // the BEV map pays in a dense layout; bias and residual start the accumulators, the epilogue (ReLU, mask, bf16 pack) writes
@@ -578,7 +579,8 @@ __device__ __forceinline__ void conv_taps_rolled(v16f (&acc)[NR][MB], const uint
 #endif
 // PIX (the packed-pixel form of k_conv3x3_ldsx): rbase[0] is not a wave-uniform row base but this lane's own pixels in the NR pixel groups, one
 // pix_code byte per group (byte j: group j), and the slot of every group is recomputed per j from an opaque copy of that word.
-template <int NR, int MTALL, int CB = 4, int STRIDE = 1, int MB = 2, int WD = TAPS_WD, bool PIX = false>
+// PIXB = 16 (the packed form of k_conv3x3_pc: 16-row tiles, 9-bit codes): half-word codes, groups 0, 1 in rbase[0] and groups 2, 3 in rbase[1].
+template <int NR, int MTALL, int CB = 4, int STRIDE = 1, int MB = 2, int WD = TAPS_WD, bool PIX = false, int PIXB = 8>
 __device__ __forceinline__ void conv_taps(v16f (&acc)[NR][MB], const uint4* __restrict__ s_in, const uint4* __restrict__ wfrag, const int (&rbase)[4],
                                           int mg, int px, int kb, int lane, int kstep0 = 0) {
 #ifdef PNX_TAPS_ROLLED
@@ -618,7 +620,19 @@ __device__ __forceinline__ void conv_taps(v16f (&acc)[NR][MB], const uint4* __re
   int addr[NR];
   auto group_addr = [&](int grp) {
     const int dx = grp >> 2, cbl = grp & 3;
-    if constexpr (PIX) {
+    if constexpr (PIX && PIXB == 16) {
+      int p[2] = {rbase[0], rbase[1]};
+      asm volatile("" : "+v"(p[0]));
+      if (NR > 2) asm volatile("" : "+v"(p[1]));
+#pragma unroll
+      for (int j = 0; j < NR; j++) {
+        const int q = (p[j >> 1] >> (16 * (j & 1))) & 0xffff;
+        const int c = tap_slot<STRIDE>(q & 31, dx);
+        addr[j] = (q >> 5) * (RS * 8) + c * 8 + ((2 * cbl + kb) ^ lds_swz(c));
+        asm volatile("" : "+v"(addr[j]));
+      }
+      return;
+    } else if constexpr (PIX) {
       int p = rbase[0];
       asm volatile("" : "+v"(p));
 #pragma unroll
@@ -1848,8 +1862,12 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
   hipStream_t st = (hipStream_t)stream;
   if (stride == 1 && getenv("PNX_CONV_DIRECT") == nullptr) {
     static const int pc_mode = getenv("PNX_CONV_PC") != nullptr ? atoi(getenv("PNX_CONV_PC")) : 1;  // bit 0: 64 -> 64 on the producer / consumer kernel (default), bit 1: 128 -> 128 and 256 -> 256, bit 2: 64 -> 320 / 384 / 448; 0: row-split kernels only (the cross-check)
+    // PNX_CONV_PACK: the packed-pixel forms, used whenever a mask is given.  Bit 0: 128 -> 128 and 256 -> 256 (k_conv3x3_ldsx<..., PACK>), bit 1: 64 -> 64
+    // (k_conv3x3_pc<64, 64, ..., PACK>); unset: both; 0: the row forms everywhere (the cross-check)
+    static const int pack_mode = getenv("PNX_CONV_PACK") != nullptr ? atoi(getenv("PNX_CONV_PACK")) : 3;
     if (pc_mode != 0) {
-      if (cin == 64 && cout == 64) return launch_pc<64, 64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
+      if (cin == 64 && cout == 64)
+        return launch_pc<64, 64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st, (pack_mode & 2) != 0);
       if (residual == nullptr && (pc_mode & 4)) {  // slower than the multi-pass row-split kernel (profiles/r06_conv_pc_ab.txt): each pass re-reads the B fragments for half the channels
         if (cin == 64 && cout == 320) return launch_pc<64, 320>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
         if (cin == 64 && cout == 384) return launch_pc<64, 384>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
@@ -1861,8 +1879,7 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
       }
     }
     if (cin == 64 && cout == 64) return launch_lds<64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
-    // PNX_CONV_PACK (default 1): masked 128 -> 128 and 256 -> 256 on the packed-pixel form of k_conv3x3_ldsx; 0: the row form (the cross-check)
-    static const bool pack = getenv("PNX_CONV_PACK") == nullptr || atoi(getenv("PNX_CONV_PACK")) != 0;
+    const bool pack = (pack_mode & 1) != 0;
     if (cin == 128 && cout == 128) return launch_ldsx<128, 128>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st, pack);
     if (cin == 256 && cout == 64) return launch_ldsx<256, 64>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st);
     if (cin == 256 && cout == 256) return launch_ldsx<256, 256>(x, wfrag, bias, residual, mask, y, batch, h, w, relu, row_dirty, tile_list, tile_count, st, pack);

@@ -7,7 +7,8 @@
 // the MFMA pipe 28 % busy (profiles/r02_conv_sq_counters.md).  A wave cannot prefetch the next tile behind its own weight stream because
 // LDS-DMA and the weight-fragment loads share one in-order vmcnt.  Here the roles are separate waves of ONE 12-wave workgroup per CU:
 //   waves 8..11  producers: tile schedule (tickets three tiles ahead), mask bytes -> row masks, the deal of the tile's active rows to the row groups
-//                (producer 0), zero-fill of rows that went inactive, and the HBM -> LDS staging of the NEXT tile (global_load_lds) into a ring of
+//                (producer 0; packed form: the list of the tile's active pixels), zero-fill of rows that went inactive (packed form: and of the
+//                inactive pixels of active rows), and the HBM -> LDS staging of the NEXT tile (global_load_lds) into a ring of
 //                halo-tile slots, one fill ahead of the consumers; their vmcnt holds nothing else;
 //   waves 0..7   consumers: NRG row groups x NCG groups of 32 output channels; a wave = up to 4 row segments x 32 channels (64 accumulator
 //                registers, 140-167 in all and no scratch, so three waves fit a SIMD: two consumers + one producer), weights through a buffer
@@ -148,8 +149,88 @@ __device__ __forceinline__ void pc_rows(const uint4* __restrict__ s_ring, int& g
   }
 }
 
+// ---- packed-pixel form of the masked 64 -> 64 kernel (PACK; PNX_CONV_PACK bit 1).  Stage 0 runs on the 3x3 dilation of the occupancy: 30 % of the 32-pixel
+// row segments hold an active pixel but only 16.5 % of the pixels are active (profiles/r03_occupancy_stats.txt).  Producer 0 lists the tile's active pixels
+// row-major (s_list: one 9-bit pix_code per entry, up to 512), the list is cut into groups of 32 and the groups -- not the row segments -- are dealt to the
+// 4 row groups: group rg + 4 j is the j-th of row group rg.  ceil(P / 32) never exceeds the number of active rows.  Per output element nothing changes
+// (accumulator = bias tile, k-steps in (dx, chunk, dy) order, the epilogue of pc_rows), so the output is bit-identical to the row form; what changes is the
+// addressing: B fragments from the lane's own listed pixel (conv_taps<PIX, 16>), stores and residual loads = tile origin + a 32-bit per-lane pixel offset.
+// The inactive pixels of active rows, which the row form zeroes with the row, are zeroed by the producers (advance), one tile ahead.
+__device__ __forceinline__ uint32_t pc_pix_off64(int code, int W) { return (uint32_t)(((code >> 5) * W + (code & 31)) * 64) * 2u; }
+
+// One tile of a consumer wave: NR pixel groups x its 32 output channels.  codes[0] / codes[1] = pix_code of this lane's pixel in groups 0, 1 / 2, 3 (half words;
+// lanes px >= n_g[j] carry code 0: they compute pixel (0, 0) of the tile and are neither loaded from the residual nor stored); y_t / res_t = tile origin.
+template <int NR, bool HAS_RES, int NSLOT, int SLOT_N>
+__device__ __forceinline__ void pc_pix64(const uint4* __restrict__ s_ring, int& g, const uint4* __restrict__ wfrag, const float* __restrict__ bias,
+                                         const uint16_t* __restrict__ res_t, uint16_t* __restrict__ y_t, const int (&codes)[2], const int (&n_g)[4], int W,
+                                         int cg, int relu, int px, int kb, int lane
+#ifdef PNX_CONV_TIMERS
+                                         , unsigned long long (&pc_T)[8], unsigned long long& pc_tk
+#endif
+) {
+  constexpr int NRA = NR > 0 ? NR : 1;
+  v16f acc[NRA][1];
+  uint4 rq[2];
+  if (NR > 0) {
+    const v16f bq = bias_tile(bias, cg * 32, kb);
+#pragma unroll
+    for (int j = 0; j < NR; j++) acc[j][0] = bq;
+    auto code = [&](int j) { return (codes[j >> 1] >> (16 * (j & 1))) & 0xffff; };
+    const char* const rp = reinterpret_cast<const char*>(res_t + cg * 32) + 16 * kb;  // residual: group 0's lines arrive under the taps, group j + 1's before group j is packed
+    if (HAS_RES) {
+      const uint32_t o = pc_pix_off64(code(0), W);
+#pragma unroll
+      for (int t = 0; t < 2; t++) {
+        rq[t] = make_uint4(0, 0, 0, 0);
+        if (px < n_g[0]) rq[t] = *reinterpret_cast<const uint4*>(rp + o + 32 * t);
+      }
+    }
+    const int cw[4] = {codes[0], codes[1], 0, 0};
+    conv_taps<NRA, 2, 4, 1, 1, TAPS_WD, true, 16>(acc, s_ring + (g % NSLOT) * SLOT_N, wfrag, cw, cg, px, kb, lane, 0);
+  }
+  PC_TOCK(1)
+  pc_barrier_lds();
+  g++;
+  PC_TOCK(2)
+  if (NR > 0) {
+    auto code = [&](int j) { return (codes[j >> 1] >> (16 * (j & 1))) & 0xffff; };
+    const char* const rp = reinterpret_cast<const char*>(res_t + cg * 32) + 16 * kb;
+    char* const yp = reinterpret_cast<char*>(y_t + cg * 32);
+#pragma unroll
+    for (int j = 0; j < NR; j++) {
+      const bool act = px < n_g[j];
+      uint4 rc[2];
+      if (HAS_RES) {
+        rc[0] = rq[0], rc[1] = rq[1];
+        if (j + 1 < NR) {
+          const uint32_t o = pc_pix_off64(code(j + 1), W);
+#pragma unroll
+          for (int t = 0; t < 2; t++) {
+            rq[t] = make_uint4(0, 0, 0, 0);
+            if (px < n_g[j + 1]) rq[t] = *reinterpret_cast<const uint4*>(rp + o + 32 * t);
+          }
+        }
+      }
+      uint4 pk[2];
+      pack_tile(acc[j][0], act, relu, pk, HAS_RES ? rc : nullptr);
+      transpose_row32(pk, lane);
+      // store_row32 for a pixel group: store d of lane L is chunk L & 3 of listed pixel 16 d + (L >> 2), whose code lane 16 d + (L >> 2) holds
+      int l = lane;
+      asm volatile("" : "+v"(l));  // opaque: the permute addresses are recomputed here, not held across the tile loop
+      const int cj = code(j);
+#pragma unroll
+      for (int d = 0; d < 2; d++) {
+        const int P = 16 * d + (l >> 2);
+        const int pc = __builtin_amdgcn_ds_bpermute(P << 2, cj);
+        if (P < n_g[j]) *reinterpret_cast<uint4*>(yp + pc_pix_off64(pc, W) + (uint32_t)((l & 3) * 16)) = pk[d];
+      }
+    }
+  }
+  PC_TOCK(3)
+}
+
 // NP > 1 (see pc_rows): x / x2 / x3 = x_hi / x_lo (NP 2) or x_hi / x_mid / x_lo (NP 3), wfrag* likewise; y is fp32.
-template <int CIN, int COUT, bool HAS_RES, int NP = 1>
+template <int CIN, int COUT, bool HAS_RES, int NP = 1, bool PACK = false>
 __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, const uint4* __restrict__ wfrag,
                                                        const uint4* __restrict__ wfrag2, const float* __restrict__ bias,
                                                        const uint16_t* __restrict__ res, const uint8_t* __restrict__ mask, uint16_t* __restrict__ y,
@@ -165,7 +246,9 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
   static_assert(!F32 || (!HAS_RES && (CIN > 64 || NPASS == 1)), "fp32 product: no residual; one pass when the tile is filled once per source");
   constexpr int SLOT_N = (TH + 2) * LDS_HW * 8;
   static_assert(COUT % PASS_C == 0 && CIN % 64 == 0, "passes of NCG x 32 output channels over 64-channel input slabs");
+  static_assert(!PACK || (CIN == 64 && COUT == 64 && NP == 1), "the packed-pixel form serves the bf16 / f16 64 -> 64 layers");
   __shared__ uint4 s_ring[NSLOT * SLOT_N];
+  __shared__ uint16_t s_list[PACK ? 4 * TH * 32 : 1];  // PACK: pix_code of the active pixels of tile n (n & 3), row-major; their number rides in s_tile[].w >> 16
   __shared__ int4 s_tile[4];               // this workgroup's n-th tile (n & 3): {image b (-1 = no more tiles), y0, x0, rows with an active site}
   __shared__ uint32_t s_rowmask[4][TH];    // its active-site masks, one word per row
   // the deal of the tile's active rows to the row groups, done ONCE by producer 0 (round 6: every consumer wave redoing it from the row masks was 11 % of the
@@ -235,10 +318,16 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       // row masks from the bytes requested one tile ago
       uint32_t my_rm = 0;  // lane r < TH: mask word of row r
       am = 0;
+      int n_px = 0;        // PACK: active pixels listed so far
 #pragma unroll
       for (int k = 0; k < TH / 2; k++) {
         const unsigned long long bal = __ballot(mb[k] != 0);
         const uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
+        if constexpr (PACK) {  // lane = (row 2k + (lane >> 5), pixel lane & 31): the ballot's bit order is the list's row-major order
+          if (pw == 0 && mb[k] != 0)
+            s_list[(n & 3) * (TH * 32) + n_px + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)(((2 * k + (lane >> 5)) << 5) | (lane & 31));
+          n_px += __popcll(bal);
+        }
         if (lane == 2 * k) my_rm = lo;
         if (lane == 2 * k + 1) my_rm = hi;
         am |= (lo != 0 ? 1u : 0u) << (2 * k) | (hi != 0 ? 1u : 0u) << (2 * k + 1);
@@ -246,7 +335,7 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       const uint32_t was = (uint32_t)__ballot(dirty != 0) & ((1u << TH) - 1u);
       if (pw == 0) {
         if (lane < TH) s_rowmask[n & 3][lane] = my_rm;
-        if (lane == 0) s_tile[n & 3] = make_int4(cb, cy0, cx0, (int)am);
+        if (lane == 0) s_tile[n & 3] = make_int4(cb, cy0, cx0, (int)(am | (uint32_t)n_px << 16));
         if (lane < NRG * 4) {  // lane = position in the list of active rows = rg + j * NRG
           uint32_t rest = am;
           for (int k = 0; k < lane && rest; k++) rest &= rest - 1;
@@ -275,6 +364,22 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
           const int nbytes = (W - cx0 < 32 ? W - cx0 : 32) * COUT * 2 * YS;
 #pragma unroll 1
           for (int o = lane * 16; o < nbytes; o += 1024) *reinterpret_cast<uint4*>(dst + o) = make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (PACK) {
+          // inactive pixels of an active row: the row form stores their zeros with the row; the consumers of this form store listed pixels only, so they
+          // are zeroed here where the segment may hold stale values (row_dirty; without one, always).  Other lines than the consumers write, so the order
+          // between the two does not matter.  Lane L writes chunk L & 7 of pixel c0 + (L >> 3): every store instruction covers 8 complete 128-byte lines.
+          if (active && w) {
+            const uint32_t cols = W - cx0 >= 32 ? 0xffffffffu : (1u << (W - cx0)) - 1u;  // columns inside the image
+            const uint32_t idle = ~(uint32_t)__builtin_amdgcn_readlane((int)my_rm, r) & cols;
+            char* dst = reinterpret_cast<char*>(y + (((int64_t)cb * H + oy) * W + cx0) * COUT);
+#pragma unroll 1
+            for (int c0 = 0; c0 < 32; c0 += 8) {
+              if (((idle >> c0) & 255u) == 0) continue;
+              const int p = c0 + (lane >> 3);
+              if ((idle >> p) & 1u) *reinterpret_cast<uint4*>(dst + p * (COUT * 2) + (lane & 7) * 16) = make_uint4(0, 0, 0, 0);
+            }
+          }
         }
         if (row_dirty != nullptr && lane == 0 && w != active) row_dirty[((int64_t)cb * H + oy) * tiles_x + tx] = active ? 1 : 0;
       }
@@ -357,6 +462,36 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       PC_TOCK(2)
       continue;
     }
+    if constexpr (PACK) {
+      // groups of 32 listed pixels, dealt round-robin to the 4 row groups: group rg + 4 j is this wave's j-th (at most TH / 4 of them)
+      const int n_px = __builtin_amdgcn_readfirstlane(ti.w) >> 16, n_grp = (n_px + 31) >> 5, rgu = __builtin_amdgcn_readfirstlane(rg);
+      const int nr = n_grp > rgu ? (n_grp - rgu + 3) >> 2 : 0;
+      int codes[2] = {0, 0}, n_g[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int gi = rgu + 4 * j;
+        n_g[j] = min(max(n_px - 32 * gi, 0), 32);
+        if (px < n_g[j]) codes[j >> 1] |= (int)s_list[(n & 3) * (TH * 32) + 32 * gi + px] << (16 * (j & 1));
+      }
+      const int64_t t0 = (((int64_t)b * H + y0) * W + x0) * COUT;  // tile origin
+      const uint16_t* res_t = HAS_RES ? res + t0 : nullptr;
+      uint16_t* y_t = y + t0;
+      PC_TOCK(0)
+#ifdef PNX_CONV_TIMERS
+#define PC_PIX(N_) pc_pix64<N_, HAS_RES, NSLOT, SLOT_N>(s_ring, g, wfrag, bias, res_t, y_t, codes, n_g, W, cg, relu, px, kb, lane, pc_T, pc_tk)
+#else
+#define PC_PIX(N_) pc_pix64<N_, HAS_RES, NSLOT, SLOT_N>(s_ring, g, wfrag, bias, res_t, y_t, codes, n_g, W, cg, relu, px, kb, lane)
+#endif
+      switch (nr) {  // wave-uniform; every case runs the same barrier
+        case 0: PC_PIX(0); break;
+        case 1: PC_PIX(1); break;
+        case 2: PC_PIX(2); break;
+        case 3: PC_PIX(3); break;
+        default: PC_PIX(4); break;
+      }
+#undef PC_PIX
+      continue;
+    }
     const int4 dr = s_drow[n & 3][rg];
     const uint4 dm = s_dmask[n & 3][rg];
     int rrow[4] = {__builtin_amdgcn_readfirstlane(dr.x), __builtin_amdgcn_readfirstlane(dr.y), __builtin_amdgcn_readfirstlane(dr.z),
@@ -391,13 +526,26 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
   PC_T_FLUSH
 }
 
+// pack: the packed-pixel form (masked 64 -> 64 only; the caller decides)
 template <int CIN, int COUT>
 int launch_pc(const void* x, const void* wfrag, const float* bias, const void* res, const uint8_t* mask, void* y, int B, int H, int W, int relu,
-              uint8_t* row_dirty, const int32_t* tlist, const int32_t* tcount, hipStream_t st) {
+              uint8_t* row_dirty, const int32_t* tlist, const int32_t* tcount, hipStream_t st, bool pack = false) {
   constexpr int TH = CIN == 64 ? 16 : 8;
   int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
   if (nb > 256) nb = 256;  // one 12-wave workgroup per CU (LDS: the ring takes 128-153 KiB)
   const int slot = mask != nullptr ? next_sched_slot() : -1;
+  if constexpr (CIN == 64 && COUT == 64) {
+    if (pack && mask != nullptr) {
+      if (res != nullptr)
+        k_conv3x3_pc<64, 64, true, 1, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, (const uint16_t*)res, mask,
+                                                                        (uint16_t*)y, B, H, W, relu, row_dirty, slot, tlist, tcount);
+      else
+        k_conv3x3_pc<64, 64, false, 1, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, nullptr, mask, (uint16_t*)y, B,
+                                                                         H, W, relu, row_dirty, slot, tlist, tcount);
+      PNX_LAUNCH_CHECK();
+      return PNX_OK;
+    }
+  }
   if (res != nullptr)
     k_conv3x3_pc<CIN, COUT, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, (const uint16_t*)res, mask, (uint16_t*)y, B, H,
                                                               W, relu, row_dirty, slot, tlist, tcount);
