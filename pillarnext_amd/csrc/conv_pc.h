@@ -528,30 +528,29 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
 
 // pack: the packed-pixel form (masked 64 -> 64 only; the caller decides)
 template <int CIN, int COUT>
-int launch_pc(const void* x, const void* wfrag, const float* bias, const void* res, const uint8_t* mask, void* y, int B, int H, int W, int relu,
-              uint8_t* row_dirty, const int32_t* tlist, const int32_t* tcount, hipStream_t st, bool pack = false) {
+int launch_pc(const ConvArgs& a, bool pack = false) {
   constexpr int TH = CIN == 64 ? 16 : 8;
-  int64_t nb = (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32);
+  int64_t nb = (int64_t)a.B * ((a.H + TH - 1) / TH) * ((a.W + 31) / 32);
   if (nb > 256) nb = 256;  // one 12-wave workgroup per CU (LDS: the ring takes 128-153 KiB)
-  const int slot = mask != nullptr ? next_sched_slot() : -1;
+  const int slot = a.mask != nullptr ? next_sched_slot() : -1;
   if constexpr (CIN == 64 && COUT == 64) {
-    if (pack && mask != nullptr) {
-      if (res != nullptr)
-        k_conv3x3_pc<64, 64, true, 1, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, (const uint16_t*)res, mask,
-                                                                        (uint16_t*)y, B, H, W, relu, row_dirty, slot, tlist, tcount);
+    if (pack && a.mask != nullptr) {
+      if (a.res != nullptr)
+        k_conv3x3_pc<64, 64, true, 1, true><<<(unsigned)nb, 768, 0, a.st>>>(a.x, nullptr, a.wfrag, nullptr, a.bias, a.res, a.mask, a.y, a.B, a.H, a.W, a.relu,
+                                                                          a.row_dirty, slot, a.tlist, a.tcount);
       else
-        k_conv3x3_pc<64, 64, false, 1, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, nullptr, mask, (uint16_t*)y, B,
-                                                                         H, W, relu, row_dirty, slot, tlist, tcount);
+        k_conv3x3_pc<64, 64, false, 1, true><<<(unsigned)nb, 768, 0, a.st>>>(a.x, nullptr, a.wfrag, nullptr, a.bias, nullptr, a.mask, a.y, a.B, a.H, a.W, a.relu,
+                                                                           a.row_dirty, slot, a.tlist, a.tcount);
       PNX_LAUNCH_CHECK();
       return PNX_OK;
     }
   }
-  if (res != nullptr)
-    k_conv3x3_pc<CIN, COUT, true><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, (const uint16_t*)res, mask, (uint16_t*)y, B, H,
-                                                              W, relu, row_dirty, slot, tlist, tcount);
+  if (a.res != nullptr)
+    k_conv3x3_pc<CIN, COUT, true><<<(unsigned)nb, 768, 0, a.st>>>(a.x, nullptr, a.wfrag, nullptr, a.bias, a.res, a.mask, a.y, a.B, a.H, a.W, a.relu, a.row_dirty,
+                                                                slot, a.tlist, a.tcount);
   else
-    k_conv3x3_pc<CIN, COUT, false><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x, nullptr, (const uint4*)wfrag, nullptr, bias, nullptr, mask, (uint16_t*)y, B, H, W, relu,
-                                                               row_dirty, slot, tlist, tcount);
+    k_conv3x3_pc<CIN, COUT, false><<<(unsigned)nb, 768, 0, a.st>>>(a.x, nullptr, a.wfrag, nullptr, a.bias, nullptr, a.mask, a.y, a.B, a.H, a.W, a.relu, a.row_dirty,
+                                                                 slot, a.tlist, a.tcount);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

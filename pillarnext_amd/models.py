@@ -1114,7 +1114,7 @@ class _HipConv3x3(nn.Module):
 
 
 class _HipDeconv2x2(nn.Module):
-    """ConvTranspose2d(k=2, s=2) + folded BN + ReLU in ONE HIP kernel (csrc/conv3x3.hip::k_deconv2x2_64): the SepHead deblock."""
+    """ConvTranspose2d(k=2, s=2) + folded BN + ReLU in ONE HIP kernel (csrc/sephead.h::k_deconv2x2_64): the SepHead deblock."""
 
     def __init__(self, weight, bias, relu=True, dtype=torch.bfloat16):
         super().__init__()
@@ -1129,7 +1129,7 @@ class _HipDeconv2x2(nn.Module):
 
 
 class _HipSepHeadOut(nn.Module):
-    """Last 3x3 conv of all SepHead branches of a task as ONE HIP kernel over the block-diagonal weight (csrc/conv3x3.hip::k_sephead_out)."""
+    """Last 3x3 conv of all SepHead branches of a task as ONE HIP kernel over the block-diagonal weight (csrc/sephead.h::k_sephead_out)."""
 
     def __init__(self, weight, bias, dtype=torch.bfloat16):
         super().__init__()

@@ -458,7 +458,7 @@ def deconv2x2(x, wfrag, bias, cout, relu=True):
 
 
 def sephead_pack_weights(w2, dtype=torch.bfloat16):
-    """Block-diagonal (16, nb*64, 3, 3) -> bf16 / fp16 fragment order [branch][tap][kc][lane = q*16 + o][8]  (csrc/conv3x3.hip::k_sephead_out)."""
+    """Block-diagonal (16, nb*64, 3, 3) -> bf16 / fp16 fragment order [branch][tap][kc][lane = q*16 + o][8]  (csrc/sephead.h::k_sephead_out)."""
     co, ci = w2.shape[:2]
     if co != 16 or ci % 64:
         raise PnxError("sephead_pack_weights wants a (16, nb*64, 3, 3) weight")
@@ -493,7 +493,7 @@ class _PnxLazyTask(ctypes.Structure):
 
 
 def sephead_lazy(tasks, class_task, batch, local, seg_len, pre_max):
-    """The regression branches of every task at the candidate cells (csrc/conv3x3.hip::k_sephead_lazy, one launch).
+    """The regression branches of every task at the candidate cells (csrc/sephead_lazy.h::k_sephead_lazy, one launch).
     tasks: list of (up (B,64,H,W) channels_last bf16 / fp16 (one dtype for all tasks), wfrag1 in that dtype, bias1, w2c, bias2); class_task: task index of every class (host list);
     local int64 (batch*len(class_task), pre_max) = b*H*W + cell per slot; seg_len int32 (batch*len(class_task),).  -> (lists, pre_max, 10) fp32,
     rows behind seg_len zero."""

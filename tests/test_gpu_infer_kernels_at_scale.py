@@ -1,11 +1,11 @@
-"""GPU: the inference convolution kernels (csrc/conv3x3.hip, csrc/conv_pc.h) at the shapes bench.py runs them at, one layer at a time, against fp64 on the
-SAME bf16 / f16 operands the kernel read.
+"""GPU: the inference convolution kernels (csrc/conv3x3.hip and the headers it includes: conv_rows.h, conv_s2.h, sephead.h, conv_pc.h) at the shapes
+bench.py runs them at, one layer at a time, against fp64 on the SAME bf16 / f16 operands the kernel read.
 
 The other inference tests use maps of 18 to 140 tiles per launch: every persistent workgroup takes one tile and exits, no ticket of the 64-slot g_tile_ctr
 ring is drawn, the depth-2 tile pipeline never iterates and the LDS words double-buffered by iteration parity are never reused; the tests that do reach many
 tiles per workgroup compare with fp32 F.conv2d at rtol 1.6e-2 / atol 2e-2, which passes an output that lost a tap on a few tiles.  Every case below first
 restates its launch's work split in Python (launch_lds, launch_ldsx, launch_pc, launch_s2, launch_direct, launch_deconv, launch_sephead: each names the
-constants of the .hip source it mirrors) and asserts (_reach) that its shape and mask reach the path it is there for: a case that does not reach it fails.
+constants of the source it mirrors) and asserts (_reach) that its shape and mask reach the path it is there for: a case that does not reach it fails.
 
 References: fp64 on the GPU, gathered at the active sites and chunked (_gconv_half: _gconv of tests/test_gpu_train_kernels_at_scale.py gathering from the
 half-precision map, so that a 12 x 64 x 1440^2 map never exists in fp64); bias, residual, ReLU and mask in fp64 too.  Bars (_check):
@@ -43,14 +43,14 @@ def _ntiles(B, H, W, th):
 
 
 def launch_lds(B, H, W):
-    """conv3x3.hip launch_lds<COUT> / k_conv3x3_lds: tiles of LDS_TH (16) rows x 32 pixels, grid = min(tiles, 256 * 2); sched_next2: indices 0..2G-1 static"""
+    """conv3x3.hip launch_lds<COUT> / conv_rows.h k_conv3x3_lds: tiles of LDS_TH (16) rows x 32 pixels, grid = min(tiles, 256 * 2); sched_next2: indices 0..2G-1 static"""
     n = _ntiles(B, H, W, 16)
     g = min(n, 512)
     return Split(n, g, 2 * g, 1, 16)
 
 
 def launch_ldsx(B, H, W, cout):
-    """conv3x3.hip launch_ldsx<CIN, COUT> / k_conv3x3_ldsx: tiles of L128_TH (8) rows, units = tiles x NH, NH = ceil(COUT / 128) passes, unit = tile * NH +
+    """conv_rows.h launch_ldsx<CIN, COUT> / k_conv3x3_ldsx: tiles of L128_TH (8) rows, units = tiles x NH, NH = ceil(COUT / 128) passes, unit = tile * NH +
     pass, grid = min(units, 512); sched_next2: indices 0..2G-1 static"""
     nh = -(-cout // 128)
     n = _ntiles(B, H, W, 8) * nh
@@ -67,7 +67,7 @@ def launch_pc(B, H, W, cin):
 
 
 def launch_s2(B, Ho, Wo):
-    """conv3x3.hip launch_s2 / k_conv3x3_s2: OUTPUT tiles of S2_TH (4) rows, grid = min(tiles, 512); sched_next: the first tile static, tickets from G"""
+    """conv_s2.h launch_s2 / k_conv3x3_s2: OUTPUT tiles of S2_TH (4) rows, grid = min(tiles, 512); sched_next: the first tile static, tickets from G"""
     n = _ntiles(B, Ho, Wo, 4)
     g = min(n, 512)
     return Split(n, g, g, 1, 4)
@@ -82,13 +82,13 @@ def launch_direct(B, Ho, Wo, cout):
 
 
 def launch_deconv(B, H, W):
-    """conv3x3.hip pnx_deconv2x2 / k_deconv2x2_64: one 32-pixel input row segment per WAVE, grid = min(ceil(segments / 4), 512); units / grid: segments, waves"""
+    """conv3x3.hip pnx_deconv2x2 / sephead.h k_deconv2x2_64: one 32-pixel input row segment per WAVE, grid = min(ceil(segments / 4), 512); units / grid: segments, waves"""
     n = B * H * -(-W // 32)
     return Split(n, 4 * min(-(-n // 4), 512), None, 1, 1)
 
 
 def launch_sephead(B, H, W):
-    """conv3x3.hip launch_sephead<NBR> / k_sephead_out<NBR, 8>: tiles of 8 rows x 32 pixels, grid = min(tiles, 768), static round-robin"""
+    """sephead.h launch_sephead<NBR> / k_sephead_out<NBR, 8>: tiles of 8 rows x 32 pixels, grid = min(tiles, 768), static round-robin"""
     n = _ntiles(B, H, W, 8)
     return Split(n, min(n, 768), None, 1, 8)
 

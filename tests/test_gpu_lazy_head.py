@@ -1,4 +1,4 @@
-"""GPU: the lazy SepHead (regression branches evaluated only at the decoder's candidate cells, csrc/conv3x3.hip::k_sephead_lazy and
+"""GPU: the lazy SepHead (regression branches evaluated only at the decoder's candidate cells, csrc/sephead_lazy.h::k_sephead_lazy and
 decode.PackedDecoder.launch_lazy) against the dense head: the kernel against torch convolutions over the whole map, the torch evaluator
 against the kernel, and the detections of the lazy pipeline against the dense pipeline (PNX_HEAD_LAZY=0) on the same weights."""
 import os

@@ -1,4 +1,4 @@
-"""GPU: what runs BEHIND the convolutions of the timed inference step (csrc/decode.hip, k_sephead_lazy of csrc/conv3x3.hip, the batched NMS of
+"""GPU: what runs BEHIND the convolutions of the timed inference step (csrc/decode.hip, k_sephead_lazy of csrc/sephead_lazy.h, the batched NMS of
 csrc/iou3d.hip) at the shapes bench.py runs it at -- C2: head map 360 x 360, 12 frames, 6 tasks with 1+2+2+1+2+2 = 10 classes, pre_max 1000, post_max 83
 (configs/pillarnext_b_nusc.yaml) -- against exact or fp64 statements of the same operation.
 

@@ -1,4 +1,4 @@
-"""Host-side weight packers of the HIP convolutions: the fragment orders documented in csrc/conv3x3.hip, checked element by
+"""Host-side weight packers of the HIP convolutions: the fragment orders documented in csrc/conv3x3.hip and csrc/sephead.h, checked element by
 element against an explicit index formula (CPU only; the kernels themselves are covered by tests/test_gpu_dense_ops.py)."""
 import numpy as np
 import pytest
@@ -45,7 +45,7 @@ def test_sephead_pack_rejects_other_shapes():
 
 
 def test_deconv2x2_pack_weights_fragment_order():
-    """ConvTranspose2d weight (Cin, Cout, 2, 2) -> [parity ky*2+kx][cin/16][cout/32][lane = kb*32 + n][8] (csrc/conv3x3.hip::k_deconv2x2_64)."""
+    """ConvTranspose2d weight (Cin, Cout, 2, 2) -> [parity ky*2+kx][cin/16][cout/32][lane = kb*32 + n][8] (csrc/sephead.h::k_deconv2x2_64)."""
     from pillarnext_amd.ops import deconv2x2_pack_weights
 
     ci, co = 64, 64

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the lazy SepHead evaluator (csrc/conv3x3.hip::k_sephead_lazy) at the bench's size: 6 tasks, 8 frames, 360 x 360 maps, 10 classes,
+"""Time the lazy SepHead evaluator (csrc/sephead_lazy.h::k_sephead_lazy) at the bench's size: 6 tasks, 8 frames, 360 x 360 maps, 10 classes,
 pre_max 1000 full lists.  With an instrumented build (PNX_CONV_TIMERS=1) prints the share of wave time per section."""
 import ctypes
 import os

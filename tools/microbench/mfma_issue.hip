@@ -1,4 +1,4 @@
-// mfma_issue.hip -- what limits the tap loop of conv3x3.hip?  The loop body of conv_taps<NR=4> (8 x v_mfma_f32_32x32x16_bf16 per
+// mfma_issue.hip -- what limits the tap loop of conv3x3.hip (conv_taps.h)?  The loop body of conv_taps<NR=4> (8 x v_mfma_f32_32x32x16_bf16 per
 // k-step, 4 ds_read_b128 of B fragments, 2 global_load_dwordx4 of weight fragments) rebuilt piece by piece on synthetic data:
 //   mode bit 0: B fragments from LDS every k-step      bit 1: weight fragments from global memory (L1/L2) every k-step
 //   bit 2: per-step address VALU like the real loop      bit 3: the real epilogue (pack, lane transpose, 128-byte-line stores) after
@@ -13,7 +13,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 constexpr int kTile = 18 * 34 * 8;  // uint4: the 76.5 KiB halo tile of k_conv3x3_lds
 __device__ __forceinline__ int swz(int c) { return (c & 7) ^ ((c >> 3) & 1); }
-// ---- the epilogue helpers of conv3x3.hip, verbatim
+// ---- the epilogue helpers of conv3x3.hip (conv_tile.h), verbatim
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
