@@ -71,7 +71,10 @@ class MaskedBatchNorm(nn.BatchNorm2d):
     eval: affine with running stats.  train: statistics over mask==1 positions only -- of the GLOBAL batch once
     enable_sync() was called (the masked counterpart of SyncBatchNorm, tools/train.py:56): per channel [sum, count] and then
     [sum of squared deviations] are all-reduced with the differentiable collective, so the backward all-reduces the matching
-    gradient sums by itself.  torch's own SyncBatchNorm cannot stand in: it takes (input) only and would average over every
+    gradient sums by itself.  The batch statistics never depend on the buffers: the fused node (_MaskedBNActFn on csrc/masked_bn.hip)
+    sums around the rank's own running mean for precision and re-centres to 0 before its one all-reduce of [sum x | sum x^2 | count],
+    so ranks whose running means differ (no buffer broadcast) still get the statistics of the joint batch; each rank's running
+    statistics then move from their own old values.  torch's own SyncBatchNorm cannot stand in: it takes (input) only and would average over every
     dense cell instead of the active sites."""
 
     sync_group = None
@@ -113,7 +116,8 @@ class _MaskedBNActFn(torch.autograd.Function):
     fp32 tensors per layer alive for the backward (x.float(), the masked products, the normalised map, the ReLU output ...); this node
     keeps x (in its own dtype), the residual (the block's input, alive anyway) and two per-channel vectors, and recomputes the rest:
     the C2 x 4-frame training step went from 106 to 50.5 GiB (profiles/r03_train_step_c2_b4_fp32.log).  SyncBatchNorm mode all-reduces [sum x, count], [sum (x-mu)^2]
-    forward and [sum g, sum g*xhat] backward over the ACTIVE sites of the global batch (dist_utils.all_reduce_sum)."""
+    forward (the HIP path: [sum x | sum x^2 | count] in fp64, once) and [sum g, sum g*xhat] backward over the ACTIVE sites of the global batch
+    (dist_utils.all_reduce_sum); dgamma / dbeta stay the local sums."""
 
     @staticmethod
     def _hip_ok(x, residual, weight=None, bias=None, norm=None):
@@ -142,19 +146,27 @@ class _MaskedBNActFn(torch.autograd.Function):
         dev = x.device
         part = torch.empty((nblk, 2 * C + 1), dtype=torch.float32, device=dev)
         mflat = None if m is None else m.reshape(-1)
-        # statistics around the running mean (identical on every rank: DDP broadcasts the buffers): sum d, sum d^2 with d = x - centre
+        # statistics around THIS rank's running mean: sum d, sum d^2 with d = x - centre, so that the fp32 partial sums carry deviations, not E[x^2]
         rm, rv = norm.running_mean, norm.running_var
         check(L.pnx_masked_bn_stats(ptr(x), dt, ptr(mflat), n, C, ptr(rm), ptr(part), stream_ptr()), "pnx_masked_bn_stats")
         s = torch.empty((2 * C + 1,), dtype=torch.float64, device=dev)       # [sum d | sum d^2 | count]
         check(L.pnx_masked_bn_reduce(ptr(part), nblk, 2 * C + 1, ptr(s), stream_ptr()), "pnx_masked_bn_reduce")
         group = norm.sync_group if getattr(norm, "sync", False) else False
+        center = rm
         if group is not False:
             from .dist_utils import all_reduce_sum
 
+            # the batch statistics must not depend on the buffers, and nothing makes the ranks' running means equal (broadcast_buffers=False, a
+            # per-rank warm-up, a hand-rolled loop): re-centre this rank's sums to centre 0 in fp64 before they are added to the others',
+            # sum x = S1 + n c, sum x^2 = S2 + 2 c S1 + n c^2, and finalize around 0
+            c = rm.double()
+            s[C:2 * C] += 2.0 * c * s[:C] + s[2 * C] * c * c
+            s[:C] += s[2 * C] * c
             all_reduce_sum(s, group)
+            center = None
         vec = torch.empty((4 * C + 1,), dtype=torch.float32, device=dev)
         mean32, invstd32, scale, shift, cnt32 = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:4 * C], vec[4 * C:]
-        check(L.pnx_masked_bn_finalize(ptr(s), C, ptr(rm), ptr(weight), ptr(bias), float(norm.eps), float(norm.momentum), ptr(rm), ptr(rv),
+        check(L.pnx_masked_bn_finalize(ptr(s), C, ptr(center), ptr(weight), ptr(bias), float(norm.eps), float(norm.momentum), ptr(rm), ptr(rv),
                                        ptr(norm.num_batches_tracked), ptr(mean32), ptr(invstd32), ptr(scale), ptr(shift), ptr(cnt32), stream_ptr()),
               "pnx_masked_bn_finalize")
         y = torch.empty_like(x)
