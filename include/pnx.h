@@ -669,7 +669,16 @@ size_t pnx_lazy_decode_bytes(void);
  *   consecutive rows, which one wave per tap accumulates in row order, 16 rows per K step; the P = ceil(n_out / R) fp32 partials
  *   (workspace = pnx_sp3_wgrad_workspace_bytes = P * T * cin * cout floats, at least 256 bytes) are added in index order by a second
  *   kernel.  No floating-point atomics: bit-identical run to run.
- * pnx_sp3_dense_backward: dfeat (n, channels)[row][c] = dout[b][c*D + z][y][x], the gradient of pnx_sp3_dense. */
+ * pnx_sp3_dense_backward: dfeat (n, channels)[row][c] = dout[b][c*D + z][y][x], the gradient of pnx_sp3_dense.
+ * Inference in 16 bits (dtype = PNX_BF16 or PNX_F16; csrc/sparse3d_half.h).  Rows are stored in that type with the channel count rounded up to
+ * a multiple of 8 (cin_pad, cout_pad, channels_pad: anything else is PNX_ERR_INVALID), pad columns exactly zero, 16-byte aligned.
+ * pnx_sp3_conv_h: pnx_sp3_conv on such rows: x (n_in, cin_pad), residual / y (n_out, cout_pad), the same map; v_mfma_f32_16x16x32 with fp32
+ *   accumulators over K = (tap, padded channel), shift (fp32, cout) + residual + ReLU in fp32, then ONE rounding to nearest even; every
+ *   column of y is written, the pad columns with zero.  A map entry < 0 or >= n_in contributes zero.  Bit-identical run to run.  w_packed is
+ *   pnx_sp3_packed_weight_halfs(taps, cin, cout) elements in fragment order (S, ceil(cout / 16), 64, 8), S = ceil(taps * cin_pad / 32):
+ *   element e of lane l of tile j of step s = w[tap][c][16 j + (l & 15)] (BatchNorm scale folded in fp32, rounded once) with
+ *   32 s + 8 (l >> 4) + e = tap * cin_pad + c, zero past the last tap / channel.  cin, cout <= 144, taps <= 27 (else 0 / PNX_ERR_UNSUPPORTED).
+ * pnx_sp3_dense_h: pnx_sp3_dense from rows (n, channels_pad) of `dtype`; out stays fp32. */
 size_t pnx_sp3_index_bytes(int32_t batch, const int32_t* grid3_host);
 int pnx_sp3_index_build(const int32_t* coords, int64_t n, int32_t batch, const int32_t* grid3_host, void* index, size_t index_bytes, int32_t* row_of_rank,
                         int32_t* count, pnx_stream_t stream);
@@ -689,6 +698,11 @@ int pnx_sp3_conv_train(const float* x, int64_t n_in, int32_t cin, const int32_t*
                        const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream);
 int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* out,
                   pnx_stream_t stream);
+size_t pnx_sp3_packed_weight_halfs(int32_t taps, int32_t cin, int32_t cout);
+int pnx_sp3_conv_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const int32_t* map, int64_t n_out, int32_t taps, const void* w_packed,
+                   const float* shift, const void* residual, int32_t relu, void* y, int32_t cout, int32_t cout_pad, int32_t dtype, pnx_stream_t stream);
+int pnx_sp3_dense_h(const void* feat, int32_t dtype, const int32_t* coords, int64_t n, int32_t channels, int32_t channels_pad, int32_t batch,
+                    const int32_t* grid3_host, float* out, pnx_stream_t stream);
 int pnx_sp3_transpose_map(const int32_t* map, int64_t n_out, int32_t taps, int64_t n_in, int32_t* tmap, pnx_stream_t stream);
 size_t pnx_sp3_wgrad_workspace_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout);
 int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, int32_t cout, const int32_t* map, int64_t n_out, int32_t taps, float* dw,

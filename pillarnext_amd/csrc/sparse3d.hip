@@ -5,6 +5,7 @@
 //   pnx_sp3_neighbor_map  (N_out, T) input row per output site and tap, -1 where the neighbour is inactive
 //   pnx_sp3_conv          gather-GEMM on the fp32 matrix cores + folded BN shift (+ residual) (+ ReLU)
 //   pnx_sp3_dense         rows -> zero-initialised (B, C*D, H, W), channel c*D + d (x.dense().view(B, C*D, H, W), :67-71)
+//   pnx_sp3_conv_h, pnx_sp3_dense_h   the same two on bf16 / fp16 rows and the 16-bit matrix cores, inference only (sparse3d_half.h)
 // and, for training:
 //   pnx_sp3_transpose_map   tmap (N_in, T): tmap[map[o][t]][t] = o, -1 elsewhere -- the data gradient is pnx_sp3_conv_train on dy, tmap and w^T
 //   pnx_sp3_wgrad           dw[co][t][ci] = sum_o dy[o][co] * x[map[o][t]][ci]: split-K gather-GEMM, fp32 partials added in a fixed order
@@ -25,6 +26,8 @@
 // one after the other (the chunk's map, x and dy rows stay in cache across the taps), a wave accumulates MT x NT tiles of 16 x 16 over the
 // chunk in row order -- a K step of 16 rows none of which has the tap costs no MFMA -- and writes them to partial c; k_sp3_wgrad_sum adds
 // the partials in index order.  No floating-point atomics: the result does not depend on timing.
+#include <algorithm>
+
 #include "pnx_common.h"
 #include "pnx_scan.h"
 
@@ -273,6 +276,8 @@ __global__ __launch_bounds__(kBlock) void k_sp3_dense(const float* __restrict__ 
 }
 
 unsigned sp3_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+#include "sparse3d_half.h"  // the 16-bit inference form: k_sp3_conv_h, k_sp3_dense_h and their launchers
 
 // tmap[map[o][t]][t] = o: for one input row and tap there is at most one output row (q = (p + pad - o) / s), so no two threads meet
 __global__ __launch_bounds__(kBlock) void k_sp3_tmap(const int32_t* __restrict__ map, int64_t n_out, int T, int64_t n_in, int32_t* __restrict__ tmap) {
@@ -582,6 +587,58 @@ int pnx_sp3_dense(const float* feat, const int32_t* coords, int64_t n, int32_t c
   PNX_CHECK_HIP(hipMemsetAsync(out, 0, bytes, st));
   if (n == 0) return PNX_OK;
   k_sp3_dense<<<sp3_blocks(n * channels), kBlock, 0, st>>>(feat, coords, n, channels, g, out);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_sp3_packed_weight_halfs(int32_t taps, int32_t cin, int32_t cout) {
+  if (taps < 1 || taps > 27 || cin < 1 || cin > 144 || cout < 1 || cout > 144) return 0;
+  const int chunks = taps * ((cin + 7) / 8);
+  return (size_t)((chunks + 3) / 4) * ((cout + 15) / 16) * 512;
+}
+
+int pnx_sp3_conv_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const int32_t* map, int64_t n_out, int32_t taps, const void* w_packed,
+                   const float* shift, const void* residual, int32_t relu, void* y, int32_t cout, int32_t cout_pad, int32_t dtype, pnx_stream_t stream) {
+  PNX_REQUIRE(dtype == PNX_BF16 || dtype == PNX_F16, PNX_ERR_UNSUPPORTED, "pnx_sp3_conv_h: dtype %d (PNX_BF16 or PNX_F16)", dtype);
+  PNX_REQUIRE(cin >= 1 && cin <= 144 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
+              "pnx_sp3_conv_h: %d -> %d channels over %d taps (channels 1..144, taps 1..27)", cin, cout, taps);
+  PNX_REQUIRE(cin_pad == ((cin + 7) & ~7) && cout_pad == ((cout + 7) & ~7), PNX_ERR_INVALID,
+              "pnx_sp3_conv_h: padded channel counts %d / %d for %d -> %d channels (each the count rounded up to a multiple of 8)", cin_pad, cout_pad, cin,
+              cout);
+  PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "pnx_sp3_conv_h: %lld -> %lld rows", (long long)n_in,
+              (long long)n_out);
+  if (n_out == 0) return PNX_OK;
+  PNX_REQUIRE(map && w_packed && shift && y && (n_in == 0 || x), PNX_ERR_INVALID, "pnx_sp3_conv_h: null pointer");
+  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)residual | (uintptr_t)y) & 15) == 0, PNX_ERR_INVALID,
+              "pnx_sp3_conv_h: x, w_packed, residual and y must be 16-byte aligned");
+  const int cpc = cin_pad / 8, S = (taps * cpc + 3) / 4, nt = (cout + 15) / 16;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PNX_BF16)
+    sp3_conv_h_nt<PNX_BF16>(nt, st, x, n_in, cpc, map, n_out, taps, w_packed, S, shift, residual, relu, y, cout, cout_pad);
+  else
+    sp3_conv_h_nt<PNX_F16>(nt, st, x, n_in, cpc, map, n_out, taps, w_packed, S, shift, residual, relu, y, cout, cout_pad);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_dense_h(const void* feat, int32_t dtype, const int32_t* coords, int64_t n, int32_t channels, int32_t channels_pad, int32_t batch,
+                    const int32_t* grid3_host, float* out, pnx_stream_t stream) {
+  Sp3Grid g;
+  int rc = sp3_grid(batch, grid3_host, &g);
+  if (rc != PNX_OK) return rc;
+  PNX_REQUIRE(dtype == PNX_BF16 || dtype == PNX_F16, PNX_ERR_UNSUPPORTED, "pnx_sp3_dense_h: dtype %d (PNX_BF16 or PNX_F16)", dtype);
+  PNX_REQUIRE(n >= 0 && channels >= 1 && channels_pad == ((channels + 7) & ~7), PNX_ERR_INVALID,
+              "pnx_sp3_dense_h: %lld rows of %d channels padded to %d (the count rounded up to a multiple of 8)", (long long)n, channels, channels_pad);
+  const size_t bytes = (size_t)g.B * channels * g.D * g.H * g.W * sizeof(float);
+  if (bytes == 0) return PNX_OK;  // a batch of 0 samples
+  PNX_REQUIRE(out != nullptr && (n == 0 || (feat && coords && ((uintptr_t)coords & 15) == 0)), PNX_ERR_INVALID, "pnx_sp3_dense_h: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  PNX_CHECK_HIP(hipMemsetAsync(out, 0, bytes, st));
+  if (n == 0) return PNX_OK;
+  if (dtype == PNX_BF16)
+    k_sp3_dense_h<PNX_BF16><<<sp3_blocks(n * channels), kBlock, 0, st>>>(feat, coords, n, channels, channels_pad, g, out);
+  else
+    k_sp3_dense_h<PNX_F16><<<sp3_blocks(n * channels), kBlock, 0, st>>>(feat, coords, n, channels, channels_pad, g, out);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

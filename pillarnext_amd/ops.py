@@ -920,6 +920,85 @@ def sp3_dense_backward(dout, coords, channels):
     return dfeat
 
 
+# 16-bit inference form (csrc/sparse3d_half.h): rows in bf16 / fp16 with the channel count padded to a multiple of 8, pad columns zero
+def _cpad(c):
+    return (int(c) + 7) // 8 * 8
+
+
+def _sp3_half(dtype, what):
+    if dtype not in _HALF:
+        raise PnxError(f"{what}: torch.bfloat16 or torch.float16, got {dtype}")
+    return _DT[dtype]
+
+
+def sp3_rows_h(x, dtype):
+    """(N, C) fp32 rows -> (N, round_up(C, 8)) rows of `dtype`: rounded once to nearest even, pad columns zero."""
+    _sp3_half(dtype, "sp3_rows_h")
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise PnxError("sp3_rows_h: x must be (N, C) fp32")
+    out = torch.zeros((x.shape[0], _cpad(x.shape[1])), dtype=dtype, device=x.device)
+    out[:, : x.shape[1]] = x.to(dtype)
+    return out
+
+
+def sp3_pack_weight_h(w, dtype):
+    """(Cout, kd, kh, kw, Cin) fp32 (BN scale folded in) -> (S, ceil(Cout / 16), 64, 8) of `dtype`, the fragment order of pnx_sp3_conv_h: K runs
+    over (tap, channel padded to cpad = round_up(Cin, 8)) in S = ceil(T * cpad / 32) steps of 32, and element e of lane l of tile j of step s is
+    w[16 j + (l & 15)][tap][c] with 32 s + 8 (l >> 4) + e = tap * cpad + c, zero past the last tap / channel.  Rounded once (nearest even) from
+    fp32.  Runs on CPU tensors too."""
+    _sp3_half(dtype, "sp3_pack_weight_h")
+    co, ci = w.shape[0], w.shape[-1]
+    T = w.shape[1] * w.shape[2] * w.shape[3]
+    cp, nt = _cpad(ci), (co + 15) // 16
+    S = (T * cp // 8 + 3) // 4
+    if lib().pnx_sp3_packed_weight_halfs(T, ci, co) != S * nt * 512:
+        raise PnxError(f"sp3_pack_weight_h: no packing for {tuple(w.shape)}")
+    wk = torch.zeros((S * 32, nt * 16), dtype=torch.float32, device=w.device)
+    wk[: T * cp].view(T, cp, nt * 16)[:, :ci, :co] = w.float().reshape(co, T, ci).permute(1, 2, 0)
+    # (s, kk, e, j, r) -> (s, j, lane = kk * 16 + r, e)
+    return wk.view(S, 4, 8, nt, 16).permute(0, 3, 1, 4, 2).reshape(S, nt, 64, 8).to(dtype).contiguous()
+
+
+def sp3_conv_h(x, nbmap, w_packed, shift, cin, cout, residual=None, relu=True):
+    """pnx_sp3_conv_h: x (N_in, round_up(cin, 8)) bf16 / fp16 padded rows (sp3_rows_h, or a previous layer's output), nbmap (N_out, T) int32,
+    w_packed from sp3_pack_weight_h in x's dtype, shift (cout,) fp32 -> (N_out, round_up(cout, 8)) in x's dtype, pad columns zero."""
+    for t, name in ((x, "x"), (nbmap, "nbmap"), (w_packed, "w_packed"), (shift, "shift")):
+        _need_cuda(t, name)
+    dt = _sp3_half(x.dtype, "sp3_conv_h")
+    if w_packed.dtype != x.dtype or shift.dtype != torch.float32 or nbmap.dtype != torch.int32 or x.dim() != 2 or nbmap.dim() != 2:
+        raise PnxError("sp3_conv_h: features and weights of one 16-bit dtype, fp32 shift, int32 map")
+    n_out, T = nbmap.shape
+    ci, co = int(cin), int(cout)
+    if x.shape[1] != _cpad(ci):
+        raise PnxError(f"sp3_conv_h: rows of {x.shape[1]} columns for {ci} channels (padded rows have {_cpad(ci)})")
+    n = lib().pnx_sp3_packed_weight_halfs(T, ci, co)
+    if n == 0 or w_packed.numel() != n or shift.numel() < co:
+        raise PnxError(f"sp3_conv_h: packed weight {tuple(w_packed.shape)} does not fit {T} taps x {ci} -> {co}")
+    if residual is not None:
+        _need_cuda(residual, "residual")
+        if residual.dtype != x.dtype or tuple(residual.shape) != (n_out, _cpad(co)):
+            raise PnxError("sp3_conv_h: residual must be (N_out, round_up(cout, 8)) of the input's dtype")
+    y = torch.empty((n_out, _cpad(co)), dtype=x.dtype, device=x.device)
+    check(lib().pnx_sp3_conv_h(ptr(x), x.shape[0], ci, x.shape[1], ptr(nbmap), n_out, T, ptr(w_packed), ptr(shift), ptr(residual), 1 if relu else 0,
+                               ptr(y), co, y.shape[1], dt, stream_ptr()), "pnx_sp3_conv_h")
+    return y
+
+
+def sp3_dense_h(feat, coords, batch, grid, channels):
+    """pnx_sp3_dense_h: padded bf16 / fp16 rows (N, round_up(channels, 8)) -> (batch, channels*D, H, W) fp32, channel c*D + d, zero elsewhere."""
+    _need_coords(coords)
+    _need_cuda(feat, "feat")
+    dt = _sp3_half(feat.dtype, "sp3_dense_h")
+    C = int(channels)
+    if feat.dim() != 2 or feat.shape[0] != coords.shape[0] or feat.shape[1] != _cpad(C):
+        raise PnxError("sp3_dense_h: feat must be (N, round_up(channels, 8)) with one row per coordinate")
+    D, H, W = (int(g) for g in grid)
+    out = torch.empty((int(batch), C * D, H, W), dtype=torch.float32, device=feat.device)
+    check(lib().pnx_sp3_dense_h(ptr(feat), dt, ptr(coords), coords.shape[0], C, feat.shape[1], int(batch), _i3(grid), ptr(out), stream_ptr()),
+          "pnx_sp3_dense_h")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- label assignment
 _ASSIGN_OUT = (("hm", torch.float32), ("anno_box", torch.float32), ("ind", torch.int64), ("mask", torch.uint8), ("cat", torch.int64),
                ("gt_boxes", torch.float32))

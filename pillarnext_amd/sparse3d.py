@@ -15,6 +15,10 @@ That folded path runs in eval mode when no gradient is wanted.  In training mode
 features require one, every layer is conv (SparseConvFunction: pnx_sp3_conv_train with the plain weight; backward = the same on the transposed
 map for dx, pnx_sp3_wgrad for dw) -> the module's own nn.BatchNorm1d on the (N, C) rows -> ReLU on torch ops, over the same index, output sets
 and neighbour maps, which forward and backward share.
+
+use_half_precision(dtype) moves the folded eval path onto bf16 / fp16 rows and the 16-bit matrix cores (pnx_sp3_conv_h): the fp32 input features
+are rounded once, every layer reads and writes padded 16-bit rows over the same index, output sets and neighbour maps, and the dense output
+stays fp32.  The default, training and any call that wants gradients are untouched.
 """
 import math
 
@@ -136,12 +140,13 @@ class SparseDenseFunction(torch.autograd.Function):
         return ops.sp3_dense_backward(dout, ctx.saved_tensors[0], ctx.channels), None, None, None
 
 
-def _fold(conv, bn):
-    """Eval BatchNorm folded into the conv: packed weight (BN scale baked in) and per-channel shift, fp32."""
+def _fold(conv, bn, dtype=None):
+    """Eval BatchNorm folded into the conv: packed weight (BN scale baked in) and per-channel shift, fp32.  dtype (bf16 / fp16): the weight in the
+    16-bit path's fragment order instead -- the scale is still folded in fp32, the product rounded once; the shift stays fp32."""
     a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
     w = conv.weight.detach().float() * a.view(-1, 1, 1, 1, 1)
     shift = (bn.bias.detach().float() - bn.running_mean.detach().float() * a).contiguous()
-    return ops.sp3_pack_weight(w), shift
+    return (ops.sp3_pack_weight(w) if dtype is None else ops.sp3_pack_weight_h(w, dtype)), shift
 
 
 class SparseResNet3D(nn.Module):
@@ -163,22 +168,35 @@ class SparseResNet3D(nn.Module):
         self.mapping = SparseConv3dBlock(c, out_channels, kernel_size=1, stride=1, use_subm=True)
         self.extra_conv = nn.Sequential(SparseConv3d(c, c, (3, 1, 1), (2, 1, 1), 0), nn.BatchNorm1d(c, eps=1e-3, momentum=0.01), nn.ReLU())
         self.profile = None  # a list: every phase of the next forwards appends (name, end event) -- tools/bench_voxel18.py
+        self.half_dtype = None  # None: fp32; torch.bfloat16 / float16: the folded eval path runs in 16 bits (use_half_precision)
+
+    def use_half_precision(self, dtype=torch.bfloat16):
+        """Inference on 16-bit rows and the 16-bit matrix cores (pnx_sp3_conv_h), as MVFFeatureNet.use_hip_convs is for the view nets: eval-mode
+        forwards that want no gradient round the fp32 input features once, run every layer in `dtype` (fp32 accumulation, BN shift, residual and
+        ReLU in fp32, one rounding per layer) and return the fp32 dense map; forward_sparse then returns its features in `dtype`.  Training and any
+        call that wants gradients keep the fp32 autograd path.  dtype=None switches back to fp32.
+        torch.float16 has 5 exponent bits: activations above 65504 become inf, which real checkpoints can reach -- bf16, the default, keeps fp32's
+        range at 8 bits of precision."""
+        if dtype is not None and dtype not in ops._HALF:
+            raise PnxError("use_half_precision: torch.bfloat16, torch.float16 or None")
+        self.half_dtype = dtype
+        return self
 
     # ------------------------------------------------------------------------------------------ plan
-    def _folded(self):
-        """Packed weights and shifts, folded once per parameter version (as mvf_encoder's view nets are)."""
-        f = self.__dict__.get("_folded_cache")
+    def _folded(self, dtype=None):
+        """Packed weights and shifts, folded once per parameter version and element type (as mvf_encoder's view nets are)."""
+        cache = self.__dict__.setdefault("_folded_cache", {})  # dtype (None: fp32) -> (parameter version, layers)
+        f = cache.get(dtype)
         if f is None or f[0] != _params_version(self):
             layers = {}
             for i, seq in enumerate(self.blocks):
-                layers[f"blocks.{i}.0"] = _fold(seq[0].conv, seq[0].norm)
+                layers[f"blocks.{i}.0"] = _fold(seq[0].conv, seq[0].norm, dtype)
                 for j, blk in enumerate(seq[1:], 1):
-                    layers[f"blocks.{i}.{j}.block1"] = _fold(blk.block1.conv, blk.block1.norm)
-                    layers[f"blocks.{i}.{j}.conv2"] = _fold(blk.conv2, blk.norm2)
-            layers["extra_conv"] = _fold(self.extra_conv[0], self.extra_conv[1])
-            layers["mapping"] = _fold(self.mapping.conv, self.mapping.norm)
-            f = (_params_version(self), layers)
-            self.__dict__["_folded_cache"] = f
+                    layers[f"blocks.{i}.{j}.block1"] = _fold(blk.block1.conv, blk.block1.norm, dtype)
+                    layers[f"blocks.{i}.{j}.conv2"] = _fold(blk.conv2, blk.norm2, dtype)
+            layers["extra_conv"] = _fold(self.extra_conv[0], self.extra_conv[1], dtype)
+            layers["mapping"] = _fold(self.mapping.conv, self.mapping.norm, dtype)
+            f = cache[dtype] = (_params_version(self), layers)
         return f[1]
 
     def _tick(self, name):
@@ -232,13 +250,26 @@ class SparseResNet3D(nn.Module):
             self._tick(name + ".rest")
             return y
         wp, shift = folded[name]
-        y = ops.sp3_conv(x, m, wp, shift, conv.out_channels, residual=residual, relu=True)
+        if wp.dtype != torch.float32:  # the 16-bit plan: padded 16-bit rows in and out
+            y = ops.sp3_conv_h(x, m, wp, shift, conv.in_channels, conv.out_channels, residual=residual, relu=True)
+        else:
+            y = ops.sp3_conv(x, m, wp, shift, conv.out_channels, residual=residual, relu=True)
         self._tick(name + ".conv")
         return y
 
     def forward_sparse(self, pillar_features, coors, input_shape, batch_size=None):
-        """The active sets: [(coords (N, 4) int32, features (N, C) fp32, grid (D, H, W))] after stage 0, 1, ..., extra_conv and mapping."""
-        return self._sets(pillar_features, coors, input_shape, batch_size, self._check(pillar_features, coors))
+        """The active sets: [(coords (N, 4) int32, features (N, C) fp32, grid (D, H, W))] after stage 0, 1, ..., extra_conv and mapping.
+        Under use_half_precision (and no gradient wanted) the features are in the 16-bit type, cut to the true channel count."""
+        diff = self._check(pillar_features, coors)
+        sets = self._sets(pillar_features, coors, input_shape, batch_size, diff)
+        if self._half(diff) is None:
+            return sets
+        ch = [*self._num_filters, self._num_filters[-1], self.mapping.conv.out_channels]
+        return [(c, x[:, :k], g) for (c, x, g), k in zip(sets, ch)]
+
+    def _half(self, diff):
+        """The element type of this forward's rows: the 16-bit type set by use_half_precision on the folded eval path, else None (fp32)."""
+        return None if diff else self.half_dtype
 
     def _sets(self, pillar_features, coors, input_shape, batch_size, diff):
         if batch_size is None:
@@ -260,7 +291,11 @@ class SparseResNet3D(nn.Module):
             if not distinct:
                 raise PnxError("SparseResNet3D: coords hold duplicate sites")
         self._tick("input.index")
-        folded = None if diff else self._folded()
+        half = self._half(diff)
+        folded = None if diff else self._folded(half)
+        if half is not None:
+            x = ops.sp3_rows_h(x, half)  # the one conversion of the input: rounded, channels padded to a multiple of 8
+            self._tick("input.rows")
         sets = []
         for i, seq in enumerate(self.blocks):
             conv = seq[0].conv
@@ -297,6 +332,8 @@ class SparseResNet3D(nn.Module):
         coords, x, grid = self._sets(pillar_features, coors, input_shape, batch_size, diff)[-1]
         if diff:
             out = SparseDenseFunction.apply(x, coords, batch_size, grid)
+        elif x.dtype != torch.float32:  # padded 16-bit rows (use_half_precision)
+            out = ops.sp3_dense_h(x, coords, batch_size, grid, self.mapping.conv.out_channels)
         else:
             out = ops.sp3_dense(x, coords, batch_size, grid)
         self._tick("dense")

@@ -3,7 +3,10 @@
 
 Prints the active sites per stage, ms per layer from HIP events (index, neighbour map and convolution separately), backbone ms per frame,
 peak memory, and -- for context -- the same backbone as a torch statement on the GPU (fp32 gather + matmul + index_add_ per tap, neighbours
-from torch.unique / searchsorted).  Usage: python tools/bench_voxel18.py [--frames 4] [--iters 5]
+from torch.unique / searchsorted).  Usage: python tools/bench_voxel18.py [--frames 4] [--iters 5] [--dtype fp32|bf16|fp16]
+
+--dtype bf16 / fp16 adds an arm that runs the backbone under use_half_precision(dtype): the two arms alternate forward by forward in one process,
+each prints its own per-layer table, and the convolution phases are compared by the A/B rule (difference against three times the larger spread).
 
 --train times forward + backward of the backbone in training mode instead (loss = sum of the dense output x a fixed random tensor): ms per step,
 the split into forward convolutions / data gradients / weight gradients / everything else (index, maps, BatchNorm, ReLU, residual, dense: torch
@@ -24,6 +27,7 @@ from pillarnext_amd import synth  # noqa: E402
 from pillarnext_amd.sparse3d import SparseResNet3D  # noqa: E402
 from pillarnext_amd.voxel_encoder import VoxelFeatureNet  # noqa: E402
 
+HALF = {"bf16": torch.bfloat16, "fp16": torch.float16}
 NUSC = dict(voxel_size=[0.075, 0.075, 0.2], pc_range=[-50.4, -50.4, -5.0, 50.4, 50.4, 3.0])
 
 
@@ -181,6 +185,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32",
+                    help="bf16 / fp16: time SparseResNet3D.use_half_precision as well, its forwards alternating with the fp32 ones in this run")
     ap.add_argument("--train", action="store_true", help="time forward + backward in training mode")
     ap.add_argument("--torch-frames", type=int, default=0, help="--train: frames of the torch statement (default: --frames)")
     a = ap.parse_args()
@@ -202,34 +208,54 @@ def main():
         sets = bb.forward_sparse(feats, coords, grid, B)
         names = ["stage0", "stage1", "stage2", "stage3", "extra_conv", "mapping"]
         print("active sites:", ", ".join(f"{n} {int(s[0].shape[0])} (grid {s[2]})" for n, s in zip(names, sets)))
-        for _ in range(2):
-            bb(feats, coords, grid, B)
+        arms = [("fp32", None)] + ([(a.dtype, HALF[a.dtype])] if a.dtype != "fp32" else [])
+        for _, dt in arms:
+            bb.use_half_precision(dt)
+            for _ in range(2):
+                bb(feats, coords, grid, B)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
-        per = collections.defaultdict(float)
-        walls = []
-        for _ in range(a.iters):
-            bb.profile = []
-            t0 = time.perf_counter()
-            bb(feats, coords, grid, B)
-            torch.cuda.synchronize()
-            walls.append((time.perf_counter() - t0) * 1e3)
-            ev = bb.profile
-            for (_, e0), (name, e1) in zip(ev[:-1], ev[1:]):
-                per[name] += e0.elapsed_time(e1) / a.iters
-            bb.profile = None
+        per = {n: collections.defaultdict(float) for n, _ in arms}
+        walls, convs = {n: [] for n, _ in arms}, {n: [] for n, _ in arms}
+        for _ in range(a.iters):  # the arms alternate: both see the same clocks and the same allocator state
+            for arm, dt in arms:
+                bb.use_half_precision(dt)
+                bb.profile = []
+                t0 = time.perf_counter()
+                bb(feats, coords, grid, B)
+                torch.cuda.synchronize()
+                walls[arm].append((time.perf_counter() - t0) * 1e3)
+                ev = bb.profile
+                conv = 0.0
+                for (_, e0), (name, e1) in zip(ev[:-1], ev[1:]):
+                    ms = e0.elapsed_time(e1)
+                    per[arm][name] += ms / a.iters
+                    conv += ms if name.endswith(".conv") else 0.0
+                convs[arm].append(conv)
+                bb.profile = None
+        bb.use_half_precision(None)
         peak = torch.cuda.max_memory_allocated() - base
-        print("ms per layer (HIP events, mean of %d):" % a.iters)
-        kinds = collections.defaultdict(float)
-        for name, ms in per.items():
-            print(f"  {name:28s} {ms:8.3f}")
-            kinds[name.rsplit(".", 1)[-1]] += ms
-        print("by phase:", ", ".join(f"{k} {v:.3f} ms" for k, v in kinds.items()))
-        walls.sort()
-        print(f"backbone: {walls[len(walls) // 2]:.2f} ms per batch (median wall), {walls[len(walls) // 2] / B:.2f} ms per frame; "
-              f"event sum {sum(per.values()):.2f} ms")
-        print(f"peak memory above inputs: {peak / 2**30:.2f} GiB")
+        for arm, _ in arms:
+            w = sorted(walls[arm])
+            if len(arms) > 1:
+                print(f"## arm {arm}")
+            print("ms per layer (HIP events, mean of %d):" % a.iters)
+            kinds = collections.defaultdict(float)
+            for name, ms in per[arm].items():
+                print(f"  {name:28s} {ms:8.3f}")
+                kinds[name.rsplit(".", 1)[-1]] += ms
+            print("by phase:", ", ".join(f"{k} {v:.3f} ms" for k, v in kinds.items()))
+            print(f"conv phase per iteration: min {min(convs[arm]):.3f}, max {max(convs[arm]):.3f} ms (spread {max(convs[arm]) - min(convs[arm]):.3f})")
+            print(f"backbone: {w[len(w) // 2]:.2f} ms per batch (median wall; min {w[0]:.2f}, max {w[-1]:.2f}), {w[len(w) // 2] / B:.2f} ms per frame; "
+                  f"event sum {sum(per[arm].values()):.2f} ms")
+        if len(arms) > 1:
+            (n0, _), (n1, _) = arms
+            m0, m1 = sum(convs[n0]) / a.iters, sum(convs[n1]) / a.iters
+            spread = max(max(convs[n]) - min(convs[n]) for n in (n0, n1))
+            print(f"conv phase {n0} {m0:.3f} ms vs {n1} {m1:.3f} ms: difference {m0 - m1:.3f} ms = {(m0 - m1) / max(spread, 1e-9):.1f} x the larger spread "
+                  f"({spread:.3f} ms; the A/B rule asks for more than 3 x), ratio {m0 / m1:.2f}")
+        print(f"peak memory above inputs{' (all arms in the process)' if len(arms) > 1 else ''}: {peak / 2**30:.2f} GiB")
         torch_backbone(bb, feats, coords, tuple(int(g) for g in grid))
         torch.cuda.synchronize()
         tw = []
