@@ -219,23 +219,24 @@ __global__ __launch_bounds__(256) void k_gather_kept(const float* __restrict__ b
   o[9] = scores[src];
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
+// ---------------------------------------------------------------------------------------------------------------- exact radix select
 // Segmented top-k: the first pre_max candidates of every (sample, class) segment in descending-score order (box_torch_ops.py:13-15:
-// scores.sort(descending) + [:pre_maxsize]), ties in ascending cell order (what a stable sort of the key array gives) -- WITHOUT
-// sorting the 6 M keys of a frame batch, of which a few percent are valid: a 4096-bin score histogram per segment finds the score
-// bin that the pre_max-th candidate falls into, the candidates at or above that bin (pre_max + at most one bin's population) are
-// collected per segment and sorted in LDS.
-constexpr int kBins = 4096, kSortCap = 8192;
-
-__device__ __forceinline__ int score_bin(uint32_t low32) {
-  const uint32_t bits = 0xFFFFFFFFu - low32;  // fp32 bits of a score in (0, 1]
-  const uint32_t base = 0x3D800000u;          // 2^-4; everything below shares bin 0 (monotone clamp)
-  const uint32_t d = bits > base ? (bits - base) >> 13 : 0u;
-  return (int)(d < (uint32_t)kBins ? d : (uint32_t)kBins - 1u);
-}
+// scores.sort(descending) + [:pre_maxsize]), ties in ascending cell order (what a stable sort of the key array gives) -- WITHOUT sorting
+// the 6 M keys of a frame batch, of which a few percent are valid, and without a weak spot.  Binning the scores, collecting everything at or
+// above the bin of the pre_max-th candidate and sorting that is fine for a trained head (a few thousand candidates) and a disaster for a
+// freshly initialised one, where half of all cells pass the score threshold and tens of thousands share one bf16-quantised score: measured
+// 6.4 ms there, against 0.87 ms for sorting all keys.  So the k-th smallest COMPOSITE  C = (low 32 key bits = ~score bits) << 32 | key index
+// of every segment is found exactly, most significant digit first (11 + 11 + 10 bits of the score, then -- only while a segment still has
+// more ties than it needs -- 11 + 11 + 10 bits of the index): composites are unique, so "C <= threshold" selects exactly min(k, valid) keys,
+// ties resolved by ascending index like a stable sort.
+// A pass = one histogram launch (a workgroup owns 16 384 consecutive keys; they belong to at most a handful of segments, so it
+// histograms into 4 LDS slots of 2 048 bins -- no global atomics -- and writes its rows; keys of a fifth segment fall back to global
+// atomics) + one select launch (per segment: sum the rows of its slots, find the digit, narrow the prefix).  Segments finish early: fewer
+// than k valid keys (every pass after the first is then a no-op for them) or a digit bucket that is needed completely.
+constexpr int kRsBins = 2048, kRsSlots = 4, kRsChunk = 16384, kRsThreads = 512, kRsMaxK = 4096;
 
 // Wave-aggregated counter update: lanes that hit the same counter are served by ONE device atomic (same-address atomics serialise at
-// ~13 ns each: a freshly initialised head puts half of all cells into the same score bin -- 3 M atomics on one word = 39 ms).
+// ~13 ns each: on a freshly initialised head half of all cells are candidates of a handful of lists -- 3 M atomics on one word = 39 ms).
 // Returns the lane's position (old value + its rank among the lanes of its group); inactive lanes get 0.
 __device__ __forceinline__ uint32_t wave_agg_add(uint32_t* __restrict__ counters, uint32_t index, bool active) {
   const int lane = threadIdx.x & 63;
@@ -252,83 +253,6 @@ __device__ __forceinline__ uint32_t wave_agg_add(uint32_t* __restrict__ counters
     todo &= ~grp;
   }
   return pos;
-}
-
-__global__ __launch_bounds__(256) void k_topk_hist(const unsigned long long* __restrict__ keys, int64_t n, uint32_t* __restrict__ hist) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const unsigned long long k = i < n ? keys[i] : ~0ULL;
-  const bool ok = k != ~0ULL;
-  wave_agg_add(hist, ok ? (uint32_t)(k >> 32) * kBins + (uint32_t)score_bin((uint32_t)k) : 0u, ok);
-}
-
-// one block per segment: threshold bin tb[s] = the highest bin b with count(bins >= b) >= pre_max (0 if the segment has fewer
-// candidates), need[s] = count(bins >= tb[s])
-__global__ __launch_bounds__(256) void k_topk_select(const uint32_t* __restrict__ hist, int pre_max, int32_t* __restrict__ tb, uint32_t* __restrict__ need) {
-  __shared__ uint32_t s_sum[256];
-  __shared__ int s_tb;
-  const int s = blockIdx.x, t = threadIdx.x;
-  const uint32_t* h = hist + (size_t)s * kBins;
-  uint32_t loc[16], tot = 0;  // thread t owns bins [16t, 16t+16)
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    loc[k] = h[16 * t + k];
-    tot += loc[k];
-  }
-  s_sum[t] = tot;
-  if (t == 0) s_tb = 0;
-  __syncthreads();
-  uint32_t above = 0;  // candidates in the bins of higher threads
-  for (int q = t + 1; q < 256; q++) above += s_sum[q];
-  __syncthreads();
-  // walking down from the top, the first bin where the running count reaches pre_max lies in exactly one thread's range
-  if (above < (uint32_t)pre_max && above + tot >= (uint32_t)pre_max) {
-    uint32_t run = above;
-    for (int k = 15; k >= 0; k--) {
-      run += loc[k];
-      if (run >= (uint32_t)pre_max) {
-        s_tb = 16 * t + k;
-        break;
-      }
-    }
-  }
-  __syncthreads();
-  const int b = s_tb;
-  uint32_t part = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    if (16 * t + k >= b) part += loc[k];
-  __syncthreads();
-  s_sum[t] = part;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t n = 0;
-    for (int q = 0; q < 256; q++) n += s_sum[q];
-    tb[s] = b;
-    need[s] = n;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_topk_offsets(const uint32_t* __restrict__ need, int S, uint32_t* __restrict__ base, uint32_t* __restrict__ cursor) {
-  if (threadIdx.x == 0) {  // S is a few hundred at most
-    uint32_t run = 0;
-    for (int s = 0; s < S; s++) {
-      base[s] = run;
-      cursor[s] = 0;
-      run += need[s];
-    }
-    base[S] = run;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_topk_collect(const unsigned long long* __restrict__ keys, int64_t n, const int32_t* __restrict__ tb,
-                                                      const uint32_t* __restrict__ base, uint32_t* __restrict__ cursor,
-                                                      unsigned long long* __restrict__ list) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const unsigned long long k = i < n ? keys[i] : ~0ULL;
-  const uint32_t seg = (uint32_t)(k >> 32), low = (uint32_t)k;
-  const bool ok = k != ~0ULL && score_bin(low) >= tb[seg];
-  const uint32_t pos = wave_agg_add(cursor, ok ? seg : 0u, ok);
-  if (ok) list[base[seg] + pos] = ((unsigned long long)low << 32) | (uint32_t)i;  // ascending = score descending, then key index ascending
 }
 
 __device__ __forceinline__ void bitonic_lds(unsigned long long* a, int n2, int t) {  // n2: power of two, 256 threads
@@ -348,57 +272,6 @@ __device__ __forceinline__ void bitonic_lds(unsigned long long* a, int n2, int t
       __syncthreads();
     }
 }
-
-// one block per segment: sort the collected candidates and emit the first pre_max
-__global__ __launch_bounds__(256) void k_topk_sort(const unsigned long long* __restrict__ list, const uint32_t* __restrict__ base,
-                                                   const uint32_t* __restrict__ need, int pre_max, unsigned long long* __restrict__ sorted_keys,
-                                                   int64_t* __restrict__ order, int64_t* __restrict__ seg_start, int32_t* __restrict__ seg_len) {
-  __shared__ unsigned long long s_a[kSortCap];
-  const int s = blockIdx.x, t = threadIdx.x;
-  const uint32_t n = need[s];
-  const unsigned long long* src = list + base[s];
-  const int keepn = (int)min(n, (uint32_t)pre_max);
-  // chunks of at most kSortCap - (what is kept so far): sort, keep the first pre_max, merge the next chunk
-  int have = 0;
-  uint32_t done = 0;
-  while (done < n || have == 0) {
-    const int room = kSortCap - have;
-    const int take = (int)min((uint32_t)room, n - done);
-    for (int i = t; i < take; i += 256) s_a[have + i] = src[done + i];
-    const int cnt = have + take;
-    int n2 = 1;
-    while (n2 < cnt) n2 <<= 1;
-    for (int i = cnt + t; i < n2; i += 256) s_a[i] = ~0ULL;
-    __syncthreads();
-    bitonic_lds(s_a, n2, t);
-    done += (uint32_t)take;
-    have = min(cnt, pre_max);
-    if (n == 0) break;
-  }
-  const unsigned long long segbits = (unsigned long long)(uint32_t)s << 32;
-  for (int j = t; j < keepn; j += 256) {
-    const unsigned long long v = s_a[j];
-    sorted_keys[(int64_t)s * pre_max + j] = segbits | (v >> 32);
-    order[(int64_t)s * pre_max + j] = (int64_t)(uint32_t)v;
-  }
-  if (t == 0) {
-    seg_start[s] = (int64_t)s * pre_max;
-    seg_len[s] = keepn;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- exact radix select
-// Segmented top-k WITHOUT sorting the key array and without a weak spot: the histogram form above collects the whole threshold bin and
-// sorts it, which is fine for a trained head (a few thousand candidates) and a disaster for a freshly initialised one, where half of all
-// cells pass the score threshold and tens of thousands share one bf16-quantised score (6.4 ms against 0.87 ms for the sort).  Here the
-// k-th smallest COMPOSITE  C = (low 32 key bits = ~score bits) << 32 | key index  of every segment is found exactly, most significant
-// digit first (11 + 11 + 10 bits of the score, then -- only while a segment still has more ties than it needs -- 11 + 11 + 10 bits of the
-// index): composites are unique, so "C <= threshold" selects exactly min(k, valid) keys, ties resolved by ascending index like a stable sort.
-// A pass = one histogram launch (a workgroup owns 16 384 consecutive keys; they belong to at most a handful of segments, so it
-// histograms into 4 LDS slots of 2 048 bins -- no global atomics -- and writes its rows; keys of a fifth segment fall back to global
-// atomics) + one select launch (per segment: sum the rows of its slots, find the digit, narrow the prefix).  Segments finish early: fewer
-// than k valid keys (every pass after the first is then a no-op for them) or a digit bucket that is needed completely.
-constexpr int kRsBins = 2048, kRsSlots = 4, kRsChunk = 16384, kRsThreads = 512, kRsMaxK = 4096;
 
 __device__ __forceinline__ int rs_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
 __device__ __forceinline__ int rs_width(int p) { return (p == 2 || p == 5) ? 10 : 11; }

@@ -3,15 +3,18 @@
 Semantics = det3d/models/heads/centerhead.py:231-384 (decode, score/range mask, IoU-rectified score, per-class
 sort + top pre_max, rotated NMS, top post_max, task merge with label offsets), restructured so that the whole frame
 batch needs one key kernel per task, ONE device sort, one box kernel, ONE batched NMS and ONE device->host copy."""
+import collections
 import ctypes
+import os
 import struct
-
 import weakref
 
 import torch
 
 from . import ops
-from ._lib import PNX_BF16, PNX_F16, PNX_F32, PnxError, check, lib, ptr, stream_ptr
+from ._lib import PnxError, check, lib, ptr, stream_ptr
+
+_SIGN = -0x8000000000000000   # keys are unsigned: as int64 they sort (and search) as unsigned with the sign bit flipped
 
 
 def _get(cfg, name):
@@ -42,10 +45,20 @@ class _PnxLazyDecode(ctypes.Structure):
                 + [(n, ctypes.c_void_p) for n in ("out", "out_host", "keep_count_host", "flag_host")])
 
 
+# What a launch needs to know about one (lazy or dense, batch, map shapes, channel counts): lists s = sample * nc_total + class, S of them.
+# HostLayout (PackedDecoder.host_layout, no GPU): descs = the tasks' DecodeTask blobs, offs = cumulative key offsets of the tasks (T + 1),
+# kofs[s] = key offset of the task that owns list s, segs[t] = the lists of task t.  Layout adds the device constants: kofs and segs as
+# tensors, tdesc / koff = descs / offs, seg_off = s * pre_max, thr = NMS threshold per list, bounds = first possible key of every list
+# (sign-flipped, for searchsorted), jj = arange(pre_max).
+HostLayout = collections.namedtuple("HostLayout", "descs offs S kofs segs")
+Layout = collections.namedtuple("Layout", "host tdesc koff kofs segs seg_off thr bounds jj")
+
+
 class PackedDecoder:
     def __init__(self, num_classes, rectifier, test_cfg, has_iou, channels_per_task):
         self.num_classes = list(num_classes)
         self.nc_total = sum(num_classes)
+        self.class_task = [t for t, n in enumerate(self.num_classes) for _ in range(n)]   # the task that owns every class
         self.rectifier = rectifier
         self.has_iou = has_iou
         self.channels = list(channels_per_task)
@@ -54,91 +67,108 @@ class PackedDecoder:
         self.post_max = int(_get(nms, "nms_post_max_size"))
         self.thr = [float(v) for t in _get(nms, "nms_iou_threshold") for v in t]
         self.cfg = test_cfg
-        self._dev = {}
-        self._topk_ws = None
-        import os
-
         # PNX_DECODE_TOPK=1 (default): exact radix-select top-k in HIP (pnx_decode_topk: most significant digit first over the composite
         # (score key, key index), lists that hold fewer than pre_max valid keys finish after the first pass) -- exactly the selection of
         # a stable sort + cut (tests/test_gpu_decode.py::test_segmented_topk_equals_the_full_stable_sort).  PNX_DECODE_TOPK=0 selects the
         # bit-ranged stable key sort of all keys (pnx_sort_keys), PNX_DECODE_TORCH_SORT=1 the generic 64-bit torch.sort (cross-checks).
-        self.use_topk = os.environ.get("PNX_DECODE_TOPK", "1") == "1"
-        self.use_torch_sort = os.environ.get("PNX_DECODE_TORCH_SORT", "0") == "1"   # the generic 64-bit torch.sort (cross-check)
-        self._sort_ws = None
+        if os.environ.get("PNX_DECODE_TOPK", "1") == "1" and self.pre_max <= 4096:
+            self.selection = "topk"
+        else:
+            self.selection = "torchsort" if os.environ.get("PNX_DECODE_TORCH_SORT", "0") == "1" else "keysort"
+        self._dev = {}   # Layout per (kind, batch, element dtype, (C, H, W) per task, device); launch_lazy_fused's scratch under ("lazy_fused", ...)
+        self._ws = {}    # selection workspaces, grown on demand
         self._tptr = {}
         self._pin = {}
 
-    def _descs(self, shapes):
-        cfg = self.cfg
-        out, off = [], 0
+    use_topk = property(lambda self: self.selection == "topk")
+    use_torch_sort = property(lambda self: self.selection == "torchsort")
+
+    def host_layout(self, lazy, B, shapes, channels):
+        """HostLayout of T tasks with (H, W) = shapes[t] and channels[t] channels per map, B samples.  Plain Python: needs no GPU."""
+        cfg, descs, offs = self.cfg, [], [0]
         for t, (H, W) in enumerate(shapes):
-            out.append(pack_task(self.channels[t], self.has_iou, self.num_classes[t], off, H, W, _get(cfg, "out_size_factor")[t],
-                                 _get(cfg, "voxel_size"), _get(cfg, "pc_range"), _get(cfg, "score_threshold"),
-                                 _get(cfg, "post_center_limit_range"), self.rectifier[t]))
-            off += self.num_classes[t]
-        return out
+            descs.append(pack_task(channels[t], self.has_iou, self.num_classes[t], sum(self.num_classes[:t]), H, W, _get(cfg, "out_size_factor")[t],
+                                   _get(cfg, "voxel_size"), _get(cfg, "pc_range"), _get(cfg, "score_threshold"),
+                                   _get(cfg, "post_center_limit_range"), self.rectifier[t], lazy=lazy))
+            offs.append(offs[-1] + B * H * W)
+        S = B * self.nc_total
+        owner = [self.class_task[s % self.nc_total] for s in range(S)]
+        return HostLayout(descs, offs, S, [offs[t] for t in owner], [[s for s in range(S) if owner[s] == t] for t in range(len(shapes))])
+
+    def _layout(self, lazy, maps):
+        """The cached Layout of a launch's maps (list, one per task, of (B, C_t, H, W) tensors of one dtype)."""
+        B, dev = maps[0].shape[0], maps[0].device
+        chw = tuple(tuple(p.shape[1:]) for p in maps)
+        ck = ("lazy" if lazy else "dense", B, maps[0].dtype, chw, dev)
+        lay = self._dev.get(ck)
+        if lay is None:
+            h = self.host_layout(lazy, B, [s[1:] for s in chw], [s[0] for s in chw] if lazy else self.channels)
+            i64 = dict(dtype=torch.int64, device=dev)
+            lay = self._dev[ck] = Layout(
+                host=h, tdesc=torch.frombuffer(bytearray(b"".join(h.descs)), dtype=torch.uint8).to(dev), koff=torch.tensor(h.offs, **i64),
+                kofs=torch.tensor(h.kofs, **i64), segs=[torch.tensor(rows, **i64) for rows in h.segs],
+                seg_off=(torch.arange(h.S + 1, dtype=torch.int32, device=dev) * self.pre_max).contiguous(),
+                thr=torch.tensor(self.thr, dtype=torch.float32, device=dev).repeat(B),
+                bounds=(torch.arange(h.S + 1, **i64) << 32) ^ _SIGN, jj=torch.arange(self.pre_max, **i64))
+        return lay
+
+    def _keys(self, maps, lay):
+        """One 64-bit key per cell of every task's map (pnx_decode_keys), concatenated in task order."""
+        h, B, dt = lay.host, maps[0].shape[0], ops._DT[maps[0].dtype]
+        keys = torch.empty((h.offs[-1],), dtype=torch.int64, device=maps[0].device)
+        for t, p in enumerate(maps):
+            assert p.is_contiguous(memory_format=torch.channels_last), "head outputs must be channels_last"
+            kp = ctypes.c_void_p(keys.data_ptr() + 8 * h.offs[t])
+            check(lib().pnx_decode_keys(ptr(p), dt, B, self.nc_total, h.descs[t], kp, stream_ptr()), "pnx_decode_keys")
+        return keys
+
+    def _workspace(self, name, nbytes, dev):
+        ws = self._ws.get(name)
+        if ws is None or ws.numel() < nbytes or ws.device != dev:
+            ws = self._ws[name] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return ws
+
+    def _select(self, keys, lay):
+        """The first pre_max keys of every list in stable ascending order, by self.selection.  -> skeys, order (source index of every sorted
+        key; candidate j of list s at seg_start[s] + j), seg_start, seg_len (S,) int32 <= pre_max, seg_total (S,) int32 = valid keys of the list."""
+        L, S, n, dev = lib(), lay.host.S, keys.numel(), keys.device
+        if self.selection == "topk":
+            # segmented top-k in HIP (csrc/decode.hip): exact radix select on (score key, key index) -> collect -> LDS sort of the <= pre_max
+            # survivors of every list; no device sort of all keys, no searchsorted
+            skeys = torch.empty((S * self.pre_max,), dtype=torch.int64, device=dev)
+            order = torch.zeros((S * self.pre_max,), dtype=torch.int64, device=dev)    # slots behind seg_len are read (and ignored) by launch_lazy's glue
+            seg_start = torch.empty((S,), dtype=torch.int64, device=dev)
+            seg_len = torch.empty((S,), dtype=torch.int32, device=dev)
+            seg_total = torch.empty((S,), dtype=torch.int32, device=dev)
+            ws = self._workspace("topk", int(L.pnx_decode_topk_workspace_bytes(n, S)) + 256, dev)
+            check(L.pnx_decode_topk(ptr(keys), n, S, self.pre_max, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), ptr(seg_total), ptr(ws),
+                                    ws.numel(), stream_ptr()), "pnx_decode_topk")
+            return skeys, order, seg_start, seg_len, seg_total
+        if self.selection == "torchsort":
+            skeys, order = torch.sort(keys ^ _SIGN, stable=True)
+            skeys = skeys ^ _SIGN
+        else:
+            # the same stable sort over the 32 + bit_length(S) bits that can differ (pnx_sort_keys: 5 radix passes instead of 8)
+            skeys, order = torch.empty_like(keys), torch.empty_like(keys)
+            ws = self._workspace("keysort", int(L.pnx_sort_keys_workspace_bytes(n)), dev)
+            check(L.pnx_sort_keys(ptr(keys), n, S, ptr(skeys), ptr(order), ptr(ws), ws.numel(), stream_ptr()), "pnx_sort_keys")
+        seg_start = torch.searchsorted(skeys ^ _SIGN, lay.bounds)
+        seg_total = (seg_start[1:] - seg_start[:-1]).to(torch.int32)
+        return skeys, order, seg_start[:S], torch.clamp(seg_total, max=self.pre_max), seg_total
+
+    def _box_buffers(self, S, dev):
+        n_rows = S * self.pre_max
+        return (torch.empty((n_rows, 9), dtype=torch.float32, device=dev), torch.zeros((n_rows, 7), dtype=torch.float32, device=dev),
+                torch.empty((n_rows,), dtype=torch.float32, device=dev))
 
     @torch.no_grad()
     def launch(self, packed, tokens=None):
         """packed: list (one per task) of (B, C_t, H, W) channels_last tensors, fp32 or bf16 (all the same dtype).
         Enqueues decode + NMS + the D2H copy and returns a PendingDetections."""
-        B = packed[0].shape[0]
-        dev = packed[0].device
-        dt = {torch.float32: PNX_F32, torch.bfloat16: PNX_BF16, torch.float16: PNX_F16}[packed[0].dtype]
-        T = len(packed)
-        shapes = [(p.shape[2], p.shape[3]) for p in packed]
-        for p in packed:
-            assert p.is_contiguous(memory_format=torch.channels_last), "packed head outputs must be channels_last"
-        descs = self._descs(shapes)
-        sizes = [B * h * w for h, w in shapes]
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + n)
-        keys = torch.empty((offs[-1],), dtype=torch.int64, device=dev)
-        L = lib()
-        for t, p in enumerate(packed):
-            kp = ctypes.c_void_p(keys.data_ptr() + 8 * offs[t])
-            check(L.pnx_decode_keys(ptr(p), dt, B, self.nc_total, descs[t], kp, stream_ptr()), "pnx_decode_keys")
-        S = B * self.nc_total
-        ck = (B, T, dt, tuple(shapes), dev)
-        if ck not in self._dev:
-            tdesc = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
-            koff = torch.tensor(offs, dtype=torch.int64, device=dev)
-            seg_off = (torch.arange(S + 1, dtype=torch.int32, device=dev) * self.pre_max).contiguous()
-            thr = torch.tensor(self.thr, dtype=torch.float32, device=dev).repeat(B)
-            bounds = (torch.arange(S + 1, device=dev, dtype=torch.int64) << 32) ^ (-0x8000000000000000)
-            self._dev[ck] = (tdesc, koff, seg_off, thr, bounds)
-        tdesc, koff, seg_off, thr, bounds = self._dev[ck]
-        if self.use_topk and self.pre_max <= 4096:
-            # segmented top-k in HIP (csrc/decode.hip): exact radix select on (score key, key index) -> collect -> LDS sort of the <= pre_max
-            # survivors of every list; no device sort of all keys, no searchsorted
-            n_rows0 = S * self.pre_max
-            skeys = torch.empty((n_rows0,), dtype=torch.int64, device=dev)
-            order = torch.empty((n_rows0,), dtype=torch.int64, device=dev)
-            seg_start = torch.empty((S,), dtype=torch.int64, device=dev)
-            seg_len = torch.empty((S,), dtype=torch.int32, device=dev)
-            wsb = int(L.pnx_decode_topk_workspace_bytes(offs[-1], S)) + 256
-            if self._topk_ws is None or self._topk_ws.numel() < wsb or self._topk_ws.device != dev:
-                self._topk_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            check(L.pnx_decode_topk(ptr(keys), offs[-1], S, self.pre_max, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), None, ptr(self._topk_ws),
-                                    self._topk_ws.numel(), stream_ptr()), "pnx_decode_topk")
-        elif self.use_torch_sort:
-            # keys are non-negative when valid ... as int64 the all-ones key is -1: sort as unsigned by flipping the sign bit
-            skeys, order = torch.sort(keys ^ (-0x8000000000000000), stable=True)
-            skeys = skeys ^ (-0x8000000000000000)
-            seg_start = torch.searchsorted(skeys ^ (-0x8000000000000000), bounds)
-            seg_len = torch.clamp(seg_start[1:] - seg_start[:-1], max=self.pre_max).to(torch.int32)
-        else:
-            # the same stable sort over the 32 + bit_length(S) bits that can differ (pnx_sort_keys: 5 radix passes instead of 8)
-            skeys = torch.empty_like(keys)
-            order = torch.empty_like(keys)
-            wsb = int(L.pnx_sort_keys_workspace_bytes(offs[-1]))
-            if self._sort_ws is None or self._sort_ws.numel() < wsb or self._sort_ws.device != dev:
-                self._sort_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            check(L.pnx_sort_keys(ptr(keys), offs[-1], S, ptr(skeys), ptr(order), ptr(self._sort_ws), self._sort_ws.numel(), stream_ptr()),
-                  "pnx_sort_keys")
-            seg_start = torch.searchsorted(skeys ^ (-0x8000000000000000), bounds)
-            seg_len = torch.clamp(seg_start[1:] - seg_start[:-1], max=self.pre_max).to(torch.int32)
+        B, T, dev = packed[0].shape[0], len(packed), packed[0].device
+        lay = self._layout(False, packed)
+        S = lay.host.S
+        skeys, order, seg_start, seg_len, _ = self._select(self._keys(packed, lay), lay)
         # pointer table of the task tensors: a torch.tensor(list, device=...) is a blocking copy from pageable memory (it would make
         # the host wait for the whole network before it could enqueue the sort/NMS); cached per pointer tuple, else a pinned async copy
         pk = tuple(p.data_ptr() for p in packed)
@@ -151,33 +181,31 @@ class PackedDecoder:
                 self._tptr.clear()
             self._tptr[pk] = tptr
             self._tptr_host = hp  # keep the pinned source alive until the copy ran
-        n_rows = S * self.pre_max
-        boxes9 = torch.empty((n_rows, 9), dtype=torch.float32, device=dev)
-        boxes7 = torch.zeros((n_rows, 7), dtype=torch.float32, device=dev)
-        scores = torch.empty((n_rows,), dtype=torch.float32, device=dev)
-        check(L.pnx_decode_boxes(ptr(tptr), ptr(tdesc), ptr(koff), T, dt, B, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), S,
-                                 self.pre_max, ptr(boxes9), ptr(boxes7), ptr(scores), stream_ptr()), "pnx_decode_boxes")
-        return self._finish(boxes9, boxes7, scores, seg_off, thr, seg_len, S, B, dev, tokens)
+        boxes9, boxes7, scores = self._box_buffers(S, dev)
+        check(lib().pnx_decode_boxes(ptr(tptr), ptr(lay.tdesc), ptr(lay.koff), T, ops._DT[packed[0].dtype], B, ptr(skeys), ptr(order), ptr(seg_start),
+                                     ptr(seg_len), S, self.pre_max, ptr(boxes9), ptr(boxes7), ptr(scores), stream_ptr()), "pnx_decode_boxes")
+        return self._finish(lay, boxes9, boxes7, scores, seg_len, B, tokens)
 
-    def _finish(self, boxes9, boxes7, scores, seg_off, thr, seg_len, S, B, dev, tokens, flag=None, fallback=None):
-        L = lib()
-        keep, cnt = ops.nms_batched(boxes7, seg_off, thr, self.pre_max, post_max=self.post_max, seg_len=seg_len)
+    def _finish(self, lay, boxes9, boxes7, scores, seg_len, B, tokens, flag=None, fallback=None):
+        S, dev = lay.host.S, boxes9.device
+        keep, cnt = ops.nms_batched(boxes7, lay.seg_off, lay.thr, self.pre_max, post_max=self.post_max, seg_len=seg_len)
         out = torch.empty((S, self.post_max, 10), dtype=torch.float32, device=dev)
-        check(L.pnx_gather_kept(ptr(boxes9), ptr(scores), ptr(keep), ptr(cnt), S, self.pre_max, self.post_max, ptr(out), stream_ptr()),
+        check(lib().pnx_gather_kept(ptr(boxes9), ptr(scores), ptr(keep), ptr(cnt), S, self.pre_max, self.post_max, ptr(out), stream_ptr()),
               "pnx_gather_kept")
         # the one device->host hand-off of the frame batch: asynchronous into pinned memory; PendingDetections.result() waits
-        slot = self._pinned_slot(out.shape, S, out.dtype, cnt.dtype)
-        out_h, cnt_h = slot["out"], slot["cnt"]
-        out_h.copy_(out, non_blocking=True)
-        cnt_h.copy_(cnt[:S], non_blocking=True)
+        slot = self._pinned_slot(out.shape, S, out.dtype, cnt.dtype, flag=flag is not None)
+        slot["out"].copy_(out, non_blocking=True)
+        slot["cnt"].copy_(cnt[:S], non_blocking=True)
+        if flag is not None:  # lazy head: the range-test flag rides on the same stream; result() falls back to the dense path if it is set
+            slot["flag"].copy_(flag, non_blocking=True)
+        return self._hand_off(slot, B, tokens, flag is not None, fallback)
+
+    def _hand_off(self, slot, B, tokens, with_flag, fallback):
+        """The PendingDetections of a pinned slot whose copies are enqueued on the current stream; it owns the slot until it is resolved."""
         ev = torch.cuda.Event()
         ev.record()
-        pend = PendingDetections(ev, out_h, cnt_h, B, self.nc_total, tokens if tokens else [None] * B)
-        if flag is not None:  # lazy head: the range-test flag rides on the same stream; result() falls back to the dense path if it is set
-            if "flag" not in slot:
-                slot["flag"] = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
-            slot["flag"].copy_(flag, non_blocking=True)
-            ev.record()
+        pend = PendingDetections(ev, slot["out"], slot["cnt"], B, self.nc_total, tokens if tokens else [None] * B)
+        if with_flag:
             pend.flag_h, pend.fallback = slot["flag"], fallback
         slot["owner"] = weakref.ref(pend)
         return pend
@@ -190,83 +218,21 @@ class PackedDecoder:
         (slots behind seg_len are ignored).  Same selection as launch(): scores come from the dense maps, the candidates are the
         first pre_max of every (sample, class) list; the centre range test runs on the evaluated candidates (pnx_decode_boxes_lazy) and
         `fallback()` (the dense path) is taken by result() in the one case where that could change the selection."""
-        B = dense[0].shape[0]
-        dev = dense[0].device
-        dt = {torch.float32: PNX_F32, torch.bfloat16: PNX_BF16, torch.float16: PNX_F16}[dense[0].dtype]
-        T = len(dense)
-        shapes = [(p.shape[2], p.shape[3]) for p in dense]
-        cfg = self.cfg
-        descs, off = [], 0
-        for t, (H, W) in enumerate(shapes):
-            descs.append(pack_task(dense[t].shape[1], self.has_iou, self.num_classes[t], off, H, W, _get(cfg, "out_size_factor")[t],
-                                   _get(cfg, "voxel_size"), _get(cfg, "pc_range"), _get(cfg, "score_threshold"),
-                                   _get(cfg, "post_center_limit_range"), self.rectifier[t], lazy=True))
-            off += self.num_classes[t]
-        sizes = [B * h * w for h, w in shapes]
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + n)
-        keys = torch.empty((offs[-1],), dtype=torch.int64, device=dev)
-        L = lib()
-        for t, p in enumerate(dense):
-            assert p.is_contiguous(memory_format=torch.channels_last), "dense head outputs must be channels_last"
-            kp = ctypes.c_void_p(keys.data_ptr() + 8 * offs[t])
-            check(L.pnx_decode_keys(ptr(p), dt, B, self.nc_total, descs[t], kp, stream_ptr()), "pnx_decode_keys")
-        S = B * self.nc_total
-        ck = ("lazy", B, T, dt, tuple(shapes), dev)
-        if ck not in self._dev:
-            tdesc = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
-            koff = torch.tensor(offs, dtype=torch.int64, device=dev)
-            seg_off = (torch.arange(S + 1, dtype=torch.int32, device=dev) * self.pre_max).contiguous()
-            thr = torch.tensor(self.thr, dtype=torch.float32, device=dev).repeat(B)
-            bounds = (torch.arange(S + 1, device=dev, dtype=torch.int64) << 32) ^ (-0x8000000000000000)
-            seg_cls = torch.arange(S, device=dev) % self.nc_total
-            segs, kofs, c0 = [], torch.zeros((S,), dtype=torch.int64, device=dev), 0
-            for t in range(T):
-                m = (seg_cls >= c0) & (seg_cls < c0 + self.num_classes[t])
-                segs.append(torch.nonzero(m).flatten())
-                kofs[m] = offs[t]
-                c0 += self.num_classes[t]
-            jj = torch.arange(self.pre_max, device=dev, dtype=torch.int64)
-            self._dev[ck] = (tdesc, koff, seg_off, thr, bounds, segs, kofs, jj)
-        tdesc, koff, seg_off, thr, bounds, segs, kofs, jj = self._dev[ck]
-        if self.use_topk and self.pre_max <= 4096:
-            n_rows0 = S * self.pre_max
-            skeys = torch.empty((n_rows0,), dtype=torch.int64, device=dev)
-            order = torch.zeros((n_rows0,), dtype=torch.int64, device=dev)     # slots behind seg_len are read (and ignored) by the evaluator's glue
-            seg_start = torch.empty((S,), dtype=torch.int64, device=dev)
-            seg_len = torch.empty((S,), dtype=torch.int32, device=dev)
-            seg_total = torch.empty((S,), dtype=torch.int32, device=dev)
-            wsb = int(L.pnx_decode_topk_workspace_bytes(offs[-1], S)) + 256
-            if self._topk_ws is None or self._topk_ws.numel() < wsb or self._topk_ws.device != dev:
-                self._topk_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            check(L.pnx_decode_topk(ptr(keys), offs[-1], S, self.pre_max, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), ptr(seg_total),
-                                    ptr(self._topk_ws), self._topk_ws.numel(), stream_ptr()), "pnx_decode_topk")
-            valid = jj[None, :] < seg_len[:, None]
-            local = torch.where(valid, order.view(S, self.pre_max) - kofs[:, None], torch.zeros_like(kofs[:, None]))
-        else:
-            skeys = torch.empty_like(keys)
-            order = torch.empty_like(keys)
-            wsb = int(L.pnx_sort_keys_workspace_bytes(offs[-1]))
-            if self._sort_ws is None or self._sort_ws.numel() < wsb or self._sort_ws.device != dev:
-                self._sort_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            check(L.pnx_sort_keys(ptr(keys), offs[-1], S, ptr(skeys), ptr(order), ptr(self._sort_ws), self._sort_ws.numel(), stream_ptr()), "pnx_sort_keys")
-            seg_start = torch.searchsorted(skeys ^ (-0x8000000000000000), bounds)
-            seg_total = (seg_start[1:] - seg_start[:-1]).to(torch.int32)
-            seg_len = torch.clamp(seg_total, max=self.pre_max)
-            # candidate cells per slot (s, j): local index b*H*W + cell inside the slot's task
-            pos = torch.clamp(seg_start[:S, None] + jj[None, :], max=offs[-1] - 1)
-            valid = jj[None, :] < seg_len[:, None]
-            local = order[pos] - kofs[:, None]
-        n_rows = S * self.pre_max
-        cand = evaluator(local, seg_len, valid, segs)                          # (S, pre_max, 10) fp32
-        boxes9 = torch.empty((n_rows, 9), dtype=torch.float32, device=dev)
-        boxes7 = torch.zeros((n_rows, 7), dtype=torch.float32, device=dev)
-        scores = torch.empty((n_rows,), dtype=torch.float32, device=dev)
+        B, T, dev = dense[0].shape[0], len(dense), dense[0].device
+        lay = self._layout(True, dense)
+        S = lay.host.S
+        skeys, order, seg_start, seg_len, seg_total = self._select(self._keys(dense, lay), lay)
+        # candidate cells per slot (s, j): local index b*H*W + cell inside the slot's task; 0 behind seg_len
+        valid = lay.jj[None, :] < seg_len[:, None]
+        pos = torch.clamp(seg_start[:, None] + lay.jj[None, :], max=order.numel() - 1)
+        local = torch.where(valid, order[pos] - lay.kofs[:, None], torch.zeros_like(lay.kofs[:, None]))
+        cand = evaluator(local, seg_len, valid, lay.segs)                      # (S, pre_max, 10) fp32
+        boxes9, boxes7, scores = self._box_buffers(S, dev)
         flag = torch.zeros((1,), dtype=torch.int32, device=dev)
-        check(L.pnx_decode_boxes_lazy(ptr(tdesc), ptr(koff), T, self.nc_total, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), ptr(seg_total), S,
-                                      self.pre_max, ptr(cand), ptr(boxes9), ptr(boxes7), ptr(scores), ptr(flag), stream_ptr()), "pnx_decode_boxes_lazy")
-        return self._finish(boxes9, boxes7, scores, seg_off, thr, seg_len, S, B, dev, tokens, flag=flag, fallback=fallback)
+        check(lib().pnx_decode_boxes_lazy(ptr(lay.tdesc), ptr(lay.koff), T, self.nc_total, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len),
+                                          ptr(seg_total), S, self.pre_max, ptr(cand), ptr(boxes9), ptr(boxes7), ptr(scores), ptr(flag), stream_ptr()),
+              "pnx_decode_boxes_lazy")
+        return self._finish(lay, boxes9, boxes7, scores, seg_len, B, tokens, flag=flag, fallback=fallback)
 
     @torch.no_grad()
     def launch_lazy_fused(self, dense, lazy_tasks, class_task, tokens=None, fallback=None):
@@ -275,82 +241,50 @@ class PackedDecoder:
         descriptor that is built once per (batch, map shapes); per step only the pointers of the dense maps, of the deblocked maps and of
         the pinned result slot change.  lazy_tasks: per task (up, wfrag1, bias1, w2c, bias2) as ops.sephead_lazy takes them.
         Every scratch buffer is persistent: the calls of consecutive steps are ordered by the stream."""
-        B, dev, T = dense[0].shape[0], dense[0].device, len(dense)
-        dt = {torch.float32: PNX_F32, torch.bfloat16: PNX_BF16, torch.float16: PNX_F16}[dense[0].dtype]
-        shapes = [(p.shape[2], p.shape[3]) for p in dense]
-        S = B * self.nc_total
-        L = lib()
-        ck = ("lazy_fused", B, T, dt, tuple(shapes), dev, torch.cuda.current_stream().cuda_stream)   # persistent scratch: one set per stream
+        B, dev, T, dtype = dense[0].shape[0], dense[0].device, len(dense), dense[0].dtype
+        S, L = B * self.nc_total, lib()
+        chw = tuple(tuple(p.shape[1:]) for p in dense)
+        ck = ("lazy_fused", B, dtype, chw, dev, torch.cuda.current_stream().cuda_stream)   # persistent scratch: one set per stream
         st = self._dev.get(ck)
         if st is None:
-            cfg = self.cfg
-            descs, off, offs = [], 0, [0]
-            for t, (H, W) in enumerate(shapes):
-                descs.append(pack_task(dense[t].shape[1], self.has_iou, self.num_classes[t], off, H, W, _get(cfg, "out_size_factor")[t],
-                                       _get(cfg, "voxel_size"), _get(cfg, "pc_range"), _get(cfg, "score_threshold"),
-                                       _get(cfg, "post_center_limit_range"), self.rectifier[t], lazy=True))
-                off += self.num_classes[t]
-                offs.append(offs[-1] + B * H * W)
-            n_keys, n_rows = offs[-1], S * self.pre_max
-            kofs = torch.tensor([offs[class_task[s % self.nc_total]] for s in range(S)], dtype=torch.int64, device=dev)
-            i64, i32, f32 = torch.int64, torch.int32, torch.float32
-            bufs = {
-                "descs_host": ctypes.create_string_buffer(b"".join(descs)),
-                "tdesc": torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev),
-                "koff_host": (ctypes.c_int64 * (T + 1))(*offs),
-                "koff": torch.tensor(offs, dtype=i64, device=dev),
-                "kofs": kofs,
-                "seg_off": (torch.arange(S + 1, dtype=i32, device=dev) * self.pre_max).contiguous(),
-                "thr": torch.tensor(self.thr, dtype=f32, device=dev).repeat(B),
-                "dense_arr": (ctypes.c_void_p * T)(),
-                "tasks_arr": (ops._PnxLazyTask * T)(),
-                "class_task": (ctypes.c_int32 * self.nc_total)(*[int(v) for v in class_task]),
-                "keys": torch.empty((n_keys,), dtype=i64, device=dev), "skeys": torch.empty((n_rows,), dtype=i64, device=dev),
-                "order": torch.empty((n_rows,), dtype=i64, device=dev), "seg_start": torch.empty((S,), dtype=i64, device=dev),
-                "local": torch.empty((n_rows,), dtype=i64, device=dev), "seg_len": torch.empty((S,), dtype=i32, device=dev),
-                "seg_total": torch.empty((S,), dtype=i32, device=dev), "cand": torch.empty((n_rows, 10), dtype=f32, device=dev),
-                "boxes9": torch.empty((n_rows, 9), dtype=f32, device=dev), "boxes7": torch.empty((n_rows, 7), dtype=f32, device=dev),
-                "scores": torch.empty((n_rows,), dtype=f32, device=dev), "flag": torch.empty((1,), dtype=i32, device=dev),
-                "keep": torch.empty((n_rows,), dtype=i32, device=dev), "cnt": torch.empty((S,), dtype=i32, device=dev),
-                "out": torch.empty((S, self.post_max, 10), dtype=f32, device=dev),
-            }
-            bufs["topk_ws"] = torch.empty(int(L.pnx_decode_topk_workspace_bytes(n_keys, S)) + 256, dtype=torch.uint8, device=dev)
-            bufs["nms_ws"] = torch.empty(max(int(L.pnx_nms_workspace_bytes(n_rows, S, self.pre_max)), 1), dtype=torch.uint8, device=dev)
+            if [int(v) for v in class_task] != self.class_task:
+                raise PnxError(f"lazy decode: class_task {list(class_task)} is not the decoder's {self.class_task}")
+            lay = self._layout(True, dense)
+            n_keys, n_rows = lay.host.offs[-1], S * self.pre_max
+            i64, i32, f32, u8 = torch.int64, torch.int32, torch.float32, torch.uint8
+            # keyed by the descriptor's field names: the host tables, then the device scratch as (elements, dtype)
+            bufs = {"dense_host": (ctypes.c_void_p * T)(), "task_descs_host": ctypes.create_string_buffer(b"".join(lay.host.descs)),
+                    "task_key_off_host": (ctypes.c_int64 * (T + 1))(*lay.host.offs), "lazy_tasks_host": (ops._PnxLazyTask * T)(),
+                    "class_task_host": (ctypes.c_int32 * self.nc_total)(*self.class_task)}
+            scratch = {"keys": (n_keys, i64), "sorted_keys": (n_rows, i64), "order": (n_rows, i64), "seg_start": (S, i64), "local": (n_rows, i64),
+                       "seg_len": (S, i32), "seg_total": (S, i32), "cand": (n_rows * 10, f32), "boxes9": (n_rows * 9, f32), "boxes7": (n_rows * 7, f32),
+                       "scores": (n_rows, f32), "flag": (1, i32), "keep": (n_rows, i32), "keep_count": (S, i32), "out": (S * self.post_max * 10, f32),
+                       "topk_ws": (int(L.pnx_decode_topk_workspace_bytes(n_keys, S)) + 256, u8),
+                       "nms_ws": (max(int(L.pnx_nms_workspace_bytes(n_rows, S, self.pre_max)), 1), u8)}
             d = _PnxLazyDecode()
-            d.n_tasks, d.n_classes_total, d.batch, d.pre_max, d.post_max, d.dtype = T, self.nc_total, B, self.pre_max, self.post_max, dt
-            d.dense_host = ctypes.cast(bufs["dense_arr"], ctypes.c_void_p)
-            d.task_descs_host = ctypes.cast(bufs["descs_host"], ctypes.c_void_p)
-            d.task_key_off_host = ctypes.cast(bufs["koff_host"], ctypes.c_void_p)
-            d.lazy_tasks_host = ctypes.cast(bufs["tasks_arr"], ctypes.c_void_p)
-            d.class_task_host = ctypes.cast(bufs["class_task"], ctypes.c_void_p)
-            for f, k in (("task_descs_dev", "tdesc"), ("task_key_off_dev", "koff"), ("list_key_off_dev", "kofs"), ("seg_off_dev", "seg_off"),
-                         ("nms_thresh_dev", "thr"), ("keys", "keys"), ("sorted_keys", "skeys"), ("order", "order"), ("seg_start", "seg_start"),
-                         ("local", "local"), ("seg_len", "seg_len"), ("seg_total", "seg_total"), ("cand", "cand"), ("boxes9", "boxes9"),
-                         ("boxes7", "boxes7"), ("scores", "scores"), ("flag", "flag"), ("keep", "keep"), ("keep_count", "cnt"),
-                         ("topk_ws", "topk_ws"), ("nms_ws", "nms_ws"), ("out", "out")):
-                setattr(d, f, bufs[k].data_ptr())
+            d.n_tasks, d.n_classes_total, d.batch, d.pre_max, d.post_max, d.dtype = T, self.nc_total, B, self.pre_max, self.post_max, ops._DT[dtype]
+            for f in list(bufs):
+                setattr(d, f, ctypes.cast(bufs[f], ctypes.c_void_p))
+            for f, (n, dt) in scratch.items():
+                bufs[f] = torch.empty((n,), dtype=dt, device=dev)
+                setattr(d, f, bufs[f].data_ptr())
+            for f, t in (("task_descs_dev", lay.tdesc), ("task_key_off_dev", lay.koff), ("list_key_off_dev", lay.kofs), ("seg_off_dev", lay.seg_off),
+                         ("nms_thresh_dev", lay.thr)):
+                setattr(d, f, t.data_ptr())
             d.topk_ws_bytes, d.nms_ws_bytes = bufs["topk_ws"].numel(), bufs["nms_ws"].numel()
-            st = self._dev[ck] = (d, bufs)
-        d, bufs = st
-        for t, (p, (up, wf, b1, w2c, b2)) in enumerate(zip(dense, lazy_tasks)):
-            if not (p.is_contiguous(memory_format=torch.channels_last) and up.is_contiguous(memory_format=torch.channels_last)
-                    and up.dtype == p.dtype and wf.dtype == p.dtype and up.shape[1] == 64 and up.shape[0] == B and tuple(up.shape[2:]) == shapes[t]):
-                raise PnxError("lazy decode: dense maps, 64-channel deblocked maps and packed weights must be channels_last bf16 / fp16 (one dtype) of the task's shape")
-            bufs["dense_arr"][t] = p.data_ptr()
-            bufs["tasks_arr"][t] = ops._PnxLazyTask(up.data_ptr(), wf.data_ptr(), b1.data_ptr(), w2c.data_ptr(), b2.data_ptr(), up.shape[2], up.shape[3])
-        slot = self._pinned_slot((S, self.post_max, 10), S, torch.float32, torch.int32)
-        if "flag" not in slot:
-            slot["flag"] = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+            st = self._dev[ck] = (d, bufs, [s[1:] for s in chw])
+        d, bufs, hw = st
+        for t, p in enumerate(dense):
+            if not (p.dtype == dtype and p.is_contiguous(memory_format=torch.channels_last)):
+                raise PnxError("lazy decode: the dense [iou] hm maps must be channels_last bf16 / fp16, one dtype")
+            bufs["dense_host"][t] = p.data_ptr()
+        ops.lazy_task_table(lazy_tasks, B, dtype, hw, bufs["lazy_tasks_host"])
+        slot = self._pinned_slot((S, self.post_max, 10), S, torch.float32, torch.int32, flag=True)
         d.out_host, d.keep_count_host, d.flag_host = slot["out"].data_ptr(), slot["cnt"].data_ptr(), slot["flag"].data_ptr()
         check(L.pnx_decode_lazy_enqueue(ctypes.byref(d), stream_ptr()), "pnx_decode_lazy_enqueue")
-        ev = torch.cuda.Event()
-        ev.record()
-        pend = PendingDetections(ev, slot["out"], slot["cnt"], B, self.nc_total, tokens if tokens else [None] * B)
-        pend.flag_h, pend.fallback = slot["flag"], fallback
-        slot["owner"] = weakref.ref(pend)
-        return pend
+        return self._hand_off(slot, B, tokens, True, fallback)
 
-    def _pinned_slot(self, out_shape, S, out_dtype, cnt_dtype):
+    def _pinned_slot(self, out_shape, S, out_dtype, cnt_dtype, flag=False):
         """One of the rotating pinned result buffers of a shape (a serving loop has at most two batches in flight: bench.py / forward_async);
         a slot is only reused once the PendingDetections that owns it was resolved (result()); otherwise the ring grows."""
         ring = self._pin.setdefault((tuple(out_shape), S), [])
@@ -359,6 +293,8 @@ class PackedDecoder:
             slot = {"out": torch.empty(out_shape, dtype=out_dtype, pin_memory=True), "cnt": torch.empty((S,), dtype=cnt_dtype, pin_memory=True),
                     "owner": None}
             ring.append(slot)
+        if flag and "flag" not in slot:
+            slot["flag"] = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
         return slot
 
     def __call__(self, packed, tokens=None):

@@ -1565,6 +1565,10 @@ class FusedPillarNeXt(nn.Module):
             self._decoder = PackedDecoder(hd.num_classes, hd.rectifier, self.post_processing, hd.with_iou, chans)
         return self._decoder
 
+    @staticmethod
+    def _lazy_eval_in_torch():   # read on every call: tests flip it between two runs of one model
+        return os.environ.get("PNX_HEAD_LAZY_TORCH", "0") == "1"
+
     @torch.no_grad()
     def lazy_eval(self, ups, local, seg_len, valid, segs):
         """The five regression branches of every task at the candidate cells (local (S, pre_max) = b*H*W + cell inside the list's task map,
@@ -1573,7 +1577,7 @@ class FusedPillarNeXt(nn.Module):
         (-> 10) at the cell; zero padding at the map border.  Returns (S, pre_max, 10) fp32 in the order reg 2, height 1, dim 3, rot 2,
         vel 2, rounded to bf16 like the dense output.  One HIP launch (ops.sephead_lazy); PNX_HEAD_LAZY_TORCH=1 runs the torch statement
         of the same arithmetic below instead (tests compare the two)."""
-        if os.environ.get("PNX_HEAD_LAZY_TORCH", "0") != "1":
+        if not self._lazy_eval_in_torch():
             tasks, class_task = self._lazy_tasks(ups)
             return ops.sephead_lazy(tasks, class_task, ups[0].shape[0], local, seg_len, local.shape[1])
         cand = torch.zeros((*local.shape, 10), dtype=torch.float32, device=local.device)
@@ -1635,7 +1639,7 @@ class FusedPillarNeXt(nn.Module):
             return self.decoder().launch([c2(c1(u)) for u, c1, c2 in zip(ups, self.task_conv1, self.task_conv2)], tokens)
 
         dec = self.decoder()
-        if self.use_plan and dec.use_topk and dec.pre_max <= 4096 and os.environ.get("PNX_HEAD_LAZY_TORCH", "0") != "1":
+        if self.use_plan and dec.selection == "topk" and not self._lazy_eval_in_torch():
             tasks, class_task = self._lazy_tasks(ups)
             return dec.launch_lazy_fused([p.dense for p in packed], tasks, class_task, tokens, dense_path)
         return dec.launch_lazy([p.dense for p in packed], lambda *a: self.lazy_eval(ups, *a), tokens, dense_path)

@@ -492,18 +492,28 @@ class _PnxLazyTask(ctypes.Structure):
                 ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
+def lazy_task_table(tasks, batch, dtype, shapes=None, arr=None):
+    """The _PnxLazyTask row of every task (up, wfrag1, bias1, w2c, bias2), written into `arr` (a caller's persistent table) or a new one.
+    Checks what k_sephead_lazy relies on: 64-channel channels_last CUDA maps of `batch` samples in ONE 16-bit dtype (the packed weights
+    included) and, where shapes[t] = the tuple (H, W) is given, of the task's map shape."""
+    if arr is None:
+        arr = (_PnxLazyTask * len(tasks))()
+    for t, (up, wf, b1, w2c, b2) in enumerate(tasks):
+        if not (up.is_cuda and dtype in _HALF and up.dtype == dtype and wf.dtype == dtype and up.shape[1] == 64 and up.shape[0] == batch
+                and up.is_contiguous(memory_format=torch.channels_last) and (shapes is None or tuple(up.shape[2:]) == shapes[t])):
+            raise PnxError("sephead_lazy needs 64-channel channels_last bf16 / fp16 CUDA maps of one dtype (packed weights included), of the "
+                           "batch and of the task's map shape")
+        arr[t] = _PnxLazyTask(up.data_ptr(), wf.data_ptr(), b1.data_ptr(), w2c.data_ptr(), b2.data_ptr(), up.shape[2], up.shape[3])
+    return arr
+
+
 def sephead_lazy(tasks, class_task, batch, local, seg_len, pre_max):
     """The regression branches of every task at the candidate cells (csrc/sephead_lazy.h::k_sephead_lazy, one launch).
     tasks: list of (up (B,64,H,W) channels_last bf16 / fp16 (one dtype for all tasks), wfrag1 in that dtype, bias1, w2c, bias2); class_task: task index of every class (host list);
     local int64 (batch*len(class_task), pre_max) = b*H*W + cell per slot; seg_len int32 (batch*len(class_task),).  -> (lists, pre_max, 10) fp32,
     rows behind seg_len zero."""
-    arr = (_PnxLazyTask * len(tasks))()
     dt = tasks[0][0].dtype
-    for i, (up, wf, b1, w2c, b2) in enumerate(tasks):
-        if not (up.is_cuda and up.dtype in _HALF and up.dtype == dt and wf.dtype == dt and up.shape[1] == 64
-                and up.is_contiguous(memory_format=torch.channels_last) and up.shape[0] == batch):
-            raise PnxError("sephead_lazy needs 64-channel channels_last bf16 / fp16 CUDA tensors of one dtype (weights included)")
-        arr[i] = _PnxLazyTask(up.data_ptr(), wf.data_ptr(), b1.data_ptr(), w2c.data_ptr(), b2.data_ptr(), up.shape[2], up.shape[3])
+    arr = lazy_task_table(tasks, batch, dt)
     nc = len(class_task)
     ct = (ctypes.c_int32 * nc)(*[int(v) for v in class_task])
     S = batch * nc

@@ -396,24 +396,69 @@ def test_bit_ranged_key_sort_equals_the_full_stable_sort(S):
     assert torch.equal(got_k, want_k) and torch.equal(got_o, want_o)
 
 
-def test_decoder_sort_paths_agree(monkeypatch):
-    """PackedDecoder with pnx_sort_keys (default) and with the generic torch.sort: identical detections."""
+@pytest.mark.parametrize("kind", ["dense", "lazy"])
+def test_decoder_sort_paths_agree(kind, monkeypatch):
+    """PackedDecoder.launch (dense) / launch_lazy (lazy) under each candidate selection -- radix-select top-k (default), pnx_sort_keys
+    (PNX_DECODE_TOPK=0), the generic torch.sort (PNX_DECODE_TOPK=0 PNX_DECODE_TORCH_SORT=1): identical detections, bit for bit, on maps where
+    some lists are cut at pre_max and some are not.  lazy: the dense maps are the [iou] hm channels of the packed maps, the evaluator
+    gathers the packed maps' regression channels at the candidate cells."""
     from pillarnext_amd.decode import PackedDecoder
 
-    g = torch.Generator(device="cuda").manual_seed(11)
-    B, H, W = 2, 64, 64
-    cfg = dict(nms=dict(nms_pre_max_size=200, nms_post_max_size=40, nms_iou_threshold=[[0.2], [0.2, 0.2]]), score_threshold=0.1,
+    g = torch.Generator().manual_seed(11)
+    B, H, W, ncls, pre_max = 2, 64, 64, [1, 2], 200
+    cfg = dict(nms=dict(nms_pre_max_size=pre_max, nms_post_max_size=40, nms_iou_threshold=[[0.2], [0.2, 0.2]]), score_threshold=0.1,
                pc_range=[-25.6, -25.6], voxel_size=[0.1, 0.1], out_size_factor=[8, 8], post_center_limit_range=[-30, -30, -10, 30, 30, 10])
-    packed = [(torch.randn((B, 16, H, W), device="cuda", generator=g) * 0.7).to(torch.bfloat16).contiguous(memory_format=torch.channels_last) for _ in range(2)]
+    maps = [torch.randn((B, 16, H, W), generator=g) * 0.7 for _ in ncls]
+    maps[1][:, 12] -= 2.0                                                   # the second class of the two-class task: a short list
+    maps = [m.to(torch.bfloat16) for m in maps]
+    # the decoder's validity rule, restated: a cell belongs to its first-maximal class (channels 11..) and is valid when the sigmoid of that
+    # logit exceeds score_threshold; the centre range test (dense: on the keys, lazy: on the candidates) must not reject anything here
+    counts = torch.zeros((B, sum(ncls)), dtype=torch.int64)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    for t, n in enumerate(ncls):
+        m = maps[t].float()
+        cx, cy = (xs + m[:, 0]) * 8 * 0.1 - 25.6, (ys + m[:, 1]) * 8 * 0.1 - 25.6
+        assert float(cx.abs().max()) < 30 and float(cy.abs().max()) < 30 and float(m[:, 2].abs().max()) < 10
+        sc = torch.sigmoid(m[:, 11:11 + n])
+        best = sc.max(dim=1).values
+        hit = sc == best[:, None]
+        first = hit & (hit.cumsum(1) == 1)
+        for c in range(n):
+            counts[:, sum(ncls[:t]) + c] = (first[:, c] & (best > 0.1)).sum(dim=(1, 2))
+    print("candidates per (sample, class) list:", counts.tolist())
+    assert bool((counts > pre_max).any()) and bool(((counts >= 1) & (counts < pre_max)).any())
+    packed = [m.cuda().contiguous(memory_format=torch.channels_last) for m in maps]
+    dense = []
+    for p in packed:
+        d = torch.zeros_like(p)
+        d[:, :6] = p[:, 10:]
+        dense.append(d.contiguous(memory_format=torch.channels_last))
+
+    def evaluator(local, seg_len, valid, segs):
+        cand = torch.zeros((*local.shape, 10), dtype=torch.float32, device=local.device)
+        for t, rows in enumerate(segs):
+            cand[rows] = packed[t].permute(0, 2, 3, 1).reshape(B * H * W, 16)[local[rows]][..., :10].float()
+        return cand
+
     res = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("PNX_DECODE_TORCH_SORT", mode)
-        dec = PackedDecoder([1, 2], [[0.5], [0.5, 0.5]], cfg, True, [16, 16])
-        res[mode] = dec(packed)
-    for a, b in zip(res["0"], res["1"]):
-        assert a["box3d_lidar"].shape[0] > 0
-        for k in ("box3d_lidar", "scores", "label_preds"):
-            assert torch.equal(a[k], b[k]), k
+    for mode, env in (("topk", {}), ("keysort", {"PNX_DECODE_TOPK": "0"}), ("torchsort", {"PNX_DECODE_TOPK": "0", "PNX_DECODE_TORCH_SORT": "1"})):
+        for k in ("PNX_DECODE_TOPK", "PNX_DECODE_TORCH_SORT"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        dec = PackedDecoder(ncls, [[0.5], [0.5, 0.5]], cfg, True, [16, 16])
+        assert dec.selection == mode
+        if kind == "dense":
+            res[mode] = dec(packed)
+        else:
+            pend = dec.launch_lazy(dense, evaluator)
+            res[mode] = pend.result()
+            assert int(pend.flag_h[0]) == 0
+    for mode in ("keysort", "torchsort"):
+        for a, b in zip(res["topk"], res[mode]):
+            assert a["box3d_lidar"].shape[0] > 0
+            for k in ("box3d_lidar", "scores", "label_preds"):
+                assert torch.equal(a[k], b[k]), (mode, k)
 
 
 def test_launch_plans_equal_the_python_launch_loop(monkeypatch):

@@ -1,8 +1,9 @@
-"""CPU: host-side packing helpers (plain torch, no GPU): the second-convolution weight layout of the lazy SepHead evaluator and the lazy
-flavour of the decoder's task descriptor."""
+"""CPU: host-side packing helpers (plain torch, no GPU): the second-convolution weight layout of the lazy SepHead evaluator, the lazy
+flavour of the decoder's task descriptor and the decoder's host layout (descriptors, key offsets, lists per task)."""
 import struct
 
 import numpy as np
+import pytest
 import torch
 
 from pillarnext_amd import ops
@@ -35,6 +36,37 @@ def test_lazy_task_descriptor_points_at_the_class_map_only():
     d, z = struct.unpack("6i6f6fi4f3i", dense), struct.unpack("6i6f6fi4f3i", lazy)
     assert d[:23] == z[:23]                                  # geometry, thresholds, range, rectifier: the same
     assert d[-3:] == (11, 10, 0) and z[-3:] == (1, 0, 1)     # o_hm, o_iou, lazy: [reg .. vel | iou | hm] vs [iou | hm]
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("num_classes", [[1, 2], [1, 2, 2, 1, 2, 2]])
+def test_decoder_host_layout(num_classes, B):
+    """PackedDecoder.host_layout (what launch, launch_lazy and launch_lazy_fused all start from) against the layout stated here: lists
+    s = sample * nc_total + class; the keys of task t are the B*H_t*W_t cells of its map, tasks concatenated in order."""
+    from pillarnext_amd.decode import PackedDecoder
+
+    T, nc_total = len(num_classes), sum(num_classes)
+    shapes = [(8, 8), (4, 6), (5, 3), (8, 8), (2, 7), (6, 4)][:T]                        # unequal maps per task
+    lazy_ch, dense_ch = [16, 8, 16, 4, 16, 16][:T], [16, 17, 13, 16, 14, 15][:T]
+    rect = [[0.5 + 0.01 * t] * n for t, n in enumerate(num_classes)]
+    cfg = dict(nms=dict(nms_pre_max_size=7, nms_post_max_size=3, nms_iou_threshold=[[0.2] * n for n in num_classes]), score_threshold=0.1,
+               pc_range=[-25.6, -25.6], voxel_size=[0.1, 0.1], out_size_factor=[8, 4, 8, 2, 8, 8][:T], post_center_limit_range=[-30, -30, -10, 30, 30, 10])
+    dec = PackedDecoder(num_classes, rect, cfg, True, dense_ch)
+    owner = []                                                                           # the task that owns class c
+    for t, n in enumerate(num_classes):
+        owner += [t] * n
+    want_offs = [int(v) for v in np.concatenate([[0], np.cumsum([B * h * w for h, w in shapes])])]
+    for lazy, channels in ((True, lazy_ch), (False, dense_ch)):
+        lay = dec.host_layout(lazy, B, shapes, channels)
+        assert lay.S == B * nc_total
+        assert list(lay.offs) == want_offs                                               # running sum of B*H*W
+        assert list(lay.kofs) == [want_offs[owner[s % nc_total]] for s in range(lay.S)]  # offset of the task that owns class s % nc_total
+        assert len(lay.segs) == T and sorted(s for rows in lay.segs for s in rows) == list(range(lay.S))       # disjoint, cover range(S)
+        for t, rows in enumerate(lay.segs):
+            assert list(rows) == sorted(rows) and all(owner[s % nc_total] == t for s in rows)
+        for t, (H, W) in enumerate(shapes):
+            assert lay.descs[t] == pack_task(channels[t], True, num_classes[t], sum(num_classes[:t]), H, W, cfg["out_size_factor"][t], cfg["voxel_size"],
+                                             cfg["pc_range"], 0.1, cfg["post_center_limit_range"], rect[t], lazy=lazy)
 
 
 def test_launch_table_structures_mirror_the_c_ones():
