@@ -5,6 +5,8 @@ from collections import OrderedDict
 
 import torch
 
+from .models import _SpConv2d
+
 
 def extract_state_dict(checkpoint):
     if isinstance(checkpoint, OrderedDict):
@@ -29,8 +31,6 @@ def load_checkpoint(model, filename, map_location=None, strict=False):
     target = model.module if hasattr(model, "module") else model
     # files written by save_checkpoint say which layout their sparse-conv weights are in; the shapes alone cannot when Cin == kH == kW
     layout = checkpoint.get("meta", {}).get("pnx_conv_layout") if isinstance(checkpoint, dict) and isinstance(checkpoint.get("meta"), dict) else None
-    from .models import _SpConv2d
-
     convs = [m for m in target.modules() if isinstance(m, _SpConv2d)] if layout in ("spconv", "dense") else []
     for m in convs:
         m.assume_layout = layout
@@ -53,8 +53,6 @@ def save_checkpoint(model, filename, optimizer=None, scheduler=None, meta=None, 
     target = model.module if hasattr(model, "module") else model
     sd = OrderedDict((k, v.cpu()) for k, v in target.state_dict().items())
     if layout == "spconv":
-        from .models import _SpConv2d
-
         for name, m in target.named_modules():
             if isinstance(m, _SpConv2d):
                 k = (name + "." if name else "") + "weight"

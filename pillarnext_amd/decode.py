@@ -5,7 +5,6 @@ sort + top pre_max, rotated NMS, top post_max, task merge with label offsets), r
 batch needs one key kernel per task, ONE device sort, one box kernel, ONE batched NMS and ONE device->host copy."""
 import collections
 import ctypes
-import os
 import struct
 import weakref
 
@@ -13,6 +12,7 @@ import torch
 
 from . import ops
 from ._lib import PnxError, check, lib, ptr, stream_ptr
+from .switches import on
 
 _SIGN = -0x8000000000000000   # keys are unsigned: as int64 they sort (and search) as unsigned with the sign bit flipped
 
@@ -71,10 +71,10 @@ class PackedDecoder:
         # (score key, key index), lists that hold fewer than pre_max valid keys finish after the first pass) -- exactly the selection of
         # a stable sort + cut (tests/test_gpu_decode.py::test_segmented_topk_equals_the_full_stable_sort).  PNX_DECODE_TOPK=0 selects the
         # bit-ranged stable key sort of all keys (pnx_sort_keys), PNX_DECODE_TORCH_SORT=1 the generic 64-bit torch.sort (cross-checks).
-        if os.environ.get("PNX_DECODE_TOPK", "1") == "1" and self.pre_max <= 4096:
+        if on("PNX_DECODE_TOPK") and self.pre_max <= 4096:
             self.selection = "topk"
         else:
-            self.selection = "torchsort" if os.environ.get("PNX_DECODE_TORCH_SORT", "0") == "1" else "keysort"
+            self.selection = "torchsort" if on("PNX_DECODE_TORCH_SORT") else "keysort"
         self._dev = {}   # Layout per (kind, batch, element dtype, (C, H, W) per task, device); launch_lazy_fused's scratch under ("lazy_fused", ...)
         self._ws = {}    # selection workspaces, grown on demand
         self._tptr = {}

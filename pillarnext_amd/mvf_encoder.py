@@ -17,8 +17,6 @@ Same class names, constructor arguments and state-dict keys as the reference.  W
     bf16, the 48 / 96 / 192 channels zero-padded to the kernels' 64 / 128 / 256: _HipViewNet), in training the masked-dense blocks of models.py
     (spconv is absent from the image; like the backbone that part is unpinned); the two PointNets: torch Linear (rocBLAS) + BatchNorm + ReLU.
 CUDA tensors only: there is no CPU path."""
-import os
-
 import numpy as np
 import torch
 from torch import nn
@@ -26,7 +24,10 @@ from torch.nn import functional as F
 
 from . import ops
 from ._lib import PNX_GROUP_CYLINDER_CLAMP, PNX_GROUP_PILLAR_CLAMP
+from .fused import _fold_bn, _HipConv3x3
+from .models import SparseBasicBlock, SparseConvBlock, _Seq
 from .reader import PFNLayer
+from .switches import on
 from .voxel_encoder import _device_points, batch_of, grid_of
 
 
@@ -121,27 +122,25 @@ class _HipViewNet:
     SingleView's `blocks`; rebuilt when its parameters change.  Inference only."""
 
     def __init__(self, blocks, dtype=torch.bfloat16):
-        from .models import SparseBasicBlock, SparseConvBlock, _fold_bn, _HipConv3x3
-
         self.dtype, self.stages = dtype, []
         self.version = _params_version(blocks)
         for seq in blocks:
             mods = []
             for m in seq:
                 if isinstance(m, SparseConvBlock):
-                    mods.append(("conv", self._conv(m.conv, m.norm, _fold_bn, _HipConv3x3), m.stride, m.subm))
+                    mods.append(("conv", self._conv(m.conv, m.norm), m.stride, m.subm))
                 elif isinstance(m, SparseBasicBlock):
-                    mods.append(("block", self._conv(m.block1.conv, m.block1.norm, _fold_bn, _HipConv3x3), self._conv(m.conv2, m.norm2, _fold_bn, _HipConv3x3)))
+                    mods.append(("block", self._conv(m.block1.conv, m.block1.norm), self._conv(m.conv2, m.norm2)))
                 else:
                     raise ops.PnxError(f"_HipViewNet: unexpected module {type(m).__name__}")
             self.stages.append(mods)
         self.cin = self.stages[0][0][1].cin
         self.cout_true = blocks[-1][-1].norm2.num_features if hasattr(blocks[-1][-1], "norm2") else blocks[-1][-1].norm.num_features
 
-    def _conv(self, conv, norm, fold, HipConv):
+    def _conv(self, conv, norm):
         if tuple(conv.kernel_size) != (3, 3) or tuple(conv.padding) != (1, 1) or conv.bias is not None:
             raise ops.PnxError("_HipViewNet: 3x3 / pad 1 / bias-free convolutions only")
-        w, b = fold(conv.weight, norm)
+        w, b = _fold_bn(conv.weight, norm)
         co, ci = w.shape[:2]
         cop, cip = _pad_to(co), _pad_to(ci)
         stride = int(conv.stride[0])
@@ -152,13 +151,11 @@ class _HipViewNet:
         wp[:co, :ci] = w
         bp = torch.zeros((cop,), dtype=torch.float32, device=w.device)
         bp[:co] = b
-        return HipConv(wp, bp, stride, dtype=self.dtype).to(w.device)
+        return _HipConv3x3(wp, bp, stride, dtype=self.dtype).to(w.device)
 
     @staticmethod
     def supported(blocks):
         try:
-            from .models import SparseBasicBlock, SparseConvBlock
-
             for seq in blocks:
                 for m in seq:
                     if isinstance(m, SparseConvBlock):
@@ -208,8 +205,6 @@ class SingleView(nn.Module):
     def __init__(self, in_channels, num_filters, layer_nums, ds_layer_strides, ds_num_filters, kernel_size, mode, voxel_size, pc_range, norm_cfg=None,
                  act_cfg=None):
         super().__init__()
-        from .models import SparseBasicBlock, SparseConvBlock, _Seq
-
         self.mode = mode
         self.voxel_size = np.array(voxel_size[:2])
         self.bias = np.array(pc_range[:2])
@@ -281,7 +276,7 @@ class SingleView(nn.Module):
         if not (self.training or torch.is_grad_enabled() and x.requires_grad) and x.dtype in ops._DT:
             return ops.bilinear_gather(x.contiguous(memory_format=torch.channels_last), pos, self.bias, self.voxel_size, unq, unq_inv, int(self.ds_rate))
         if (torch.is_grad_enabled() and x.requires_grad and x.is_cuda and x.dtype in ops._DT and not pos.requires_grad
-                and os.environ.get("PNX_TRAIN_BILINEAR_HIP") != "0"):
+                and on("PNX_TRAIN_BILINEAR_HIP")):
             # training: the eval kernel forward, its gradient w.r.t. the map on pnx_bilinear_gather_backward
             return ops.BilinearGather.apply(x.contiguous(memory_format=torch.channels_last), pos, self.bias, self.voxel_size, unq, unq_inv, int(self.ds_rate))
         vs = torch.from_numpy(self.voxel_size).type_as(pos).to(pos.device)

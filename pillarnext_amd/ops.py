@@ -751,6 +751,121 @@ def conv3x3_masked(x, wfrag, bias, cout, stride=1, mask=None, residual=None, rel
     return y
 
 
+# --------------------------------------------------------------------------------------------- train-mode masked BatchNorm (csrc/masked_bn.hip)
+# One call per launch of include/pnx.h's masked_bn family, in the order the autograd node (train_nodes._MaskedBNActFn) issues them:
+#   forward   stats -> reduce -> [all-reduce of the sums] -> finalize -> apply
+#   backward  bwd_stats -> reduce -> [all-reduce of a copy] -> bwd_finalize -> bwd_apply
+# Maps: (B,C,H,W) channels_last bf16 / fp32 with C in MASKED_BN_CHANNELS; mask: flat fp32 [B*H*W] (0 = inactive) or None = every site active.
+MASKED_BN_CHANNELS = (8, 16, 32, 64, 128, 256)
+
+
+def _bn_maps(what, x, mask, *like_x):
+    """Validator -> (n_sites, C, PNX_BF16 / PNX_F32): x as above, the mask flat fp32 or None, every other map None or of x's dtype, shape and layout."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] in MASKED_BN_CHANNELS
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        raise PnxError(f"{what}: x must be a channels_last bf16 / fp32 CUDA map (B,C,H,W) with C in {MASKED_BN_CHANNELS}")
+    n = x.shape[0] * x.shape[2] * x.shape[3]
+    if mask is not None and not (mask.is_cuda and mask.dtype == torch.float32 and mask.dim() == 1 and mask.numel() == n and mask.is_contiguous()):
+        raise PnxError(f"{what}: the mask must be a flat fp32 CUDA vector of B*H*W = {n} values, or None")
+    for t in like_x:
+        if t is not None and not (t.is_cuda and t.dtype == x.dtype and t.shape == x.shape and t.is_contiguous(memory_format=torch.channels_last)):
+            raise PnxError(f"{what}: the residual and the gradient must have x's dtype, shape and channels_last layout")
+    return n, x.shape[1], _DT[x.dtype]
+
+
+def _bn_vecs(what, n, *vecs, dtype=torch.float32):
+    """Validator: every vector that is given is a contiguous CUDA vector of n values (fp32 unless said otherwise)."""
+    for v in vecs:
+        if v is not None and not (v.is_cuda and v.dtype == dtype and v.dim() == 1 and v.numel() == n and v.is_contiguous()):
+            raise PnxError(f"{what}: needs contiguous {str(dtype).split('.')[-1]} CUDA vectors of {n} values")
+
+
+def masked_bn_blocks():
+    """Rows of the partial sums masked_bn_stats / masked_bn_bwd_stats write (their grid size)."""
+    return int(lib().pnx_masked_bn_blocks())
+
+
+def masked_bn_stats(x, mask, center):
+    """partials fp32 (blocks, 2C + 1): per workgroup [sum d | sum d^2 | active sites] with d = x - center (fp32 (C), or None = 0)."""
+    n, C, dt = _bn_maps("masked_bn_stats", x, mask)
+    _bn_vecs("masked_bn_stats", C, center)
+    part = torch.empty((masked_bn_blocks(), 2 * C + 1), dtype=torch.float32, device=x.device)
+    check(lib().pnx_masked_bn_stats(ptr(x), dt, ptr(mask), n, C, ptr(center), ptr(part), stream_ptr()), "pnx_masked_bn_stats")
+    return part
+
+
+def masked_bn_reduce(part):
+    """fp64 (cols): the rows of a partials array added in a fixed order -- what is all-reduced under SyncBatchNorm."""
+    if not (part.is_cuda and part.dtype == torch.float32 and part.dim() == 2 and part.is_contiguous() and part.shape[1] // 2 in MASKED_BN_CHANNELS):
+        raise PnxError(f"masked_bn_reduce: the partials must be a contiguous fp32 CUDA matrix of 2C or 2C + 1 columns with C in {MASKED_BN_CHANNELS}")
+    rows, cols = part.shape
+    s = torch.empty((cols,), dtype=torch.float64, device=part.device)
+    check(lib().pnx_masked_bn_reduce(ptr(part), rows, cols, ptr(s), stream_ptr()), "pnx_masked_bn_reduce")
+    return s
+
+
+def masked_bn_finalize(sums, center, weight, bias, eps, momentum, running_mean, running_var, num_batches_tracked):
+    """(mean, invstd, scale, shift (C each), count (1)) fp32 from sums = [sum d | sum d^2 | count] around `center` (None = 0), and torch's update of the
+    running statistics in place (num_batches_tracked += 1 when given)."""
+    C = (sums.numel() - 1) // 2
+    _bn_vecs("masked_bn_finalize", 2 * C + 1, sums, dtype=torch.float64)
+    _bn_vecs("masked_bn_finalize", C, center, weight, bias, running_mean, running_var)
+    nbt = num_batches_tracked
+    if C not in MASKED_BN_CHANNELS or (nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1)):
+        raise PnxError(f"masked_bn_finalize: 2C + 1 sums with C in {MASKED_BN_CHANNELS}, num_batches_tracked an int64 CUDA scalar")
+    vec = torch.empty((4 * C + 1,), dtype=torch.float32, device=sums.device)
+    mean, invstd, scale, shift, cnt = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:4 * C], vec[4 * C:]
+    check(lib().pnx_masked_bn_finalize(ptr(sums), C, ptr(center), ptr(weight), ptr(bias), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                                       ptr(nbt), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(cnt), stream_ptr()), "pnx_masked_bn_finalize")
+    return mean, invstd, scale, shift, cnt
+
+
+def masked_bn_apply(x, residual, mask, scale, shift, relu):
+    """y = [relu](x * scale + shift [+ residual]) at the active sites, zeros elsewhere; y like x."""
+    n, C, dt = _bn_maps("masked_bn_apply", x, mask, residual)
+    _bn_vecs("masked_bn_apply", C, scale, shift)
+    y = torch.empty_like(x)
+    check(lib().pnx_masked_bn_apply(ptr(x), ptr(residual), dt, ptr(mask), n, C, ptr(scale), ptr(shift), 1 if relu else 0, ptr(y), stream_ptr()),
+          "pnx_masked_bn_apply")
+    return y
+
+
+def masked_bn_bwd_stats(gy, x, residual, mask, scale, shift, mean, invstd, relu):
+    """partials fp32 (blocks, 2C): [sum g | sum g * xhat] with g = gy * [pre-activation > 0], xhat = (x - mean) * invstd."""
+    n, C, dt = _bn_maps("masked_bn_bwd_stats", x, mask, residual, gy)
+    _bn_vecs("masked_bn_bwd_stats", C, scale, shift, mean, invstd)
+    part = torch.empty((masked_bn_blocks(), 2 * C), dtype=torch.float32, device=x.device)
+    check(lib().pnx_masked_bn_bwd_stats(ptr(gy), ptr(x), ptr(residual), dt, ptr(mask), n, C, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), 1 if relu else 0,
+                                        ptr(part), stream_ptr()), "pnx_masked_bn_bwd_stats")
+    return part
+
+
+def masked_bn_bwd_finalize(sums_local, sums_global, count):
+    """(dgamma, dbeta, mean_g, mean_gx) fp32 (C each): the parameter gradients from the LOCAL sums [sum g | sum g xhat] (fp64 (2C)), the means over
+    `count` active sites from the global ones (None: the local ones)."""
+    C = sums_local.numel() // 2
+    _bn_vecs("masked_bn_bwd_finalize", 2 * C, sums_local, sums_global, dtype=torch.float64)
+    _bn_vecs("masked_bn_bwd_finalize", 1, count)
+    if C not in MASKED_BN_CHANNELS:
+        raise PnxError(f"masked_bn_bwd_finalize: 2C sums with C in {MASKED_BN_CHANNELS}")
+    vec = torch.empty((4 * C,), dtype=torch.float32, device=sums_local.device)
+    dgamma, dbeta, mg, mgx = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:]
+    check(lib().pnx_masked_bn_bwd_finalize(ptr(sums_local), ptr(sums_global), C, ptr(count), ptr(dgamma), ptr(dbeta), ptr(mg), ptr(mgx), stream_ptr()),
+          "pnx_masked_bn_bwd_finalize")
+    return dgamma, dbeta, mg, mgx
+
+
+def masked_bn_bwd_apply(gy, x, residual, mask, scale, shift, mean, invstd, relu, mean_g, mean_gx, want_residual_grad=False):
+    """(dx like x, the residual's gradient like it or None) of masked_bn_apply from the upstream gradient gy and the means of masked_bn_bwd_finalize."""
+    n, C, dt = _bn_maps("masked_bn_bwd_apply", x, mask, residual, gy)
+    _bn_vecs("masked_bn_bwd_apply", C, scale, shift, mean, invstd, mean_g, mean_gx)
+    dx = torch.empty_like(x)
+    gres = torch.empty_like(residual) if residual is not None and want_residual_grad else None
+    check(lib().pnx_masked_bn_bwd_apply(ptr(gy), ptr(x), ptr(residual), dt, ptr(mask), n, C, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), 1 if relu else 0,
+                                        ptr(mean_g), ptr(mean_gx), ptr(dx), ptr(gres), stream_ptr()), "pnx_masked_bn_bwd_apply")
+    return dx, gres
+
+
 # --------------------------------------------------------------------------------------------- sparse 3-D convolution (csrc/sparse3d.hip)
 def _i3(v):
     return (ctypes.c_int32 * 3)(*[int(a) for a in v])

@@ -21,6 +21,7 @@ from torch.nn import functional as F
 
 from . import ops
 from ._lib import PNX_NCHW, PNX_NHWC, PnxError, make_geom
+from .switches import on
 
 
 class PFNLayer(nn.Module):
@@ -109,9 +110,7 @@ class PillarFeatureNet(nn.Module):
 
     @staticmethod
     def _unfused_training():
-        import os
-
-        return os.environ.get("PNX_TRAIN_FUSED", "1") == "0"  # the round-1 path: torch Linear/BatchNorm1d + HIP scatter-max
+        return not on("PNX_TRAIN_FUSED")  # the round-1 path: torch Linear/BatchNorm1d + HIP scatter-max
 
     def folded_params(self):
         """BN-folded parameter buffer, re-folded whenever a parameter/buffer changed (tensor version counters)."""

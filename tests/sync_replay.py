@@ -1,6 +1,6 @@
-"""World N in ONE process, one rank after the other -- test helper for the synchronised BatchNorm nodes (models._MaskedBNActFn, pfn_train.FusedPFNTrain).
+"""World N in ONE process, one rank after the other -- test helper for the synchronised BatchNorm nodes (train_nodes._MaskedBNActFn, pfn_train.FusedPFNTrain).
 
-Both nodes reach their collective through dist_utils.all_reduce_sum(t, group), imported at call time, and hand on whatever object enable_sync() was
+Both nodes reach their collective through dist_utils.all_reduce_sum(t, group), looked up at call time, and hand on whatever object enable_sync() was
 given.  Threads cannot stand in for ranks: the backward nodes of every caller run on the device's one autograd worker thread, so a barrier inside
 a node would deadlock.  Replay instead:
 

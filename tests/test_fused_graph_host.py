@@ -44,7 +44,7 @@ def test_kernel_routing_and_workspace_policy():
 
 
 def test_bn_fold_equals_conv_then_bn():
-    from pillarnext_amd.models import _fold_bn
+    from pillarnext_amd.fused import _fold_bn
 
     torch.manual_seed(0)
     conv = torch.nn.Conv2d(8, 12, 3, padding=1, bias=True)

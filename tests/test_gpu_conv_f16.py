@@ -131,10 +131,11 @@ def test_fp16_detector_runs_on_the_hip_kernels_and_matches_miopen():
     (PNX_HIP_CONV=0) to fp16 rounding of reordered fp32 sums."""
     from test_gpu_configs import _waymo_fused
     from pillarnext_amd import models, synth
+    from pillarnext_amd.fused import _HipConv3x3, _HipDeconv2x2
 
     det, fused = _waymo_fused("C4", F16)      # C4 geometry (1504^2), fp16 network; C5 differs in the point count only
-    assert all(isinstance(m, models._HipConv3x3) for mods in fused.stages for m in mods) and isinstance(fused.shared, models._HipConv3x3)
-    assert all(isinstance(d, models._HipDeconv2x2) for d in fused.task_deblock) and fused.lazy_head and fused._plan_ok() and fused._head_plan_ok()
+    assert all(isinstance(m, _HipConv3x3) for mods in fused.stages for m in mods) and isinstance(fused.shared, _HipConv3x3)
+    assert all(isinstance(d, _HipDeconv2x2) for d in fused.task_deblock) and fused.lazy_head and fused._plan_ok() and fused._head_plan_ok()
     assert fused.stages[0][0].wfrag.dtype == F16
     B = 2
     pts = torch.from_numpy(synth.make_batch("C4", B, "sweep")).cuda()
@@ -149,7 +150,7 @@ def test_fp16_detector_runs_on_the_hip_kernels_and_matches_miopen():
             ref_net = models.FusedPillarNeXt(det, dtype=F16).cuda().eval()
         finally:
             os.environ.pop("PNX_HIP_CONV", None)
-        assert not any(isinstance(m, models._HipConv3x3) for mods in ref_net.stages for m in mods)
+        assert not any(isinstance(m, _HipConv3x3) for mods in ref_net.stages for m in mods)
         pa = fused.forward_preds(pts, B, lazy=False)
         pb = ref_net.forward_preds(pts, B)
     for tok in ("a", "b"):

@@ -239,7 +239,7 @@ def test_training_step_end_to_end():
 def test_training_graph_on_the_fused_masked_bn_kernels(monkeypatch):
     """The training graph with the masked BatchNorm + residual + ReLU node on the HIP kernels (csrc/masked_bn.hip; channels_last maps) against
     the same detector with the node in its torch statement:
-      fp32:  channels_last + HIP kernels (masked BN node; 3x3 convolutions on the three-bf16-product node, models._MaskedConv3x3F32Fn)  vs  NCHW + torch node +
+      fp32:  channels_last + HIP kernels (masked BN node; 3x3 convolutions on the three-bf16-product node, train_nodes._MaskedConv3x3F32Fn)  vs  NCHW + torch node +
              MIOpen fp32 convolutions -- same loss to 1e-5, every parameter gradient within 8 % norm-wise (this freshly initialised net amplifies ANY rounding difference ~1e4-1e5 x: what is left
              is MIOpen running other fp32 solvers for NHWC than for NCHW, measured 0.5-2 %, and the three-product node's 4e-6 per layer, measured 2.5-3.9 %)
       bf16:  autocast + channels_last, HIP kernels  vs  the torch node in the same graph -- loss within 0.5 %, gradients within the run-to-run

@@ -138,7 +138,7 @@ def _check_against_fp64(r, tag):
 
 @pytest.mark.parametrize("cin,cout,stride,subm,shape", BACKBONE)
 def test_six_product_node_against_fp64(cin, cout, stride, subm, shape, monkeypatch):
-    """models._MaskedConv3x3F32Fn under PNX_TRAIN_F32_PIECES=3 on the nine cases of the three-product test (which holds that node to 2^-14 / 3e-5)."""
+    """train_nodes._MaskedConv3x3F32Fn under PNX_TRAIN_F32_PIECES=3 on the nine cases of the three-product test (which holds that node to 2^-14 / 3e-5)."""
     r = _run_backbone(cin, cout, stride, subm, shape, monkeypatch)
     _check_against_fp64(r, f"{cin}->{cout} s{stride}")
 
@@ -193,7 +193,8 @@ def test_default_is_the_three_product_node(monkeypatch):
     import torch.nn.functional as F
 
     from pillarnext_amd import ops
-    from pillarnext_amd.models import _split_pack, x3_conv
+    from pillarnext_amd.models import x3_conv
+    from pillarnext_amd.train_nodes import _split_pack
 
     for case in (0, 4):
         runs = [_run_backbone(*BACKBONE[case], monkeypatch, pieces=p) for p in (None, "2")]

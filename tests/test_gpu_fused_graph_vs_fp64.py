@@ -317,6 +317,7 @@ def test_every_layer_of_the_fused_graph_against_fp64(dtype, monkeypatch):
     bar and the bit-zero check), again without the stage workspaces (bit-equal recordings); last, the planned path on a second instance against the
     verified launch-by-launch path, detections bit for bit."""
     from pillarnext_amd import models, ops
+    from pillarnext_amd.fused import _HipConv3x3, _HipDeconv2x2, _HipSepHeadOut
 
     torch.manual_seed(21)
     torch.backends.cudnn.deterministic = True
@@ -324,9 +325,9 @@ def test_every_layer_of_the_fused_graph_against_fp64(dtype, monkeypatch):
     random_bn_(det, 22)
     assert [int(v) for v in det.reader.grid_size] == [NY, NX]
     fused = models.FusedPillarNeXt(det, dtype=dtype).cuda().eval()
-    assert all(isinstance(m, models._HipConv3x3) for mods in fused.stages for m in mods) and fused.sparse_ws and fused.tile_lists
-    assert isinstance(fused.shared, models._HipConv3x3) and all(isinstance(m, models._HipDeconv2x2) for m in fused.task_deblock)
-    assert all(isinstance(m, models._HipSepHeadOut) for m in list(fused.task_conv2) + list(fused.lazy_conv2)) and fused.lazy_head
+    assert all(isinstance(m, _HipConv3x3) for mods in fused.stages for m in mods) and fused.sparse_ws and fused.tile_lists
+    assert isinstance(fused.shared, _HipConv3x3) and all(isinstance(m, _HipDeconv2x2) for m in fused.task_deblock)
+    assert all(isinstance(m, _HipSepHeadOut) for m in list(fused.task_conv2) + list(fused.lazy_conv2)) and fused.lazy_head
     for blk in det.backbone.blocks:
         c = blk[0].conv.out_channels
         assert ops.conv_tile_rows(c, c, 1) == TILE_H[c]

@@ -1,4 +1,4 @@
-"""GPU: the training-mode masked 3x3 convolution node (models._MaskedConv3x3Fn: forward, dgrad and the stride-1 wgrad on the product's HIP
+"""GPU: the training-mode masked 3x3 convolution node (train_nodes._MaskedConv3x3Fn: forward, dgrad and the stride-1 wgrad on the product's HIP
 kernels, the stride-2 backward on MIOpen) against torch's own autograd of F.conv2d in FP32 on the same bf16-rounded operands, on LiDAR-like masks (sparse_conv.py:16-63:
 SubMConv2d / SparseConv2d compute at the active sites only).  bf16 tolerances: outputs and input gradients to 2 bf16 ulps of a K = 9*Cin
 fp32 sum, weight gradients relative to the largest entry."""
@@ -70,7 +70,7 @@ def test_masked_conv_node_matches_fp32_autograd(cin, cout, stride, subm, shape):
                                                        (256, 256, 1, True, (2, 23, 33)), (64, 128, 2, False, (2, 50, 66)), (128, 256, 2, False, (1, 37, 41)),
                                                        (256, 256, 2, False, (2, 24, 64)), (64, 64, 1, True, (1, 16, 32)), (128, 128, 1, True, (1, 8, 33))])
 def test_fp32_node_on_three_bf16_products_against_fp64(cin, cout, stride, subm, shape):
-    """models._MaskedConv3x3F32Fn (pnx_split_f32 + pnx_conv3x3_x3 + three wgrad calls) against the fp64 autograd of mask_out * conv2d on the SAME fp32
+    """train_nodes._MaskedConv3x3F32Fn (pnx_split_f32 + pnx_conv3x3_x3 + three wgrad calls) against the fp64 autograd of mask_out * conv2d on the SAME fp32
     operands.  Tolerance: 2^-14 of the sum of |terms| (each product carries 2^-16 from the dropped low x low term and the halves' rounding; the bound is
     on the absolute sum because cancellation does not shrink the error), and MIOpen's own fp32 result must not be more than 64 x closer on average."""
     import torch.nn.functional as F
@@ -161,7 +161,7 @@ def test_dense_fp32_layers_on_the_three_product_node(c, shape, shared):
                                            (4, (1, 8, 16), torch.float32), (2, (2, 40, 33), torch.bfloat16), (3, (1, 30, 47), torch.bfloat16),
                                            (1, (1, 5, 3), torch.bfloat16)])
 def test_sephead_output_convolution_kernels(k, shape, dtype):
-    """csrc/head_train.hip (models._SmallKConv3x3Fn) against the fp64 autograd of F.conv2d on the same operands: fp32 maps to 1e-5 of the sum of |terms|,
+    """csrc/head_train.hip (train_nodes._SmallKConv3x3Fn) against the fp64 autograd of F.conv2d on the same operands: fp32 maps to 1e-5 of the sum of |terms|,
     bf16 maps (fp32 accumulation of bf16 inputs, output rounded once) to one bf16 ulp on top."""
     import torch.nn.functional as F
 

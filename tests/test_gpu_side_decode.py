@@ -1,4 +1,4 @@
-"""GPU: the decoder on its own stream, launched behind the next batch's reader (FusedPillarNeXt.decode_on_side_stream, the default; models._DeferredDecode)
+"""GPU: the decoder on its own stream, launched behind the next batch's reader (FusedPillarNeXt.decode_on_side_stream, the default; fused._DeferredDecode)
 in a pipelined serving loop returns the same detections, bit for bit, as the single-stream loop -- also when a result is asked for before the next
 batch is enqueued (the deferred launch is flushed) and when a pending result is dropped."""
 import pytest
@@ -46,7 +46,8 @@ def test_side_stream_decode_equals_single_stream():
 
 def test_deferred_decode_is_flushed_by_result_and_survives_a_dropped_pending():
     from pillarnext_amd import synth
-    from pillarnext_amd.models import FusedPillarNeXt, _DeferredDecode, build_pillarnext_b
+    from pillarnext_amd.fused import _DeferredDecode
+    from pillarnext_amd.models import FusedPillarNeXt, build_pillarnext_b
 
     cfg = synth.CONFIGS["C2"]
     torch.manual_seed(0)

@@ -1,6 +1,6 @@
 """GPU: the synchronised (world > 1) mode of the two hand-written BatchNorm paths against the fp64 statement of the JOINT batch:
 
-  models._MaskedBNActFn on csrc/masked_bn.hip (masked_bn_act, PNX_MASKED_BN_HIP=1): one forward and one backward collective;
+  train_nodes._MaskedBNActFn on csrc/masked_bn.hip (masked_bn_act, PNX_MASKED_BN_HIP=1): one forward and one backward collective;
   pfn_train.FusedPFNTrain on csrc/pfn_train.hip (PNX_TRAIN_FUSED=1): two forward and two backward collectives.
 
 World N runs in this one process, rank after rank, through tests/sync_replay.py (no process started, no collective backend initialised): the
@@ -157,7 +157,7 @@ def test_masked_bn_sync_with_different_running_means(monkeypatch, dtype):
     """Rank 1's running mean is half a channel std away from rank 0's (no buffer broadcast: broadcast_buffers=False, a per-rank warm-up, a
     hand-rolled loop).  The node sums around the rank's running mean; batch statistics, y, dx and the gradients must still be those of the joint
     batch, at the same bars, and each rank's running mean moves from its own old value.  Before the sums were re-centred to 0 in front of the
-    all-reduce (models._MaskedBNActFn._forward_hip) the ranks' sums were added as if they shared one centre, and the means were wrong by the
+    all-reduce (train_nodes._MaskedBNActFn._forward_hip) the ranks' sums were added as if they shared one centre, and the means were wrong by the
     shift times the other rank's share of the sites."""
     monkeypatch.setenv("PNX_MASKED_BN_HIP", "1")
     gen = torch.Generator(device="cuda").manual_seed(31 + (dtype == torch.bfloat16))

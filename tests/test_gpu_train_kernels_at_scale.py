@@ -332,7 +332,7 @@ FWD = [(64, 64, 1, (2, 512, 512)), (128, 128, 1, (2, 400, 400)), (256, 256, 1, (
 
 @pytest.mark.parametrize("cin,cout,stride,shape", FWD)
 def test_conv_nodes_forward_and_data_gradient_on_tickets(cin, cout, stride, shape, monkeypatch):
-    """models._MaskedConv3x3Fn (bf16) and _MaskedConv3x3F32Fn (x3, x6) with more than 3 x grid tiles: the stride-1 producer / consumer kernel (forward and
+    """train_nodes._MaskedConv3x3Fn (bf16) and _MaskedConv3x3F32Fn (x3, x6) with more than 3 x grid tiles: the stride-1 producer / consumer kernel (forward and
     data gradient, csrc/conv_pc.h) and the stride-2 data gradient (csrc/conv_dgrad_s2.h) take most of their tiles from tickets.  y and dx against fp64,
     bit-identical on repeat, exact zeros at inactive sites."""
     import torch.nn.functional as F
@@ -426,7 +426,7 @@ def test_ticket_ring_wraps_without_losing_tiles():
     import torch.nn.functional as F
 
     from pillarnext_amd import ops
-    from pillarnext_amd.models import _split_pack
+    from pillarnext_amd.train_nodes import _split_pack
 
     gen = torch.Generator(device="cuda").manual_seed(21)
     w64 = torch.randn((64, 64, 3, 3), device="cuda", generator=gen) * 0.06

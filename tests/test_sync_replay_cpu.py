@@ -1,4 +1,4 @@
-"""CPU: tests/sync_replay.py itself, and through it the synchronised mode of models._MaskedBNActFn's torch path (CPU tensors: three collectives,
+"""CPU: tests/sync_replay.py itself, and through it the synchronised mode of train_nodes._MaskedBNActFn's torch path (CPU tensors: three collectives,
 [sum x | count], [sum (x - mean)^2] forward and [sum g | sum g xhat] backward) at worlds 2 and 3 against the fp64 autograd statement of the JOINT
 batch, at the tolerances of test_dist_gloo.py::_worker_syncbn.  No process is started and no collective backend initialised."""
 import copy

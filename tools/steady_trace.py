@@ -23,7 +23,7 @@ def main():
         if len(starts) > nsteps:
             delim = name
             break
-    # the LAST delimiter belongs to the final batch, whose decoder is flushed at once instead of waiting behind a next reader (models._DeferredDecode):
+    # the LAST delimiter belongs to the final batch, whose decoder is flushed at once instead of waiting behind a next reader (fused._DeferredDecode):
     # that interval is short, so the window ends one delimiter earlier
     if len(starts) > nsteps + 2:
         starts = starts[:-1]
