@@ -289,7 +289,8 @@ class ASPPNeck(nn.Module):
 
     def forward(self, x):
         if x.requires_grad:
-            return torch.utils.checkpoint.checkpoint(self._forward, x, use_reentrant=False)
+            # context_fn: the BatchNorm nodes inside must sum around the same centre in the recomputation as in the forward (train_nodes.checkpoint_contexts)
+            return torch.utils.checkpoint.checkpoint(self._forward, x, use_reentrant=False, context_fn=train_nodes.checkpoint_contexts)
         return self._forward(x)
 
 

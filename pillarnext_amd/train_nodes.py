@@ -2,12 +2,34 @@
 blocks) call masked_conv / masked_bn_act in the backbone, x3_conv / dense_bn_act / smallk_conv in the neck and the head; each helper decides from
 the layer, the tensors and the switches (switches.py, read on every call) whether the product's kernel serves the call, and hands the module
 itself (MIOpen) the rest.  Every kernel is reached through its checked wrapper in ops.py."""
+import contextlib
+import threading
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import dist_utils, ops
 from .switches import on, train_f32_pieces
+
+
+_CKPT = threading.local()
+
+
+@contextlib.contextmanager
+def _ckpt_phase(phase):
+    prev = getattr(_CKPT, "phase", None)
+    _CKPT.phase = phase
+    try:
+        yield
+    finally:
+        _CKPT.phase = prev
+
+
+def checkpoint_contexts():
+    """context_fn of torch.utils.checkpoint.checkpoint(..., use_reentrant=False) for a region that holds _MaskedBNActFn nodes: tells the node whether it
+    runs in the region's forward or in its recomputation (which happens on the autograd engine's thread: the flag is per thread)."""
+    return _ckpt_phase("forward"), _ckpt_phase("recompute")
 
 
 class _MaskedBNActFn(torch.autograd.Function):
@@ -39,14 +61,22 @@ class _MaskedBNActFn(torch.autograd.Function):
         mflat = None if m is None else m.reshape(-1)
         # statistics around THIS rank's running mean: sum d, sum d^2 with d = x - centre, so that the fp32 partial sums carry deviations, not E[x^2]
         rm, rv = norm.running_mean, norm.running_var
-        s = ops.masked_bn_reduce(ops.masked_bn_stats(x, mflat, rm))        # [sum d | sum d^2 | count], fp64
+        # Inside a checkpointed region (ASPPNeck) the forward runs again during the backward, AFTER the first call moved the running mean: sums taken
+        # around the moved mean round differently, so mean / invstd / scale / shift, and with them the recomputed y that the backward of every later
+        # layer saves, would differ in their last bits from what the forward handed on.  The first call keeps its centre, the recomputation sums
+        # around that one (checkpoint_contexts below); the running statistics still move once per call, from their current values.
+        center, phase = rm, getattr(_CKPT, "phase", None)
+        if phase == "forward":
+            norm._pnx_ckpt_center = rm.clone()
+        elif phase == "recompute" and getattr(norm, "_pnx_ckpt_center", None) is not None:
+            center, norm._pnx_ckpt_center = norm._pnx_ckpt_center, None
+        s = ops.masked_bn_reduce(ops.masked_bn_stats(x, mflat, center))    # [sum d | sum d^2 | count], fp64
         group = norm.sync_group if getattr(norm, "sync", False) else False
-        center = rm
         if group is not False:
             # the batch statistics must not depend on the buffers, and nothing makes the ranks' running means equal (broadcast_buffers=False, a
             # per-rank warm-up, a hand-rolled loop): re-centre this rank's sums to centre 0 in fp64 before they are added to the others',
             # sum x = S1 + n c, sum x^2 = S2 + 2 c S1 + n c^2, and finalize around 0
-            c = rm.double()
+            c = center.double()
             s[C:2 * C] += 2.0 * c * s[:C] + s[2 * C] * c * c
             s[:C] += s[2 * C] * c
             dist_utils.all_reduce_sum(s, group)
