@@ -222,6 +222,35 @@ int pnx_scatter_max(const float* x, const int64_t* index, int64_t n, int32_t cha
 int pnx_scatter_max_backward(const float* grad_out, const int64_t* argmax, int64_t n, int32_t channels, int64_t num_pillars,
                              float* grad_x, pnx_stream_t stream);
 
+/* One per-point layer of the multi-view reader in TRAINING mode, the training twin of pnx_pfn_layer_eval (csrc/point_layer_train.hip):
+ *   z = x W^T      y = relu((z - mean) invstd gamma + beta)      gmax / argmax = pnx_scatter_max(y, inv) (lowest row wins ties; empty cell: 0 and n)
+ * with mean / invstd from the batch statistics of z, and its backward.  fp32 on the fp32 matrix instructions, no reduced-precision operand.
+ *   x (n, ldx) fp32, ldx >= cin: a column slice of a wider buffer is read in place.  w (cout, cin) fp32 as nn.Linear stores it; nothing packed is
+ *   kept between calls.  1 <= cin <= 576, 1 <= cout <= 256 (else PNX_ERR_UNSUPPORTED; every argument is checked before any HIP call).
+ *   prm (6, cout) fp32: mean | invstd | gamma | beta | D1 / n | D2 / n (the last two rows are read by pnx_point_layer_backward only).
+ * The protocol (host side: pillarnext_amd/ops.py PointLayer):
+ *   pnx_point_layer_stats           sums[0:cout] = sum z, sums[cout:2 cout] = sum z^2 over the rows, fp64: the host forms mean and the biased variance
+ *                                   from them (and would all-reduce these 2 cout doubles under SyncBatchNorm; no collective is issued here)
+ *   pnx_point_layer_forward         y (n, ldy) (may be NULL: then no (n, cout) tensor is written) and / or gmax (num_groups, cout) fp32 with argmax
+ *                                   (num_groups, cout) int64, both fully written; gmax needs inv (n) int64 and argmax
+ *   pnx_point_layer_backward_stats  dz = (dy + dgmax routed to the arg-max row) where the ReLU is open; sums = D1 = sum dz (= dbeta) | D2 = sum dz xhat
+ *                                   (= dgamma), fp64.  dy (n, lddy) and dgmax (num_groups, cout) may each be NULL, not both; they add
+ *   pnx_point_layer_backward        dxpre = gamma invstd (dz - D1/n - xhat D2/n); dw (cout, cin) = dxpre^T x; dx (n, lddx) = dxpre W (may be NULL)
+ * Every pass recomputes z: nothing of size (n, cout) lives between two calls (the backward call holds dxpre in its own workspace).
+ * Deterministic: no floating-point atomics, fixed summation orders; the workspace (pnx_point_layer_workspace_bytes(n, cin, cout, backward != 0 for
+ * pnx_point_layer_backward); 0 = unsupported sizes; 256-byte aligned) need not be cleared. */
+size_t pnx_point_layer_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t backward);
+int pnx_point_layer_stats(const float* x, int32_t ldx, int64_t n, int32_t cin, const float* w, int32_t cout, double* sums, void* workspace,
+                          size_t workspace_bytes, pnx_stream_t stream);
+int pnx_point_layer_forward(const float* x, int32_t ldx, int64_t n, int32_t cin, const float* w, int32_t cout, const float* prm, const int64_t* inv,
+                            int64_t num_groups, float* y, int32_t ldy, float* gmax, int64_t* argmax, pnx_stream_t stream);
+int pnx_point_layer_backward_stats(const float* x, int32_t ldx, int64_t n, int32_t cin, const float* w, int32_t cout, const float* prm, const float* dy,
+                                   int32_t lddy, const int64_t* inv, int64_t num_groups, const float* dgmax, const int64_t* argmax, double* sums,
+                                   void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+int pnx_point_layer_backward(const float* x, int32_t ldx, int64_t n, int32_t cin, const float* w, int32_t cout, const float* prm, const float* dy,
+                             int32_t lddy, const int64_t* inv, int64_t num_groups, const float* dgmax, const int64_t* argmax, float* dx, int32_t lddx,
+                             float* dw, void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+
 /* Scatter an existing (P,64) fp32 pillar list to the dense canvas (sparse_resnet.py:63-68). */
 int pnx_scatter_canvas(const float* feat_max, const int32_t* coords, const int32_t* num_pillars_dev, int64_t pillar_capacity,
                        int32_t batch, int32_t gy, int32_t gx, void* canvas, int32_t canvas_dtype, int32_t canvas_layout,

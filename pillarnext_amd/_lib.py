@@ -75,6 +75,11 @@ PROTOTYPES = {
     "pnx_scatter_max_workspace_bytes": (_sz, [_i64, _i64]),
     "pnx_scatter_max": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
     "pnx_scatter_max_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp]),
+    "pnx_point_layer_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "pnx_point_layer_stats": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "pnx_point_layer_forward": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "pnx_point_layer_backward_stats": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pnx_point_layer_backward": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "pnx_scatter_canvas": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "pnx_merge_sweeps_desc_bytes": (_sz, []),
     "pnx_merge_sweeps_workspace_bytes": (_sz, [_i64]),

@@ -9,13 +9,15 @@ Same class names, constructor arguments and state-dict keys as the reference.  W
     per-cell means and the 10-column decoration: ONE C call each (pnx_group_points, modes PILLAR_CLAMP / CYLINDER_CLAMP); MVFFeatureNet's range
     mask (mvf:290-297) is the call's prefilter and both views write their columns into one (N', 20) buffer -- the torch.cat of mvf:304 never runs;
   * the PFN layers of a view in eval mode: pnx_pfn_layer_eval (Linear + folded BatchNorm + ReLU + per-cell max; the concat [x, max[inv]] of a
-    non-last layer is read in place by the next one); in training they are reader.PFNLayer on the HIP scatter-max (autograd);
+    non-last layer is read in place by the next one); in training each layer is ONE autograd node on csrc/point_layer_train.hip (ops.PointLayer:
+    Linear + BatchNorm1d with batch statistics + ReLU + per-cell max, fp32; PNX_TRAIN_POINT_HIP=0 selects reader.PFNLayer on the HIP scatter-max);
   * sampling the view's map back at the points: pnx_bilinear_gather, in eval and as the forward of ops.BilinearGather in training, whose backward is
     pnx_bilinear_gather_backward (deterministic; PNX_TRAIN_BILINEAR_HIP=0 selects the torch statement over flat indices, which also serves when the
     positions need a gradient);
   * the per-view sparse ResNets: in eval mode the masked HIP convolution kernels of the PillarNeXt backbone (csrc/conv3x3.hip; BatchNorm folded,
     bf16, the 48 / 96 / 192 channels zero-padded to the kernels' 64 / 128 / 256: _HipViewNet), in training the masked-dense blocks of models.py
-    (spconv is absent from the image; like the backbone that part is unpinned); the two PointNets: torch Linear (rocBLAS) + BatchNorm + ReLU.
+    (spconv is absent from the image; like the backbone that part is unpinned); the two PointNets: in training the same fused node (pointnet2
+    hands over its per-pillar maximum and never writes the (N, 256) activation), otherwise torch Linear (rocBLAS) + BatchNorm + ReLU.
 CUDA tensors only: there is no CPU path."""
 import numpy as np
 import torch
@@ -40,7 +42,15 @@ class PointNet(nn.Module):
         self.norm = nn.BatchNorm1d(out_channels, eps=1e-3, momentum=0.01)
 
     def forward(self, points):
+        if points.is_cuda and ops.point_layer_serves(self, self.norm):         # training: the fused node of csrc/point_layer_train.hip
+            return ops.point_layer(points, self.linear, self.norm)[0]
         return F.relu(self.norm(self.linear(points)))
+
+    def cell_max(self, points, unq_inv, num_cells):
+        """scatter_max(forward(points), unq_inv)[0] (mvf:322): on the node the (N, C) activation is never written."""
+        if points.is_cuda and ops.point_layer_serves(self, self.norm):
+            return ops.point_layer(points, self.linear, self.norm, unq_inv, num_cells, want_y=False, want_max=True)[1]
+        return ops.scatter_max(self.forward(points), unq_inv, num_cells)[0]
 
 
 class _ClampView(nn.Module):
@@ -229,6 +239,18 @@ class SingleView(nn.Module):
 
     def cell_features(self, features, unq_inv, num_cells):
         """(P, C) = scatter_max over the cells of the PFN stack's output (mvf:187-188)."""
+        if self.training and features.is_cuda and all(ops.point_layer_serves(pfn, pfn.norm) for pfn in self.pfn_layers):
+            # training on the fused node (PNX_TRAIN_POINT_HIP): per layer Linear + BatchNorm1d + ReLU + cell max in one autograd node; the last
+            # layer's maximum IS the cell feature -- the feat_max[unq_inv] gather and the second scatter_max of the torch path do not run
+            x = features
+            for k, pfn in enumerate(self.pfn_layers):
+                last = k == len(self.pfn_layers) - 1
+                if pfn.last_vfe != last:
+                    raise ops.PnxError("SingleView: only the final PFN layer may be a last_layer")
+                y, g = ops.point_layer(x, pfn.linear, pfn.norm, unq_inv, num_cells, want_y=not last, want_max=True)
+                if last:
+                    return g
+                x = torch.cat([y, g[unq_inv]], dim=1)
         if self.training or torch.is_grad_enabled() and any(p.requires_grad for p in self.pfn_layers.parameters()):
             for pfn in self.pfn_layers:
                 features = pfn(features, unq_inv, num_cells)
@@ -332,7 +354,7 @@ class MVFFeatureNet(nn.Module):
         pv = self.pillarview(feat, pcoords, pinv, psize, batch_size)
         cv = self.cylinderview(feat, ccoords, cinv, csize, batch_size)
         x = torch.cat((self.pointnet1(feat), pv, cv), dim=-1)
-        pillar = ops.scatter_max(self.pointnet2(x), pinv, pcoords.shape[0])[0]
+        pillar = self.pointnet2.cell_max(x, pinv, pcoords.shape[0])
         ds = int(self.ds_rate)
         u = pcoords.long()
         H, W = int(psize[0]) // ds, int(psize[1]) // ds

@@ -266,6 +266,136 @@ class BilinearGather(torch.autograd.Function):
         return gi.to(dtype), None, None, None, None, None, None
 
 
+# --------------------------------------------------------------------------------------------- per-point training layer (csrc/point_layer_train.hip)
+_PL_WS = Workspace()
+
+
+def _rows_in_place(t):
+    """fp32 rows with unit column stride and a row stride >= the width (a column slice of a wider buffer), else a contiguous copy."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    n, c = t.shape
+    if n > 0 and (t.stride(1) != 1 and c > 1 or n > 1 and t.stride(0) < c):
+        t = t.contiguous()
+    return t
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+class PointLayer(torch.autograd.Function):
+    """Linear(bias=False) + BatchNorm1d with batch statistics + ReLU [+ per-cell maximum] over a list of points, forward and backward on
+    csrc/point_layer_train.hip.  forward(x (n, cin), weight (cout, cin), gamma, beta, inv (n) int64 or None, num_groups, want_y, want_max, eps, norm)
+    -> (y (n, cout) or None, gmax (num_groups, cout) or None, argmax int64 or None).  `norm` (or None) is the module whose running statistics
+    advance by BatchNorm1d's rule.  Saved for the backward: the inputs, the arg-max rows and 2 x cout statistics -- no (n, cout) tensor; the backward
+    recomputes x W^T.  Computes in fp32 under autocast."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, weight, gamma, beta, inv, num_groups, want_y, want_max, eps, norm):
+        if not (x.is_cuda and weight.is_cuda and x.dim() == 2 and weight.dim() == 2 and x.shape[1] == weight.shape[1]):
+            raise PnxError("point_layer: x (n, cin) and weight (cout, cin) CUDA (ROCm) tensors; there is no CPU implementation")
+        if not (want_y or want_max):
+            raise PnxError("point_layer: neither y nor the per-cell maximum requested")
+        n, cin = x.shape
+        cout = weight.shape[0]
+        if n < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.shape}")
+        x, w = _rows_in_place(x), weight.detach().float().contiguous()
+        ga, be = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        dev = x.device
+        G = 0
+        if want_max:
+            if inv is None or num_groups is None or inv.dtype != torch.int64 or inv.shape[0] != n:
+                raise PnxError("point_layer: the per-cell maximum needs inv (n) int64 and num_groups")
+            inv, G = inv.contiguous(), int(num_groups)
+        nbytes = lib().pnx_point_layer_workspace_bytes(n, cin, cout, 0)
+        if nbytes == 0:
+            raise PnxError(f"point_layer: {cin} -> {cout} channels over {n} rows is not served (cin <= 576, cout <= 256)")
+        ws = _PL_WS.get(nbytes, dev)
+        sums = torch.empty((2, cout), dtype=torch.float64, device=dev)
+        check(lib().pnx_point_layer_stats(ptr(x), _ld(x), n, cin, ptr(w), cout, ptr(sums), ptr(ws), ws.numel(), stream_ptr()), "pnx_point_layer_stats")
+        # the seam: under SyncBatchNorm `sums` (and n) is what the ranks would all-reduce
+        mean = sums[0] / n
+        var = (sums[1] / n - mean * mean).clamp_(min=0.0)
+        invstd = torch.rsqrt(var + eps)
+        prm = torch.zeros((6, cout), dtype=torch.float32, device=dev)
+        prm[0], prm[1], prm[2], prm[3] = mean, invstd, ga, be
+        y = torch.empty((n, cout), dtype=torch.float32, device=dev) if want_y else None
+        gmax = torch.empty((G, cout), dtype=torch.float32, device=dev) if want_max else None
+        arg = torch.empty((G, cout), dtype=torch.int64, device=dev) if want_max else None
+        check(lib().pnx_point_layer_forward(ptr(x), _ld(x), n, cin, ptr(w), cout, ptr(prm), ptr(inv) if want_max else None, G, ptr(y), cout, ptr(gmax), ptr(arg),
+                                            stream_ptr()), "pnx_point_layer_forward")
+        if norm is not None and norm.training and norm.track_running_stats and norm.running_mean is not None:
+            norm.num_batches_tracked.add_(1)
+            f = 1.0 / float(norm.num_batches_tracked) if norm.momentum is None else float(norm.momentum)
+            norm.running_mean.mul_(1.0 - f).add_((mean * f).to(norm.running_mean.dtype))
+            norm.running_var.mul_(1.0 - f).add_((var * (f * n / (n - 1.0))).to(norm.running_var.dtype))
+        ctx.save_for_backward(x, w, prm, inv if want_max else None, arg)
+        ctx.flags = (bool(want_y), bool(want_max), G)
+        if arg is not None:
+            ctx.mark_non_differentiable(arg)
+        return y, gmax, arg
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, dgmax, _darg):
+        x, w, prm, inv, arg = ctx.saved_tensors
+        want_y, want_max, G = ctx.flags
+        n, cin = x.shape
+        cout = w.shape[0]
+        dev = x.device
+        dy = _rows_in_place(dy) if want_y and dy is not None else None
+        dgmax = dgmax.float().contiguous() if want_max and dgmax is not None else None
+        if dy is None and dgmax is None:
+            return (None,) * 10
+        nbytes = lib().pnx_point_layer_workspace_bytes(n, cin, cout, 1)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)       # holds dxpre (n, cout): a transient of this call, not kept
+        ws = ws[(-ws.data_ptr()) % 256:]
+        sums = torch.empty((2, cout), dtype=torch.float64, device=dev)
+        grad = (ptr(dy), _ld(dy) if dy is not None else cout, ptr(inv) if dgmax is not None else None, G, ptr(dgmax), ptr(arg) if dgmax is not None else None)
+        check(lib().pnx_point_layer_backward_stats(ptr(x), _ld(x), n, cin, ptr(w), cout, ptr(prm), *grad, ptr(sums), ptr(ws), ws.numel(), stream_ptr()),
+              "pnx_point_layer_backward_stats")
+        prm = prm.clone()
+        prm[4], prm[5] = sums[0] / n, sums[1] / n
+        dx = torch.empty((n, cin), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((cout, cin), dtype=torch.float32, device=dev)
+        check(lib().pnx_point_layer_backward(ptr(x), _ld(x), n, cin, ptr(w), cout, ptr(prm), *grad, ptr(dx), cin, ptr(dw), ptr(ws), ws.numel(), stream_ptr()),
+              "pnx_point_layer_backward")
+        return dx, dw, sums[1].float(), sums[0].float(), None, None, None, None, None, None
+
+
+def point_layer(x, linear, norm, inv=None, num_groups=None, want_y=True, want_max=False):
+    """relu(norm(linear(x))) with batch statistics on the fused training node (PointLayer) -> (y or None, gmax or None): y (n, cout) when want_y, the
+    per-cell maximum gmax (num_groups, cout) over inv when want_max.  linear: nn.Linear without bias; norm: BatchNorm1d (or a SyncBatchNorm in a world
+    of one process), whose running statistics advance.  CUDA tensors only; fewer than two rows raise what BatchNorm1d raises."""
+    if linear.bias is not None:
+        raise PnxError("point_layer: the Linear must have no bias")
+    if norm.weight is None or norm.bias is None:
+        raise PnxError("point_layer: the norm must be affine")
+    y, gmax, _ = PointLayer.apply(x, linear.weight, norm.weight, norm.bias, inv, num_groups, want_y, want_max, float(norm.eps), norm)
+    return y, gmax
+
+
+def point_layer_serves(module, norm):
+    """Does the fused training node stand in for `module`'s Linear + norm + ReLU?  PNX_TRAIN_POINT_HIP on, training mode, and a plain BatchNorm1d --
+    or a SyncBatchNorm while the world is one process (with more it needs the collective the node does not issue: torch keeps it)."""
+    from torch import nn
+
+    from .switches import on
+
+    if not (on("PNX_TRAIN_POINT_HIP") and module.training and norm.training):
+        return False
+    if type(norm) is nn.BatchNorm1d:
+        return True
+    if isinstance(norm, nn.SyncBatchNorm):
+        import torch.distributed as dist
+
+        return not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1
+    return False
+
+
 # --------------------------------------------------------------------------------------------- IoU / NMS
 def _boxes(t, name):
     _need_cuda(t, name)

@@ -19,6 +19,8 @@ SWITCHES = {
     "PNX_FUSED_LOSS": (True, "CenterHead.loss on csrc/center_loss.hip; off: the torch losses of losses.py"),
     "PNX_TRAIN_FUSED": (True, "the reader's fused training passes (pfn_train.py); off: torch Linear / BatchNorm1d + HIP scatter-max"),
     "PNX_TRAIN_BILINEAR_HIP": (True, "multi-view reader, training: point sampling on pnx_bilinear_gather[_backward]; off: the torch statement"),
+    "PNX_TRAIN_POINT_HIP": (False, "multi-view reader, training: Linear + BatchNorm1d + ReLU [+ per-cell max] of the PFN layers and the PointNets on "
+                                   "csrc/point_layer_train.hip; off: the torch modules"),
     "PNX_HEAD_LAZY_TORCH": (False, "lazy head: evaluate the candidates with the torch statement of the kernel's arithmetic"),
     # read once, when a FusedPillarNeXt is built
     "PNX_HIP_CONV": (True, "fused graph: 3x3 layers, deblock and head output on the HIP kernels; off: MIOpen + one epilogue pass"),

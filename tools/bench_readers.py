@@ -8,7 +8,11 @@ bitmap / scan scratch).  usage: python tools/bench_readers.py [--points 180000] 
 --train runs the training leg instead: sampling a view's map at the points, forward + backward, through SingleView.sample -- the autograd node on
 pnx_bilinear_gather / pnx_bilinear_gather_backward against the torch statement (PNX_TRAIN_BILINEAR_HIP=0: four advanced-index gathers, four
 index_put(accumulate) scatters on float atomics) -- at the YAML's geometry, 192 channels, both views' map sizes; the two alternate in one run,
-medians of device-event times after warm-up, torch.cuda.max_memory_allocated above the resident inputs for each."""
+medians of device-event times after warm-up, torch.cuda.max_memory_allocated above the resident inputs for each.  Its second leg (--leg points
+runs it alone) times the reader's six per-point layers at the same geometry -- the PFN layers of both views (20 -> 24, 48 -> 48), pointnet1
+(20 -> 192) and pointnet2 (576 -> 256 + per-pillar max) -- forward + backward, the fused node of csrc/point_layer_train.hip (PNX_TRAIN_POINT_HIP=1)
+against the torch modules (=0, the parent's path), alternating in one run: median / min / max of device-event times and peak memory above the
+inputs per layer and in total, the weight-gradient difference, and the verdict the switch's default follows; it writes --points-out."""
 import argparse
 import os
 import sys
@@ -83,6 +87,106 @@ def train_leg(a):
     print(f"both views: node {total['node']:.1f} us, torch {total['torch']:.1f} us, node / torch = {total['node'] / total['torch']:.3f}")
 
 
+def point_layers_leg(a):
+    """The six per-point layers of the mvf18 reader in training, node against torch, one layer at a time."""
+    from torch.nn import functional as F
+
+    B = a.batch
+    t = torch.from_numpy(synth.make_batch("C4", B, "sweep", n=a.points)).cuda()
+    pr, vs = [-76.8, -76.8, -10.0, 76.8, 76.8, 10.0], [0.075, 0.075, 20]
+    cr, cs = [-180, -10.0, 0, 180, 10.0, 107], [0.140625, 0.2, 107]
+    torch.manual_seed(0)
+    m = MVFFeatureNet(in_channels=5, voxel_size=vs, pc_range=pr, cylinder_size=cs, cylinder_range=cr, num_filters=[48, 48], layer_nums=[0, 0, 0, 0],
+                      ds_layer_strides=[1, 2, 2, 2], ds_num_filters=[48, 96, 192, 192], kernel_size=[3, 3, 3, 3], out_channels=256).cuda().train()
+    with torch.no_grad():
+        feat, rp, rc, _ = m.group_views(t, B)
+    n = feat.shape[0]
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *shape: torch.randn(shape, device="cuda", generator=gen)  # noqa: E731
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# the multi-view reader's per-point layers in training, forward + backward: {n} points in {B} frames, {rp['G']} pillars, {rc['G']} cylinder cells, MI355X")
+    say("# node = ops.PointLayer on csrc/point_layer_train.hip (fp32 MFMA, deterministic); torch = PNX_TRAIN_POINT_HIP=0, the parent's path "
+        "(rocBLAS GEMM + BatchNorm1d + ReLU kernels + pnx_scatter_max)")
+
+    def pfn_first(pfn, x, inv, G, node):          # -> cat [y, max[inv]] (n, 2 c), as SingleView.cell_features / PFNLayer.forward hand it on
+        if node:
+            y, g = ops.point_layer(x, pfn.linear, pfn.norm, inv, G, want_y=True, want_max=True)
+            return torch.cat([y, g[inv]], dim=1)
+        return pfn(x, inv, G)
+
+    def pfn_last(pfn, x, inv, G, node):           # -> the cell feature (G, c)
+        if node:
+            return ops.point_layer(x, pfn.linear, pfn.norm, inv, G, want_y=False, want_max=True)[1]
+        return ops.scatter_max(pfn(x, inv, G), inv, G)[0]
+
+    def pn_plain(pn, x, inv, G, node):
+        return ops.point_layer(x, pn.linear, pn.norm)[0] if node else F.relu(pn.norm(pn.linear(x)))
+
+    def pn_max(pn, x, inv, G, node):
+        if node:
+            return ops.point_layer(x, pn.linear, pn.norm, inv, G, want_y=False, want_max=True)[1]
+        return ops.scatter_max(F.relu(pn.norm(pn.linear(x))), inv, G)[0]
+
+    pi, ci, PG, CG = rp["unq_inv"], rc["unq_inv"], rp["G"], rc["G"]
+    layers = [("pillar pfn0   20 ->  24 (+max, cat)", pfn_first, m.pillarview.pfn_layers[0], feat, pi, PG, (n, 48)),
+              ("pillar pfn1   48 ->  48 (cell max) ", pfn_last, m.pillarview.pfn_layers[1], rnd(n, 48).requires_grad_(True), pi, PG, (PG, 48)),
+              ("cyl    pfn0   20 ->  24 (+max, cat)", pfn_first, m.cylinderview.pfn_layers[0], feat, ci, CG, (n, 48)),
+              ("cyl    pfn1   48 ->  48 (cell max) ", pfn_last, m.cylinderview.pfn_layers[1], rnd(n, 48).requires_grad_(True), ci, CG, (CG, 48)),
+              ("pointnet1     20 -> 192            ", pn_plain, m.pointnet1, feat, None, 0, (n, 192)),
+              ("pointnet2    576 -> 256 (cell max) ", pn_max, m.pointnet2, rnd(n, 576).requires_grad_(True), pi, PG, (PG, 256))]
+    runs = a.iters
+    tot = {"node": np.zeros(runs), "torch": np.zeros(runs)}
+    tot_peak = {"node": 0, "torch": 0}
+    slower = []
+    for name, fn, mod, x, inv, G, gshape in layers:
+        go = rnd(*gshape)
+        times, peak, grads = {"node": [], "torch": []}, {}, {}
+        for it in range(a.warm + runs):
+            for leg in ("node", "torch"):                                          # alternating, so that both see the same machine
+                mod.zero_grad(set_to_none=True)
+                if x.requires_grad:
+                    x.grad = None
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn(mod, x, inv, G, leg == "node").backward(go)
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= a.warm:
+                    times[leg].append(e0.elapsed_time(e1) * 1e3)
+                    peak[leg] = max(peak.get(leg, 0), torch.cuda.max_memory_allocated() - base)
+                grads[leg] = mod.linear.weight.grad.detach().clone()
+        diff = float((grads["node"] - grads["torch"]).abs().max() / grads["torch"].abs().max())
+        for leg in ("node", "torch"):
+            us = np.asarray(times[leg])
+            tot[leg] += us
+            tot_peak[leg] = max(tot_peak[leg], peak[leg])
+            say(f"{name} {leg:5s}: median {np.median(us):9.1f} us  (min {us.min():9.1f}, max {us.max():9.1f}, {len(us)} runs), peak above the inputs {peak[leg] / 2**20:8.1f} MiB")
+        ratio = float(np.median(times["node"]) / np.median(times["torch"]))
+        if ratio > 1.0:
+            slower.append(name.strip())
+        say(f"{name} max |dW(node) - dW(torch)| / max |dW| = {diff:.2e}; node / torch time = {ratio:.3f}")
+    for leg in ("node", "torch"):
+        say(f"six layers, {leg:5s}: median {np.median(tot[leg]):9.1f} us  (min {tot[leg].min():9.1f}, max {tot[leg].max():9.1f}), largest peak above the inputs {tot_peak[leg] / 2**20:8.1f} MiB")
+    gain = float(np.median(tot["torch"]) - np.median(tot["node"]))
+    spread = float((tot["node"].max() - tot["node"].min()) + (tot["torch"].max() - tot["torch"].min()))
+    on = gain > spread and tot_peak["node"] < tot_peak["torch"]
+    say(f"torch - node = {gain:.1f} us against the two legs' max - min spread of {spread:.1f} us, node / torch = {np.median(tot['node']) / np.median(tot['torch']):.3f}; "
+        f"peak memory {'lower' if tot_peak['node'] < tot_peak['torch'] else 'not lower'} on the node -> PNX_TRAIN_POINT_HIP defaults to {'on' if on else 'off'}")
+    say("layers on which the node is slower than torch: " + (", ".join(slower) if slower else "none"))
+    if a.points_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.points_out)), exist_ok=True)
+        with open(a.points_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=180_000)
@@ -90,9 +194,16 @@ def main():
     ap.add_argument("--train", action="store_true", help="the training leg: sampling forward + backward, node against the torch statement")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warm", type=int, default=5)
+    ap.add_argument("--leg", choices=["all", "sampling", "points"], default="all", help="--train: the sampling leg, the per-point layers, or both")
+    ap.add_argument("--points-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mvf_point_layers_train.txt"),
+                    help="--train: where the per-point layers' leg writes its report ('' = nowhere)")
     a = ap.parse_args()
     if a.train:
-        return train_leg(a)
+        if a.leg in ("all", "sampling"):
+            train_leg(a)
+        if a.leg in ("all", "points"):
+            point_layers_leg(a)
+        return
     B = a.batch
     pts = synth.make_batch("C4", B, "sweep", n=a.points)                    # Waymo-shaped sweep cloud, +-75.2 m
     t = torch.from_numpy(pts).cuda()
