@@ -13,7 +13,9 @@
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream)
  *   - return value: PNX_OK (0) or a negative pnx_status; pnx_last_error() gives a message.
  *     Unlike the reference (iou3d_nms.cpp:14-38) nothing ever calls exit().
- *   - not re-entrant on the same workspace; one workspace per stream.
+ *   - workspaces: 256-byte aligned, at least the entry's pnx_*_workspace_bytes(...) bytes, one per stream (no call is re-entrant on the
+ *     same workspace), and they need not be cleared unless an entry says otherwise.  A NULL or misaligned workspace is PNX_ERR_INVALID, a
+ *     short one PNX_ERR_WORKSPACE; the message names the entry and both byte counts.
  */
 #ifndef PNX_H
 #define PNX_H
@@ -205,7 +207,7 @@ int pnx_bilinear_gather(const void* image, int32_t dtype, int32_t batch, int32_t
  *   image index is outside [0, batch) contributes nothing.  Any channel count; ds_rate a power of two; n = 0 zero-fills grad_image.
  * Deterministic: the points are sorted by base cell (a stable radix sort of the point indices, so ties stay in point order) and every cell sums
  * its terms in fp32 in that order, one rounded product per term -- no floating-point atomics; the same inputs give the same bits.  All work
- * happens inside the call and its workspace (pnx_bilinear_gather_backward_workspace_bytes; 0 = sizes beyond 32-bit indices; 256-byte aligned). */
+ * happens inside the call and its workspace (pnx_bilinear_gather_backward_workspace_bytes; 0 = sizes beyond 32-bit indices). */
 size_t pnx_bilinear_gather_backward_workspace_bytes(int64_t n, int32_t batch, int32_t h, int32_t w);
 int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t batch, int32_t h, int32_t w, int32_t channels, const float* pos,
                                  int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords,
@@ -238,7 +240,7 @@ int pnx_scatter_max_backward(const float* grad_out, const int64_t* argmax, int64
  *   pnx_point_layer_backward        dxpre = gamma invstd (dz - D1/n - xhat D2/n); dw (cout, cin) = dxpre^T x; dx (n, lddx) = dxpre W (may be NULL)
  * Every pass recomputes z: nothing of size (n, cout) lives between two calls (the backward call holds dxpre in its own workspace).
  * Deterministic: no floating-point atomics, fixed summation orders; the workspace (pnx_point_layer_workspace_bytes(n, cin, cout, backward != 0 for
- * pnx_point_layer_backward); 0 = unsupported sizes; 256-byte aligned) need not be cleared. */
+ * pnx_point_layer_backward); 0 = unsupported sizes). */
 size_t pnx_point_layer_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t backward);
 int pnx_point_layer_stats(const float* x, int32_t ldx, int64_t n, int32_t cin, const float* w, int32_t cout, double* sums, void* workspace,
                           size_t workspace_bytes, pnx_stream_t stream);
@@ -446,7 +448,7 @@ int pnx_boxes_aligned_iou_bev_cpu(const float* boxes_a_host, const float* boxes_
  *                 k-th kept box, ascending -- exactly what nms_gpu writes into `keep`
  *   keep_count    int32[num_segments]: number kept (already min'ed with post_max if post_max > 0)
  *   max_seg_len   an upper bound on any segment's length (host value; sizes the launch)
- *   workspace     pnx_nms_workspace_bytes(total_boxes, num_segments, max_seg_len) bytes, 8-byte aligned.  The box count is known on the device only, so
+ *   workspace     pnx_nms_workspace_bytes(total_boxes, num_segments, max_seg_len) bytes.  The box count is known on the device only, so
  *                 pnx_nms_rotated_batched checks what the host can: workspace_bytes below pnx_nms_workspace_bytes(1, num_segments, max_seg_len) -- its
  *                 layout plus the mask words of ONE box -- is PNX_ERR_WORKSPACE; sizing it for all boxes stays the caller's duty.
  */

@@ -62,7 +62,7 @@ class AssignLabel:
                    "mask": [e((B, M), torch.uint8) for _ in range(T)], "cat": [e((B, M), torch.int64) for _ in range(T)],
                    "gt_boxes": [e((B, M, 7), torch.float32) for _ in range(T)]}
             counts = e((B, T), torch.int32)
-            ws = e((ops.assign_workspace_bytes(B, T, M) + 256,), torch.uint8)
+            ws = e((ops.assign_workspace_bytes(B, T, M),), torch.uint8)
             self._cache[key] = (out, counts, ws, self.descriptor())
         return self._cache[key]
 

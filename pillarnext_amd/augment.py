@@ -213,9 +213,12 @@ class PasteAugment:
     """paste_and_augment with its buffers: one object per (sampler, augmentations) pair, buffers cached per batch size as AssignLabel's are."""
 
     def __init__(self, sampler=None, augmentations=None):
+        from . import ops
+
         self.sampler, self.augmentations = sampler, augmentations
         self._cache = {}
         self._points = {}
+        self._ws = ops.Workspace()
         self.last = None   # the buffers of the last call: accept, paste_offset, pasted_rows, frame_rows, .. (for tools and tests; all on the device)
 
     def _buffers(self, B, K, S, D, device):
@@ -235,14 +238,10 @@ class PasteAugment:
         from . import ops
 
         key = (B, width, str(device))
-        out, ws = self._points.get(key, (None, None))
+        out = self._points.get(key)
         if out is None or out.shape[0] < capacity:
-            out = torch.empty((int(capacity * 1.25) + 64, width), dtype=torch.float32, device=device)
-        need = ops.paste_augment_workspace_bytes(n_points, B) + 256
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((int(need * 1.25),), dtype=torch.uint8, device=device)
-        self._points[key] = (out, ws)
-        return out[:capacity], ws
+            out = self._points[key] = torch.empty((int(capacity * 1.25) + 64, width), dtype=torch.float32, device=device)
+        return out[:capacity], self._ws.get(ops.paste_augment_workspace_bytes(n_points, B), device)
 
     def __call__(self, points, gt_boxes, gt_classes, num_gt=None, host_classes=None):
         """points (N, 1 + F) fp32 CUDA rows [batch index, x, y, z, ..] (rows with a batch index outside [0, B) are dropped: SweepMerger's output

@@ -228,14 +228,29 @@ __global__ __launch_bounds__(kAB) void k_assign_heatmap(AssignParams p, const in
   }
 }
 
+// The draw lists k_assign_objects leaves for k_assign_heatmap: (x, y, radius, class) per object and the length of every (frame, task) list.
+struct AssignWs {
+  int4* draw;
+  int32_t* draw_len;
+  size_t bytes;
+};
+AssignWs assign_carve(void* base, int batch, int n_tasks, int max_objs) {
+  AssignWs w;
+  PnxCarver c(base);
+  const size_t lists = (size_t)batch * n_tasks;
+  w.draw = c.take<int4>(lists * max_objs);
+  w.draw_len = c.take<int32_t>(lists);
+  w.bytes = c.used();
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t pnx_assign_workspace_bytes(int32_t batch, int32_t n_tasks, int32_t max_objs) {
   if (batch <= 0 || n_tasks <= 0 || max_objs <= 0) return 0;
-  const size_t lists = (size_t)batch * n_tasks;
-  return pnx_align_up(lists * max_objs * sizeof(int4), 256) + pnx_align_up(lists * sizeof(int32_t), 256);
+  return assign_carve(nullptr, batch, n_tasks, max_objs).bytes;
 }
 
 int pnx_assign_labels(const float* gt_boxes, const int32_t* gt_cls, const int32_t* num_gt, int32_t batch, int32_t k, const pnx_assign_desc* desc_host,
@@ -282,15 +297,12 @@ int pnx_assign_labels(const float* gt_boxes, const int32_t* gt_cls, const int32_
                 "pnx_assign_labels: class %d maps to (task %d, class %d), outside the task list", g, d.class_task[g], d.class_cls[g]);
     p.class_task[g] = (signed char)d.class_task[g], p.class_cls[g] = (signed char)d.class_cls[g];
   }
-  PNX_REQUIRE(workspace_bytes >= pnx_assign_workspace_bytes(batch, d.n_tasks, d.max_objs), PNX_ERR_WORKSPACE, "pnx_assign_labels: workspace too small (%zu < %zu bytes)",
-              workspace_bytes, pnx_assign_workspace_bytes(batch, d.n_tasks, d.max_objs));
+  const AssignWs ws = assign_carve(workspace, batch, d.n_tasks, d.max_objs);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_assign_labels");
   hipStream_t st = (hipStream_t)stream;
-  PnxCarver c(workspace);
-  int4* draw = c.take<int4>((size_t)batch * d.n_tasks * d.max_objs);
-  int32_t* draw_len = c.take<int32_t>((size_t)batch * d.n_tasks);
-  k_assign_objects<<<batch, kAB, 0, st>>>(p, gt_boxes, gt_cls, num_gt, counts, draw, draw_len);
+  k_assign_objects<<<batch, kAB, 0, st>>>(p, gt_boxes, gt_cls, num_gt, counts, ws.draw, ws.draw_len);
   PNX_LAUNCH_CHECK();
-  k_assign_heatmap<<<(unsigned)tiles, kAB, 0, st>>>(p, draw, draw_len);
+  k_assign_heatmap<<<(unsigned)tiles, kAB, 0, st>>>(p, ws.draw, ws.draw_len);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -595,6 +595,28 @@ __global__ __launch_bounds__(kPB) void k_augment_boxes(float* __restrict__ boxes
   q[D - 1] = v[8];
 }
 
+// Point pass: keep bits of the scene rows (one word per 32 rows of a chunk), the per-(frame, chunk) row counts with one head slot per frame
+// (the pasted rows), their exclusive prefix and the block totals of the two-level scan.
+struct PasteWs {
+  uint32_t *keepw, *arr, *pre, *blk;
+  int nch, nblk;
+  int64_t len;
+  size_t bytes;
+};
+PasteWs paste_carve(void* base, int64_t n_points, int batch) {
+  PasteWs w;
+  PnxCarver c(base);
+  w.nch = (int)((n_points + kChunk - 1) / kChunk);
+  w.len = (int64_t)batch * (w.nch + 1);
+  w.nblk = (int)((w.len + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
+  w.keepw = c.take<uint32_t>((size_t)w.nch * (kChunk / 32) + 8);
+  w.arr = c.take<uint32_t>(w.len + 8);
+  w.pre = c.take<uint32_t>(w.len + 8);
+  w.blk = c.take<uint32_t>(w.nblk + 8);
+  w.bytes = c.used();
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -632,10 +654,7 @@ int pnx_paste_select(const float* gt_boxes, const int32_t* gt_cls, const int32_t
 
 size_t pnx_paste_augment_workspace_bytes(int64_t n_points, int32_t batch) {
   if (n_points < 0 || batch <= 0) return 0;
-  const int64_t nch = (n_points + kChunk - 1) / kChunk;
-  const int64_t len = (int64_t)batch * (nch + 1);
-  const int64_t nblk = (len + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS;
-  return pnx_align_up((size_t)(nch * (kChunk / 32) + 8) * 4, 256) + pnx_align_up((size_t)(len + 8) * 4, 256) * 2 + pnx_align_up((size_t)(nblk + 8) * 4, 256);
+  return paste_carve(nullptr, n_points, batch).bytes;
 }
 
 int pnx_paste_augment_points(const float* points, int64_t n_points, int32_t point_dim, int32_t batch, const int32_t* cand_bank, const float* cand_boxes,
@@ -657,25 +676,17 @@ int pnx_paste_augment_points(const float* points, int64_t n_points, int32_t poin
     PNX_REQUIRE(cand_boxes && paste_offset && pasted_rows && bank_points && bank_offsets && n_obj >= 1 && bank_rows >= 0, PNX_ERR_INVALID,
                 "pnx_paste_augment_points: null pointer or bad size (a candidate array, paste_offset, pasted_rows or the bank)");
   }
-  PNX_REQUIRE(workspace && workspace_bytes >= pnx_paste_augment_workspace_bytes(n_points, batch), PNX_ERR_WORKSPACE,
-              "pnx_paste_augment_points: workspace too small (%zu < %zu bytes)", workspace_bytes, pnx_paste_augment_workspace_bytes(n_points, batch));
+  const PasteWs ws = paste_carve(workspace, n_points, batch);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_paste_augment_points");
   hipStream_t st = (hipStream_t)stream;
-  const int nch = (int)((n_points + kChunk - 1) / kChunk);
-  const int64_t len = (int64_t)batch * (nch + 1);
-  const int nblk = (int)((len + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
-  PnxCarver c(workspace);
-  uint32_t* keepw = c.take<uint32_t>((size_t)nch * (kChunk / 32) + 8);
-  uint32_t* arr = c.take<uint32_t>(len + 8);
-  uint32_t* pre = c.take<uint32_t>(len + 8);
-  uint32_t* blk = c.take<uint32_t>(nblk + 8);
-  PointArgs p{points, n_points, point_dim + 1, batch, s, box_dim, nch, cand_boxes, paste_offset};
-  k_paste_head<<<1, 64, 0, st>>>(s > 0 ? pasted_rows : nullptr, batch, nch, arr);
-  if (nch > 0) k_paste_flags<<<nch, kPB, 0, st>>>(p, keepw, arr);
-  k_scan_local<SCAN_IDENT><<<nblk, kBlock, 0, st>>>(arr, len, pre, blk);
-  k_scan_blocks<<<1, kBlock, 0, st>>>(blk, nblk, n_out);
-  k_paste_frame_rows<<<1, 64, 0, st>>>(pre, blk, nblk, batch, nch, frame_rows);
-  if (nch > 0) k_paste_write<<<nch, kPB, 0, st>>>(p, keepw, pre, blk, nblk, xform, out, capacity);
-  if (s > 0) k_paste_objects<<<batch * s, kPB, 0, st>>>(p, cand_bank, bank_points, bank_offsets, n_obj, bank_rows, pre, blk, xform, out, capacity);
+  PointArgs p{points, n_points, point_dim + 1, batch, s, box_dim, ws.nch, cand_boxes, paste_offset};
+  k_paste_head<<<1, 64, 0, st>>>(s > 0 ? pasted_rows : nullptr, batch, ws.nch, ws.arr);
+  if (ws.nch > 0) k_paste_flags<<<ws.nch, kPB, 0, st>>>(p, ws.keepw, ws.arr);
+  k_scan_local<SCAN_IDENT><<<ws.nblk, kBlock, 0, st>>>(ws.arr, ws.len, ws.pre, ws.blk);
+  k_scan_blocks<<<1, kBlock, 0, st>>>(ws.blk, ws.nblk, n_out);
+  k_paste_frame_rows<<<1, 64, 0, st>>>(ws.pre, ws.blk, ws.nblk, batch, ws.nch, frame_rows);
+  if (ws.nch > 0) k_paste_write<<<ws.nch, kPB, 0, st>>>(p, ws.keepw, ws.pre, ws.blk, ws.nblk, xform, out, capacity);
+  if (s > 0) k_paste_objects<<<batch * s, kPB, 0, st>>>(p, cand_bank, bank_points, bank_offsets, n_obj, bank_rows, ws.pre, ws.blk, xform, out, capacity);
   if (capacity > 0) k_paste_tail<<<(unsigned)((capacity + kPB - 1) / kPB), kPB, 0, st>>>(out, point_dim + 1, capacity, n_out);
   PNX_LAUNCH_CHECK();
   return PNX_OK;

@@ -279,14 +279,31 @@ __global__ __launch_bounds__(kLB) void k_loss_scatter(LossGrads gm, LossGeom g, 
 
 constexpr int kNegBlocks = 1024;
 
+// The workspace of one forward / backward pair: the forward fills it, the backward reads gathered and iou3d.
+struct LossWs {
+  float *gathered, *boxes7, *iou3d;
+  double* part;
+  size_t bytes;
+};
+LossWs loss_carve(void* base, int batch, int max_objs) {
+  LossWs w;
+  PnxCarver c(base);
+  const size_t n = (size_t)batch * max_objs;
+  w.gathered = c.take<float>(n * kGW);
+  w.boxes7 = c.take<float>(n * 7);
+  w.iou3d = c.take<float>(n);
+  w.part = c.take<double>(kNegBlocks);
+  w.bytes = c.used();
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t pnx_center_loss_workspace_bytes(int32_t batch, int32_t max_objs) {
   if (batch <= 0 || max_objs <= 0) return 0;
-  const size_t n = (size_t)batch * max_objs;
-  return pnx_align_up(n * kGW * 4, 256) + pnx_align_up(n * 7 * 4, 256) + pnx_align_up(n * 4, 256) + pnx_align_up(kNegBlocks * 8, 256);
+  return loss_carve(nullptr, batch, max_objs).bytes;
 }
 
 // maps7 / grads7: HOST arrays of 7 device pointers in the order hm, reg, height, dim, rot, vel, iou (iou may be NULL)
@@ -297,27 +314,23 @@ int pnx_center_loss_forward(const void* const* maps7, const float* hm_target, co
   PNX_REQUIRE(maps7 && hm_target && ind && mask && cat && anno_box && gt_boxes && geom4_host && losses15 && workspace, PNX_ERR_INVALID, "null pointer");
   for (int k = 0; k < 6; k++) PNX_REQUIRE(maps7[k] != nullptr, PNX_ERR_INVALID, "head map %d is NULL", k);
   PNX_REQUIRE(batch > 0 && n_classes > 0 && h > 0 && w > 0 && max_objs > 0, PNX_ERR_INVALID, "bad sizes");
-  PNX_REQUIRE(workspace_bytes >= pnx_center_loss_workspace_bytes(batch, max_objs), PNX_ERR_WORKSPACE, "workspace too small");
+  const LossWs ws = loss_carve(workspace, batch, max_objs);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_center_loss_forward");
   hipStream_t st = (hipStream_t)stream;
-  PnxCarver c(workspace);
   const int n = batch * max_objs;
-  float* gathered = c.take<float>((size_t)n * kGW);
-  float* boxes7 = c.take<float>((size_t)n * 7);
-  float* iou3d = c.take<float>((size_t)n);
-  double* part = c.take<double>(kNegBlocks);
   LossMaps m = {(const float*)maps7[0], (const float*)maps7[1], (const float*)maps7[2], (const float*)maps7[3], (const float*)maps7[4],
                 (const float*)maps7[5], (const float*)maps7[6]};
   LossGeom g = {batch, n_classes, h, w, max_objs, geom4_host[0], geom4_host[1], geom4_host[2], geom4_host[3]};
   const int64_t ncell = (int64_t)batch * n_classes * h * w;
-  k_focal_neg<<<kNegBlocks, kLB, 0, st>>>(m.hm, hm_target, ncell, part);
-  k_loss_gather<<<(n + kLB - 1) / kLB, kLB, 0, st>>>(m, g, ind, cat, gathered, boxes7);
+  k_focal_neg<<<kNegBlocks, kLB, 0, st>>>(m.hm, hm_target, ncell, ws.part);
+  k_loss_gather<<<(n + kLB - 1) / kLB, kLB, 0, st>>>(m, g, ind, cat, ws.gathered, ws.boxes7);
   PNX_LAUNCH_CHECK();
   const int has_iou = m.iou != nullptr;
   if (has_iou) {
-    const int rc = pnx_boxes_aligned_iou3d(boxes7, gt_boxes, n, iou3d, stream);
+    const int rc = pnx_boxes_aligned_iou3d(ws.boxes7, gt_boxes, n, ws.iou3d, stream);
     if (rc != PNX_OK) return rc;
   }
-  k_loss_reduce<<<1, kLossReduceThreads, 0, st>>>(gathered, mask, anno_box, gt_boxes, iou3d, part, kNegBlocks, n, has_iou, with_reg_iou != 0, losses15);
+  k_loss_reduce<<<1, kLossReduceThreads, 0, st>>>(ws.gathered, mask, anno_box, gt_boxes, ws.iou3d, ws.part, kNegBlocks, n, has_iou, with_reg_iou != 0, losses15);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
@@ -344,19 +357,16 @@ extern "C" int pnx_center_loss_backward(const void* const* maps7, void* const* g
   PNX_REQUIRE(maps7 && grads7 && hm_target && ind && mask && cat && anno_box && gt_boxes && geom4_host && losses15 && upstream13 && coef_scratch && workspace,
               PNX_ERR_INVALID, "null pointer");
   for (int k = 0; k < 6; k++) PNX_REQUIRE(maps7[k] != nullptr && grads7[k] != nullptr, PNX_ERR_INVALID, "head map / gradient %d is NULL", k);
-  PNX_REQUIRE(workspace_bytes >= pnx_center_loss_workspace_bytes(batch, max_objs), PNX_ERR_WORKSPACE, "workspace too small");
+  const LossWs ws = loss_carve(workspace, batch, max_objs);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_center_loss_backward");
   hipStream_t st = (hipStream_t)stream;
-  PnxCarver c(workspace);
   const int n = batch * max_objs;
-  const float* gathered = c.take<float>((size_t)n * kGW);
-  (void)c.take<float>((size_t)n * 7);
-  const float* iou3d = c.take<float>((size_t)n);
   LossGrads gm = {(float*)grads7[0], (float*)grads7[1], (float*)grads7[2], (float*)grads7[3], (float*)grads7[4], (float*)grads7[5], (float*)grads7[6]};
   LossGeom g = {batch, n_classes, h, w, max_objs, geom4_host[0], geom4_host[1], geom4_host[2], geom4_host[3]};
   const int64_t ncell = (int64_t)batch * n_classes * h * w;
   k_hm_coef<<<1, 1, 0, st>>>(losses15, upstream13, coef_scratch);
   k_focal_neg_bwd<<<kNegBlocks, kLB, 0, st>>>((const float*)maps7[0], hm_target, ncell, coef_scratch, gm.hm);
-  k_loss_scatter<<<(n + kLB - 1) / kLB, kLB, 0, st>>>(gm, g, gathered, ind, cat, mask, anno_box, gt_boxes, iou3d, losses15, upstream13,
+  k_loss_scatter<<<(n + kLB - 1) / kLB, kLB, 0, st>>>(gm, g, ws.gathered, ind, cat, mask, anno_box, gt_boxes, ws.iou3d, losses15, upstream13,
                                                       maps7[6] != nullptr, with_reg_iou != 0);
   PNX_LAUNCH_CHECK();
   return PNX_OK;

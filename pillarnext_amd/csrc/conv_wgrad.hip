@@ -346,8 +346,8 @@ static int wgrad_impl(const char* name, PnxPieces<NP> x, PnxPieces<NP> dy, const
   PNX_REQUIRE(stride == 1 || stride == 2, PNX_ERR_UNSUPPORTED, "stride %d", stride);
   PNX_REQUIRE(cin >= 64 && cout >= 64 && (cin & 63) == 0 && (cout & 63) == 0 && cin <= 512 && cout <= 512, PNX_ERR_UNSUPPORTED,
               "weight gradient for %d -> %d channels (multiples of 64 up to 512)", cin, cout);
-  PNX_REQUIRE(((x.bits() | dy.bits() | (uintptr_t)workspace) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
-  PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_wgrad_workspace_bytes(cin, cout), PNX_ERR_WORKSPACE, "workspace too small");
+  PNX_REQUIRE(((x.bits() | dy.bits()) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, pnx_conv3x3_wgrad_workspace_bytes(cin, cout), name);
   hipStream_t st = (hipStream_t)stream;
   if (stride == 1) return launch_wgrad<1, NP>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);
   return launch_wgrad<2, NP>(x, dy, mask, dw, batch, h, w, cin, cout, workspace, st);

@@ -488,16 +488,42 @@ __global__ __launch_bounds__(256) void k_rs_sort(const unsigned long long* __res
   }
 }
 
+// Histogram rows and their segment per (chunk, slot), with one chunk to spare; the per-segment overflow histogram; the select state; the survivors.
+struct TopkWs {
+  uint32_t *rows, *ovf;
+  int32_t* slotseg;
+  RsState rs;
+  unsigned long long* list;
+  int nchunks;
+  size_t bytes;
+};
+TopkWs topk_carve(void* base, int64_t n_keys, int num_segments) {
+  TopkWs w;
+  PnxCarver c(base);
+  const size_t S = (size_t)num_segments;
+  w.nchunks = (int)((n_keys + kRsChunk - 1) / kRsChunk);
+  w.rows = c.take<uint32_t>((size_t)(w.nchunks + 1) * kRsSlots * kRsBins);
+  w.slotseg = c.take<int32_t>((size_t)(w.nchunks + 1) * kRsSlots);
+  w.ovf = c.take<uint32_t>(S * kRsBins);
+  w.rs.prefix = c.take<unsigned long long>(S + 8);
+  w.rs.thr = c.take<unsigned long long>(S + 8);
+  w.rs.rem = c.take<uint32_t>(S + 8);
+  w.rs.flag = c.take<uint32_t>(S + 8);
+  w.rs.total = c.take<uint32_t>(S + 8);
+  w.rs.cursor = c.take<uint32_t>(S + 8);
+  w.rs.n_open = c.take<int32_t>(S + 8);
+  w.list = c.take<unsigned long long>(S * kRsMaxK);
+  w.bytes = c.used() + 256;
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t pnx_decode_topk_workspace_bytes(int64_t n_keys, int32_t num_segments) {
   if (n_keys < 0 || num_segments < 1) return 0;
-  const size_t nchunks = (size_t)((n_keys + kRsChunk - 1) / kRsChunk) + 1;
-  const size_t S = (size_t)num_segments;
-  return pnx_align_up(nchunks * kRsSlots * kRsBins * 4, 256) + pnx_align_up(nchunks * kRsSlots * 4, 256) + pnx_align_up(S * kRsBins * 4, 256) +
-         2 * pnx_align_up((S + 8) * 8, 256) + 5 * pnx_align_up((S + 8) * 4, 256) + pnx_align_up(S * kRsMaxK * 8, 256) + 256;
+  return topk_carve(nullptr, n_keys, num_segments).bytes;
 }
 
 // keys = the concatenated outputs of pnx_decode_keys for all tasks; outputs in the layout pnx_decode_boxes consumes
@@ -506,35 +532,22 @@ int pnx_decode_topk(const uint64_t* keys, int64_t n_keys, int32_t num_segments, 
   PNX_REQUIRE(keys && sorted_keys && order && seg_start && seg_len && workspace, PNX_ERR_INVALID, "null pointer");
   PNX_REQUIRE(n_keys >= 0 && n_keys < ((int64_t)1 << 32) && num_segments >= 1 && pre_max >= 1 && pre_max <= kRsMaxK, PNX_ERR_INVALID,
               "bad sizes (pre_max <= %d)", kRsMaxK);
-  PNX_REQUIRE(workspace_bytes >= pnx_decode_topk_workspace_bytes(n_keys, num_segments), PNX_ERR_WORKSPACE, "workspace too small");
+  const TopkWs w = topk_carve(workspace, n_keys, num_segments);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, w.bytes, "pnx_decode_topk");
   hipStream_t st = (hipStream_t)stream;
   const int S = num_segments;
-  const int nchunks = (int)((n_keys + kRsChunk - 1) / kRsChunk);
-  PnxCarver c(workspace);
-  uint32_t* rows = c.take<uint32_t>((size_t)(nchunks + 1) * kRsSlots * kRsBins);
-  int32_t* slotseg = c.take<int32_t>((size_t)(nchunks + 1) * kRsSlots);
-  uint32_t* ovf = c.take<uint32_t>((size_t)S * kRsBins);
-  RsState rs;
-  rs.prefix = c.take<unsigned long long>(S + 8);
-  rs.thr = c.take<unsigned long long>(S + 8);
-  rs.rem = c.take<uint32_t>(S + 8);
-  rs.flag = c.take<uint32_t>(S + 8);
-  rs.total = c.take<uint32_t>(S + 8);
-  rs.cursor = c.take<uint32_t>(S + 8);
-  rs.n_open = c.take<int32_t>(S + 8);
-  unsigned long long* list = c.take<unsigned long long>((size_t)S * kRsMaxK);
   {
     int nb = (int)(((int64_t)S * kRsBins + 256 * 8 - 1) / (256 * 8));
     nb = nb < (S + 255) / 256 ? (S + 255) / 256 : (nb > 1024 ? 1024 : nb);
-    k_rs_init<<<nb, 256, 0, st>>>(rs, S, pre_max, ovf);
+    k_rs_init<<<nb, 256, 0, st>>>(w.rs, S, pre_max, w.ovf);
   }
   for (int p = 0; p < 6; p++) {
-    if (nchunks > 0) k_rs_hist<<<nchunks, kRsThreads, 0, st>>>((const unsigned long long*)keys, n_keys, p, rs, slotseg, rows, ovf);
-    k_rs_select<<<S, 256, 0, st>>>(p, rs, slotseg, nchunks * kRsSlots, rows, ovf);
+    if (w.nchunks > 0) k_rs_hist<<<w.nchunks, kRsThreads, 0, st>>>((const unsigned long long*)keys, n_keys, p, w.rs, w.slotseg, w.rows, w.ovf);
+    k_rs_select<<<S, 256, 0, st>>>(p, w.rs, w.slotseg, w.nchunks * kRsSlots, w.rows, w.ovf);
   }
   const unsigned nb = (unsigned)((n_keys + 255) / 256);
-  if (nb > 0) k_rs_collect<<<nb, 256, 0, st>>>((const unsigned long long*)keys, n_keys, rs, pre_max, list);
-  k_rs_sort<<<S, 256, 0, st>>>(list, rs, pre_max, (unsigned long long*)sorted_keys, order, seg_start, seg_len, seg_total);
+  if (nb > 0) k_rs_collect<<<nb, 256, 0, st>>>((const unsigned long long*)keys, n_keys, w.rs, pre_max, w.list);
+  k_rs_sort<<<S, 256, 0, st>>>(w.list, w.rs, pre_max, (unsigned long long*)sorted_keys, order, seg_start, seg_len, seg_total);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }
@@ -575,7 +588,7 @@ size_t pnx_sort_keys_workspace_bytes(int64_t n_keys) {
 int pnx_sort_keys(const uint64_t* keys, int64_t n_keys, int32_t num_segments, uint64_t* sorted_keys, int64_t* order, void* workspace,
                   size_t workspace_bytes, pnx_stream_t stream) {
   PNX_REQUIRE(keys && sorted_keys && order && workspace && n_keys > 0 && num_segments > 0, PNX_ERR_INVALID, "bad arguments");
-  PNX_REQUIRE(workspace_bytes >= pnx_sort_keys_workspace_bytes(n_keys), PNX_ERR_INVALID, "workspace too small");
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, pnx_sort_keys_workspace_bytes(n_keys), "pnx_sort_keys");
   unsigned bits = 0;
   while ((1 << bits) <= num_segments) bits++;  // 2^bits > num_segments: the all-ones pattern of an invalid key exceeds every valid segment
   size_t bytes = workspace_bytes;

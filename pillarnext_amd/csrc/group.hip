@@ -463,14 +463,13 @@ int pnx_group_points(const float* points, int64_t n, int32_t stride, int32_t bat
   int rc = group_check_geom(g, batch, stride);
   if (rc != PNX_OK) return rc;
   PNX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) - 4096, PNX_ERR_INVALID, "n_points %lld", (long long)n);
-  PNX_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 255) == 0, PNX_ERR_INVALID, "workspace must be 256-byte aligned");
   PNX_REQUIRE(n == 0 || points != nullptr, PNX_ERR_INVALID, "points is NULL");
   const int nf_out = g->mode == PNX_GROUP_VOXEL ? stride - 1 : stride - 1 + 5;
   PNX_REQUIRE(point_features == nullptr || feature_ld >= nf_out, PNX_ERR_INVALID, "feature_ld %d < %d columns", feature_ld, nf_out);
   PNX_REQUIRE((coords == nullptr && group_mean == nullptr) || group_capacity > 0, PNX_ERR_INVALID, "group_capacity must be > 0");
   PNX_REQUIRE(coords == nullptr || ((uintptr_t)coords & 15) == 0, PNX_ERR_INVALID, "coords must be 16-byte aligned");
   const GroupWs w = group_carve(workspace, n, stride, batch, g);
-  PNX_REQUIRE(workspace_bytes >= w.bytes, PNX_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, w.bytes);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, w.bytes, "pnx_group_points");
   hipStream_t st = (hipStream_t)stream;
   GroupGeomDev G;
   for (int k = 0; k < 3; k++) G.mn[k] = g->min[k], G.vs[k] = g->voxel[k], G.g[k] = g->grid[k], G.kmin[k] = g->keep_min[k], G.kmax[k] = g->keep_max[k];
@@ -570,9 +569,8 @@ int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t
     PNX_CHECK_HIP(hipMemsetAsync(grad_image, 0, (size_t)cells * channels * sizeof(float), st));
     return PNX_OK;
   }
-  PNX_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 255) == 0, PNX_ERR_INVALID, "pnx_bilinear_gather_backward: workspace must be 256-byte aligned");
   const BilGradWs ws = bilgrad_carve(workspace, n, cells);
-  PNX_REQUIRE(workspace_bytes >= ws.bytes, PNX_ERR_WORKSPACE, "pnx_bilinear_gather_backward: workspace %zu bytes < %zu needed", workspace_bytes, ws.bytes);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_bilinear_gather_backward");
   const float inv_ds = 1.0f / (float)ds_rate;
   const float mn0 = pos_min2_host[0], mn1 = pos_min2_host[1], vs0 = pos_voxel2_host[0], vs1 = pos_voxel2_host[1];
   k_bilinear_keys<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(batch, h, w, pos, pos_ld, mn0, mn1, vs0, vs1, cell_coords, unq_inv, inv_ds, n, ws.key);

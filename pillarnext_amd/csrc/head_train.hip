@@ -335,8 +335,8 @@ int pnx_conv3x3_smallk_wgrad(const void* x, const void* dy, float* dw, float* db
   PNX_REQUIRE(x && dy && dw && workspace && batch > 0 && h > 0 && w > 0, PNX_ERR_INVALID, "pnx_conv3x3_smallk_wgrad: bad arguments");
   PNX_REQUIRE(cin == HT_C && k >= 1 && k <= 4, PNX_ERR_UNSUPPORTED, "pnx_conv3x3_smallk_wgrad: %d -> %d channels (64 -> 1..4)", cin, k);
   PNX_REQUIRE(dtype == PNX_F32 || dtype == PNX_BF16, PNX_ERR_UNSUPPORTED, "pnx_conv3x3_smallk_wgrad: fp32 or bf16 maps");
-  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)workspace) & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
-  PNX_REQUIRE(workspace_bytes >= pnx_conv3x3_smallk_wgrad_workspace_bytes(k), PNX_ERR_WORKSPACE, "workspace too small");
+  PNX_REQUIRE(((uintptr_t)x & 15) == 0, PNX_ERR_INVALID, "16-byte alignment required");
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, pnx_conv3x3_smallk_wgrad_workspace_bytes(k), "pnx_conv3x3_smallk_wgrad");
   if (dtype == PNX_F32) return launch_wgrad_t<float>(x, dy, dw, dbias, batch, h, w, k, (float*)workspace, (hipStream_t)stream);
   return launch_wgrad_t<uint16_t>(x, dy, dw, dbias, batch, h, w, k, (float*)workspace, (hipStream_t)stream);
 }

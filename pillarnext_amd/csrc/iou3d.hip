@@ -373,11 +373,14 @@ int launch_pairs(int mode, const float* a, int64_t n, const float* b, int64_t m,
 
 // Host-side layout of the rotated NMS workspace in front of the mask words (all sizes follow from num_segments and max_seg_len).
 struct NmsLayout {
-  size_t pairs_off, tiles_off, counts_off, mask_off;
+  BoxPre* pre;
+  unsigned long long *pairs, *tiles;
+  unsigned int* counts;
+  size_t mask_off;  // the mask words follow the layout
   unsigned int pair_cap, tile_cap;
 };
 int g_nms_pair_cap_dbg = 0;  // 0: the default capacity
-NmsLayout nms_layout(int num_segments, int max_seg_len) {
+NmsLayout nms_layout(void* base, int num_segments, int max_seg_len) {
   NmsLayout l;
   const size_t cb = (size_t)((max_seg_len + 63) / 64), slots = (size_t)num_segments * cb * 64;
   size_t pc = slots * 32;  // room for 32 candidate pairs per box on average; what does not fit is done tile by tile
@@ -389,10 +392,12 @@ NmsLayout nms_layout(int num_segments, int max_seg_len) {
   size_t tc = (size_t)num_segments * cb * (cb + 1) / 2;  // every tile on or above the diagonal
   if (tc > ((size_t)1 << 24)) tc = (size_t)1 << 24;
   l.pair_cap = (unsigned int)pc, l.tile_cap = (unsigned int)(tc < 1 ? 1 : tc);
-  l.pairs_off = pnx_align_up(slots * sizeof(BoxPre), 256);
-  l.tiles_off = pnx_align_up(l.pairs_off + pc * sizeof(unsigned long long), 256);
-  l.counts_off = pnx_align_up(l.tiles_off + (size_t)l.tile_cap * sizeof(unsigned long long), 256);
-  l.mask_off = l.counts_off + 256;
+  PnxCarver c(base);
+  l.pre = c.take<BoxPre>(slots);
+  l.pairs = c.take<unsigned long long>(l.pair_cap);
+  l.tiles = c.take<unsigned long long>(l.tile_cap);
+  l.counts = c.take<unsigned int>(64);
+  l.mask_off = c.used();
   return l;
 }
 
@@ -410,37 +415,33 @@ int nms_batched(const float* boxes, const int32_t* seg_offsets, const int32_t* s
   PNX_REQUIRE(num_segments <= 65535, PNX_ERR_UNSUPPORTED, "more than 65535 segments");
   const int cbmax = (max_seg_len + 63) / 64;
   PNX_REQUIRE(cbmax * 8 <= 64 * 1024, PNX_ERR_UNSUPPORTED, "segment longer than 524288 boxes");
-  // the caller sizes the workspace with pnx_nms_workspace_bytes(total, ...); `total` lives in seg_offsets on the device, so here the alignment is checked
-  // and, for the rotated form below, the layout plus one box's row of mask words (the least any call with a box in it needs)
-  PNX_REQUIRE(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= 8, PNX_ERR_WORKSPACE, "bad workspace");
+  // the caller sizes the workspace with pnx_nms_workspace_bytes(total, ...); `total` lives in seg_offsets on the device, so what the host checks is the
+  // least any call with a box in it needs: one word, and for the rotated form below the layout plus one box's row of mask words
+  const char* who = ROTATED ? "pnx_nms_rotated_batched" : "pnx_nms_normal_batched";
   uint64_t* mask = (uint64_t*)workspace;
   dim3 grid(cbmax, cbmax, num_segments);
   if (ROTATED) {
     // workspace = [segment slots of BoxPre | pair list | overflow tile list | counters | mask words]; every size is known on the host
-    const NmsLayout lay = nms_layout(num_segments, max_seg_len);
+    const NmsLayout lay = nms_layout(workspace, num_segments, max_seg_len);
     // the mask words behind the layout: box gi owns the cbmax words mask[gi * cbmax ..] (k_box_pre, k_nms_pairs, k_nms_greedy).  The number of boxes lives in
     // seg_offsets on the device; what the host knows is that a call with a box in it has at least one such row, i.e. at least
     // pnx_nms_workspace_bytes(1, num_segments, max_seg_len): anything below that cannot hold the mask of ANY non-empty call
-    PNX_REQUIRE(workspace_bytes >= lay.mask_off + (size_t)cbmax * sizeof(uint64_t) + 8, PNX_ERR_WORKSPACE,
-                "workspace smaller than pnx_nms_workspace_bytes(1, num_segments, max_seg_len): no room for one box's mask words");
+    PNX_CHECK_WORKSPACE(workspace, workspace_bytes, lay.mask_off + (size_t)cbmax * sizeof(uint64_t) + 8, who);
     PNX_REQUIRE(max_seg_len < (1 << 20) && (size_t)num_segments * cbmax * (cbmax + 1) / 2 <= ((size_t)1 << 24), PNX_ERR_UNSUPPORTED,
                 "rotated NMS: segments of at most 2^20 boxes, at most 2^24 mask tiles in all");
-    char* wsb = reinterpret_cast<char*>(workspace);
-    BoxPre* pre = reinterpret_cast<BoxPre*>(wsb);
     NmsLists L;
-    L.pairs = reinterpret_cast<unsigned long long*>(wsb + lay.pairs_off);
-    L.tiles = reinterpret_cast<unsigned long long*>(wsb + lay.tiles_off);
-    L.counts = reinterpret_cast<unsigned int*>(wsb + lay.counts_off);
+    L.pairs = lay.pairs, L.tiles = lay.tiles, L.counts = lay.counts;
     L.pair_cap = lay.pair_cap, L.tile_cap = lay.tile_cap;
-    mask = reinterpret_cast<uint64_t*>(wsb + lay.mask_off);
+    mask = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + lay.mask_off);
     const size_t n_tiles = (size_t)num_segments * cbmax * (cbmax + 1) / 2;
     const int strip = n_tiles <= 2048 ? 4 : (n_tiles <= 8192 ? 8 : kStrip);
-    k_box_pre<<<dim3((unsigned)((max_seg_len + 255) / 256), (unsigned)num_segments), 256, 0, st>>>(boxes, seg_offsets, seg_len, cbmax, pre, mask, L.counts);
-    k_nms_cand<<<dim3((unsigned)((cbmax + strip - 1) / strip), (unsigned)cbmax, (unsigned)num_segments), 256, 0, st>>>(pre, seg_offsets, seg_len, thresh, cbmax,
+    k_box_pre<<<dim3((unsigned)((max_seg_len + 255) / 256), (unsigned)num_segments), 256, 0, st>>>(boxes, seg_offsets, seg_len, cbmax, lay.pre, mask, L.counts);
+    k_nms_cand<<<dim3((unsigned)((cbmax + strip - 1) / strip), (unsigned)cbmax, (unsigned)num_segments), 256, 0, st>>>(lay.pre, seg_offsets, seg_len, thresh, cbmax,
                                                                                                                       strip, L);
-    k_nms_pairs<<<1024, 256, 0, st>>>(pre, seg_offsets, thresh, mask, cbmax, L);
-    k_nms_tiles<<<2048, 64, 0, st>>>(pre, seg_offsets, seg_len, thresh, mask, cbmax, L);
+    k_nms_pairs<<<1024, 256, 0, st>>>(lay.pre, seg_offsets, thresh, mask, cbmax, L);
+    k_nms_tiles<<<2048, 64, 0, st>>>(lay.pre, seg_offsets, seg_len, thresh, mask, cbmax, L);
   } else {
+    PNX_CHECK_WORKSPACE(workspace, workspace_bytes, 8, who);
     k_nms_mask<false><<<grid, 64, 0, st>>>(boxes, seg_offsets, seg_len, thresh, mask, cbmax);
   }
   k_nms_greedy<<<num_segments, 64, cbmax * sizeof(uint64_t), st>>>(mask, seg_offsets, seg_len, cbmax, post_max, keep, keep_count);
@@ -474,7 +475,7 @@ int32_t pnx_debug_nms_pair_cap(int32_t cap) {  // test hook: capacity of the rot
 size_t pnx_nms_workspace_bytes(int64_t total_boxes, int32_t num_segments, int32_t max_seg_len) {
   if (total_boxes <= 0 || max_seg_len <= 0) return 8;
   // (rotated NMS) per-box precompute, candidate-pair list, overflow tile list, counters -- then the mask words
-  return nms_layout(num_segments > 0 ? num_segments : 0, max_seg_len).mask_off + (size_t)total_boxes * (size_t)((max_seg_len + 63) / 64) * sizeof(uint64_t) + 8;
+  return nms_layout(nullptr, num_segments > 0 ? num_segments : 0, max_seg_len).mask_off + (size_t)total_boxes * (size_t)((max_seg_len + 63) / 64) * sizeof(uint64_t) + 8;
 }
 
 int pnx_nms_rotated_batched(const float* boxes, const int32_t* seg_offsets, const int32_t* seg_len, int32_t num_segments, int32_t max_seg_len,

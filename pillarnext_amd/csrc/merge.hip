@@ -78,6 +78,23 @@ __global__ __launch_bounds__(kBlock) void k_merge_write(const float* __restrict_
   o[1 + ncopy] = s.time;
 }
 
+// keep flag and exclusive prefix per raw row, block totals of the two-level scan
+struct MergeWs {
+  uint32_t *keep, *pre, *blk;
+  int nblk;
+  size_t bytes;
+};
+MergeWs merge_carve(void* base, int64_t n_raw) {
+  MergeWs w;
+  PnxCarver c(base);
+  w.nblk = (int)((n_raw + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
+  w.keep = c.take<uint32_t>(n_raw + 8);
+  w.pre = c.take<uint32_t>(n_raw + 8);
+  w.blk = c.take<uint32_t>(w.nblk + 8);
+  w.bytes = c.used();
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -86,8 +103,7 @@ size_t pnx_merge_sweeps_desc_bytes(void) { return sizeof(SegDesc); }
 
 size_t pnx_merge_sweeps_workspace_bytes(int64_t n_raw) {
   if (n_raw < 0) return 0;
-  const int64_t nblk = (n_raw + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS + 8;
-  return pnx_align_up((size_t)(n_raw + 8) * 4, 256) * 2 + pnx_align_up((size_t)nblk * 4, 256);
+  return merge_carve(nullptr, n_raw).bytes;
 }
 
 int pnx_merge_sweeps(const float* raw, int64_t n_raw, int32_t raw_stride, int32_t n_copy, const void* seg_descs_dev, int32_t n_segments, float* out,
@@ -96,23 +112,19 @@ int pnx_merge_sweeps(const float* raw, int64_t n_raw, int32_t raw_stride, int32_
   PNX_REQUIRE(n_raw == 0 || (raw && seg_descs_dev && out), PNX_ERR_INVALID, "null pointer");
   PNX_REQUIRE(n_out_dev != nullptr, PNX_ERR_INVALID, "n_out is NULL");
   PNX_REQUIRE(n_raw < ((int64_t)1 << 31) - 64, PNX_ERR_UNSUPPORTED, "more than 2^31 rows");
-  PNX_REQUIRE(workspace && workspace_bytes >= pnx_merge_sweeps_workspace_bytes(n_raw), PNX_ERR_WORKSPACE, "workspace too small");
+  const MergeWs w = merge_carve(workspace, n_raw);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, w.bytes, "pnx_merge_sweeps");
   hipStream_t st = (hipStream_t)stream;
-  PnxCarver c(workspace);
-  uint32_t* keep = c.take<uint32_t>(n_raw + 8);
-  uint32_t* pre = c.take<uint32_t>(n_raw + 8);
-  const int nblk = (int)((n_raw + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
-  uint32_t* blk = c.take<uint32_t>(nblk + 8);
   if (n_raw == 0) {
     PNX_CHECK_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(int32_t), st));
     return PNX_OK;
   }
   const SegDesc* segs = reinterpret_cast<const SegDesc*>(seg_descs_dev);
   const int nb = (int)((n_raw + kBlock - 1) / kBlock);
-  k_merge_flags<<<nb, kBlock, 0, st>>>(raw, raw_stride, n_raw, segs, n_segments, keep);
-  k_scan_local<SCAN_IDENT><<<nblk, kBlock, 0, st>>>(keep, n_raw, pre, blk);
-  k_scan_blocks<<<1, kBlock, 0, st>>>(blk, nblk, n_out_dev);
-  k_merge_write<<<nb, kBlock, 0, st>>>(raw, raw_stride, n_raw, segs, n_segments, keep, pre, blk, n_copy, out, n_copy + 2, n_out_dev);
+  k_merge_flags<<<nb, kBlock, 0, st>>>(raw, raw_stride, n_raw, segs, n_segments, w.keep);
+  k_scan_local<SCAN_IDENT><<<w.nblk, kBlock, 0, st>>>(w.keep, n_raw, w.pre, w.blk);
+  k_scan_blocks<<<1, kBlock, 0, st>>>(w.blk, w.nblk, n_out_dev);
+  k_merge_write<<<nb, kBlock, 0, st>>>(raw, raw_stride, n_raw, segs, n_segments, w.keep, w.pre, w.blk, n_copy, out, n_copy + 2, n_out_dev);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

@@ -88,11 +88,27 @@ struct PnxCarver {
   T* take(size_t count) {
     off = pnx_align_up(off, 256);
     T* r = (T*)(base ? base + off : nullptr);
+#ifdef PNX_CARVE_PROBE  // tools/carve_check.cpp, host sanitizers: write the first and the last element of every field
+    if (base && count) r[0] = T(), r[count - 1] = T();
+#endif
     off += count * sizeof(T);
     return r;
   }
   size_t used() const { return pnx_align_up(off, 256); }
 };
+
+// The one check in front of every carve (include/pnx.h: the workspace contract).  PnxCarver aligns offsets, not addresses: the base has to be aligned.
+inline int pnx_check_workspace(const void* workspace, size_t workspace_bytes, size_t need, const char* entry) {
+  PNX_REQUIRE(workspace != nullptr, PNX_ERR_INVALID, "%s: workspace is NULL (%zu bytes needed)", entry, need);
+  PNX_REQUIRE(workspace_bytes >= need, PNX_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", entry, workspace_bytes, need);
+  PNX_REQUIRE(((uintptr_t)workspace & 255) == 0, PNX_ERR_INVALID, "%s: workspace must be 256-byte aligned (%zu bytes given, %zu needed)", entry,
+              workspace_bytes, need);
+  return PNX_OK;
+}
+#define PNX_CHECK_WORKSPACE(workspace, workspace_bytes, need, entry)                             \
+  do {                                                                                           \
+    if (int _rc = pnx_check_workspace((workspace), (workspace_bytes), (need), (entry))) return _rc; \
+  } while (0)
 
 // Device-side copy of pnx_geom plus the padded row length of the occupancy bitmap.
 struct PnxGeomDev {

@@ -366,12 +366,6 @@ int pl_check(const char* who, const float* x, int64_t ldx, int64_t n, int cin, c
   return PNX_OK;
 }
 
-int ws_check(const char* who, const void* ws, size_t have, size_t need) {
-  PNX_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, PNX_ERR_INVALID, "%s: workspace must be 256-byte aligned", who);
-  PNX_REQUIRE(have >= need, PNX_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu needed", who, have, need);
-  return PNX_OK;
-}
-
 template <int MODE>
 int launch_rows(const PlArgs& a, int blocks, hipStream_t st) {
   int chunks = 1;
@@ -406,7 +400,7 @@ int pnx_point_layer_stats(const float* x, int32_t ldx, int64_t n, int32_t cin, c
   if (int rc = pl_check(who, x, ldx, n, cin, w, cout)) return rc;
   PNX_REQUIRE(sums != nullptr, PNX_ERR_INVALID, "%s: null pointer (sums)", who);
   const PlWs ws = pl_carve(workspace, n, cin, cout, false);
-  if (int rc = ws_check(who, workspace, workspace_bytes, ws.bytes)) return rc;
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, who);
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) {
     PNX_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * cout, st));
@@ -455,7 +449,7 @@ int pnx_point_layer_backward_stats(const float* x, int32_t ldx, int64_t n, int32
   if (int rc = grad_check(who, n, cout, dy, lddy, inv, num_groups, dgmax, argmax)) return rc;
   PNX_REQUIRE(prm != nullptr && sums != nullptr, PNX_ERR_INVALID, "%s: null pointer (prm / sums)", who);
   const PlWs ws = pl_carve(workspace, n, cin, cout, false);
-  if (int rc = ws_check(who, workspace, workspace_bytes, ws.bytes)) return rc;
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, who);
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) {
     PNX_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * cout, st));
@@ -480,7 +474,7 @@ int pnx_point_layer_backward(const float* x, int32_t ldx, int64_t n, int32_t cin
   PNX_REQUIRE(prm != nullptr && dw != nullptr, PNX_ERR_INVALID, "%s: null pointer (prm / dw)", who);
   PNX_REQUIRE(dx == nullptr || lddx >= cin, PNX_ERR_INVALID, "%s: lddx %d < cin %d", who, lddx, cin);
   const PlWs ws = pl_carve(workspace, n, cin, cout, true);
-  if (int rc = ws_check(who, workspace, workspace_bytes, ws.bytes)) return rc;
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, who);
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) {
     PNX_CHECK_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)cout * cin, st));

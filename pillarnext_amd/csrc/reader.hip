@@ -668,7 +668,7 @@ inline int64_t cells_of(const GeomDev& g) { return (int64_t)g.B * g.gx * g.gyp; 
 
 inline int nblocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
-int check_common(const float* points, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, void* ws, size_t ws_bytes) {
+int check_common(const char* who, const float* points, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, void* ws, size_t ws_bytes) {
   PNX_REQUIRE(g != nullptr, PNX_ERR_INVALID, "geom is NULL");
   PNX_REQUIRE(n >= 0 && batch >= 1, PNX_ERR_INVALID, "n_points=%lld batch=%d", (long long)n, batch);
   PNX_REQUIRE(n == 0 || points != nullptr, PNX_ERR_INVALID, "points is NULL");
@@ -676,10 +676,7 @@ int check_common(const float* points, int64_t n, int32_t stride, int32_t batch, 
   PNX_REQUIRE(g->gx > 0 && g->gy > 0, PNX_ERR_INVALID, "empty grid");
   PNX_REQUIRE(cells_padded(g, batch) < ((int64_t)1 << 31), PNX_ERR_UNSUPPORTED, "batch*gx*gy exceeds the int32 cell key");
   PNX_REQUIRE(n < ((int64_t)1 << 31) - 64, PNX_ERR_UNSUPPORTED, "more than 2^31 points");
-  PNX_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, PNX_ERR_INVALID, "workspace must be 256-byte aligned");
-  const size_t need = pnx_reader_workspace_bytes(n, batch, g);
-  PNX_REQUIRE(ws_bytes >= need, PNX_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", ws_bytes, need);
-  return PNX_OK;
+  return pnx_check_workspace(ws, ws_bytes, pnx_reader_workspace_bytes(n, batch, g), who);
 }
 
 // Steps 1-4: keys, bitmap scan, rank/slots/coords, CSR.  Leaves counters = {P, N'}.
@@ -992,7 +989,7 @@ int pnx_reader_forward(const float* points, int64_t n, int32_t stride, int32_t b
                        void* canvas, int32_t canvas_dtype, int32_t canvas_layout, uint8_t* occupancy, float* feat_max, int32_t* coords,
                        int64_t pillar_capacity, int64_t* unq_inv, int32_t* pillar_of_point, int32_t* counts, void* workspace,
                        size_t workspace_bytes, pnx_stream_t stream) {
-  int rc = check_common(points, n, stride, batch, g, workspace, workspace_bytes);
+  int rc = check_common("pnx_reader_forward", points, n, stride, batch, g, workspace, workspace_bytes);
   if (rc != PNX_OK) return rc;
   PNX_REQUIRE(pfn_folded != nullptr, PNX_ERR_INVALID, "pfn_folded is NULL");
   PNX_REQUIRE(canvas_dtype >= PNX_F32 && canvas_dtype <= PNX_F16, PNX_ERR_INVALID, "bad canvas_dtype %d", canvas_dtype);
@@ -1031,7 +1028,7 @@ size_t pnx_pfn_train_partial_floats(int32_t F, int32_t which) {
 int pnx_pfn_forward_train(int32_t pass, const float* points, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, const float* params,
                           float* partials, float* feat_max, int64_t pillar_capacity, int32_t* coords, int32_t* pillar_of_point, int32_t* counts,
                           void* workspace, size_t workspace_bytes, pnx_stream_t stream) {
-  int rc = check_common(points, n, stride, batch, g, workspace, workspace_bytes);
+  int rc = check_common("pnx_pfn_forward_train", points, n, stride, batch, g, workspace, workspace_bytes);
   if (rc != PNX_OK) return rc;
   PNX_REQUIRE(pass >= 0 && pass <= 2, PNX_ERR_INVALID, "pass %d not in 0..2", pass);
   PNX_REQUIRE(pass == 2 || partials != nullptr, PNX_ERR_INVALID, "partials is NULL");
@@ -1055,7 +1052,7 @@ int pnx_pfn_backward(int32_t pass, int64_t n, int32_t stride, int32_t batch, con
   PNX_REQUIRE(g != nullptr && workspace != nullptr && params && grad_feat_max && feat_max && partials, PNX_ERR_INVALID, "null pointer");
   PNX_REQUIRE(pass == 0 || pass == 1, PNX_ERR_INVALID, "pass %d not in 0..1", pass);
   PNX_REQUIRE(stride >= 4 && stride <= 7, PNX_ERR_UNSUPPORTED, "row_stride %d", stride);
-  PNX_REQUIRE(workspace_bytes >= pnx_reader_workspace_bytes(n, batch, g), PNX_ERR_WORKSPACE, "workspace too small");
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, pnx_reader_workspace_bytes(n, batch, g), "pnx_pfn_backward");
   const ReaderWs w = carve(workspace, n, batch, g);  // the records written by pnx_pfn_forward_train(pass 0) on the same workspace
   return pnx_launch_pfn_train(w, stride - 1, pass == 0 ? 3 : 4, params, partials, grad_feat_max, feat_max, nullptr, 0, (hipStream_t)stream);
 }
@@ -1111,7 +1108,7 @@ int pnx_profile_end(float* reader_us, float* canvas_us, int32_t* samples) {
 int pnx_voxelize(const float* points, int64_t n, int32_t stride, int32_t batch, const pnx_geom* g, float* features, int32_t* coords,
                  int64_t pillar_capacity, int64_t* unq_inv, int32_t* pillar_of_point, int32_t* counts, void* workspace,
                  size_t workspace_bytes, pnx_stream_t stream) {
-  int rc = check_common(points, n, stride, batch, g, workspace, workspace_bytes);
+  int rc = check_common("pnx_voxelize", points, n, stride, batch, g, workspace, workspace_bytes);
   if (rc != PNX_OK) return rc;
   PNX_REQUIRE(coords == nullptr || pillar_capacity > 0, PNX_ERR_INVALID, "pillar_capacity must be > 0");
   hipStream_t st = (hipStream_t)stream;

@@ -98,11 +98,9 @@ int pnx_scatter_max(const float* x, const int64_t* index, int64_t n, int32_t cha
   if (P == 0) return PNX_OK;
   PNX_REQUIRE(out && workspace && (n == 0 || (x && index)), PNX_ERR_INVALID, "null pointer");
   PNX_REQUIRE(n < ((int64_t)1 << 31) - 64 && P < ((int64_t)1 << 31) - 64, PNX_ERR_UNSUPPORTED, "more than 2^31 rows");
-  PNX_REQUIRE(((uintptr_t)workspace & 255) == 0, PNX_ERR_INVALID, "workspace must be 256-byte aligned");
-  const size_t need = pnx_scatter_max_workspace_bytes(n, P);
-  PNX_REQUIRE(workspace_bytes >= need, PNX_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
   const SmWs w = sm_carve(workspace, n, P);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, w.bytes, "pnx_scatter_max");
+  hipStream_t st = (hipStream_t)stream;
   PNX_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)P * 4, st));
   const int nbn = (int)((n + kBlock - 1) / kBlock);
   if (n > 0) k_sm_count<<<nbn, kBlock, 0, st>>>(index, n, P, w.count, w.slot);

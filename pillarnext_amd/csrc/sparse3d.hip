@@ -414,9 +414,7 @@ void sp3_wgrad_nt(int nt, dim3 grid, hipStream_t st, const float* x, int64_t n_i
 
 int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
   *ix = sp3_carve(index, g);
-  PNX_REQUIRE(index != nullptr && ((uintptr_t)index & 255) == 0, PNX_ERR_INVALID, "sparse3d: index must be a 256-byte aligned buffer");
-  PNX_REQUIRE(index_bytes >= ix->bytes, PNX_ERR_WORKSPACE, "sparse3d: index %zu bytes < %zu needed", index_bytes, ix->bytes);
-  return PNX_OK;
+  return pnx_check_workspace(index, index_bytes, ix->bytes, "sparse3d index");
 }
 
 // bitmap already marked: word prefix (level 1 + level 2), total set bits -> count
@@ -675,8 +673,7 @@ int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, in
     return PNX_OK;
   }
   PNX_REQUIRE(x && dy && map && workspace, PNX_ERR_INVALID, "pnx_sp3_wgrad: null pointer");
-  const size_t need = pnx_sp3_wgrad_workspace_bytes(n_out, taps, cin, cout);
-  PNX_REQUIRE(workspace_bytes >= need, PNX_ERR_WORKSPACE, "pnx_sp3_wgrad: workspace %zu bytes < %zu needed", workspace_bytes, need);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, pnx_sp3_wgrad_workspace_bytes(n_out, taps, cin, cout), "pnx_sp3_wgrad");
   const Sp3WgradSplit sp = sp3_wgrad_split(n_out, cout);
   const dim3 grid((unsigned)sp.P, (unsigned)sp.groups);
   const int nt = (cin + 15) / 16;

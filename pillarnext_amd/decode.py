@@ -76,7 +76,7 @@ class PackedDecoder:
         else:
             self.selection = "torchsort" if on("PNX_DECODE_TORCH_SORT") else "keysort"
         self._dev = {}   # Layout per (kind, batch, element dtype, (C, H, W) per task, device); launch_lazy_fused's scratch under ("lazy_fused", ...)
-        self._ws = {}    # selection workspaces, grown on demand
+        self._topk_ws, self._keysort_ws = ops.Workspace(), ops.Workspace()    # selection scratch
         self._tptr = {}
         self._pin = {}
 
@@ -122,12 +122,6 @@ class PackedDecoder:
             check(lib().pnx_decode_keys(ptr(p), dt, B, self.nc_total, h.descs[t], kp, stream_ptr()), "pnx_decode_keys")
         return keys
 
-    def _workspace(self, name, nbytes, dev):
-        ws = self._ws.get(name)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = self._ws[name] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return ws
-
     def _select(self, keys, lay):
         """The first pre_max keys of every list in stable ascending order, by self.selection.  -> skeys, order (source index of every sorted
         key; candidate j of list s at seg_start[s] + j), seg_start, seg_len (S,) int32 <= pre_max, seg_total (S,) int32 = valid keys of the list."""
@@ -140,7 +134,7 @@ class PackedDecoder:
             seg_start = torch.empty((S,), dtype=torch.int64, device=dev)
             seg_len = torch.empty((S,), dtype=torch.int32, device=dev)
             seg_total = torch.empty((S,), dtype=torch.int32, device=dev)
-            ws = self._workspace("topk", int(L.pnx_decode_topk_workspace_bytes(n, S)) + 256, dev)
+            ws = self._topk_ws.get(int(L.pnx_decode_topk_workspace_bytes(n, S)), dev)
             check(L.pnx_decode_topk(ptr(keys), n, S, self.pre_max, ptr(skeys), ptr(order), ptr(seg_start), ptr(seg_len), ptr(seg_total), ptr(ws),
                                     ws.numel(), stream_ptr()), "pnx_decode_topk")
             return skeys, order, seg_start, seg_len, seg_total
@@ -150,7 +144,7 @@ class PackedDecoder:
         else:
             # the same stable sort over the 32 + bit_length(S) bits that can differ (pnx_sort_keys: 5 radix passes instead of 8)
             skeys, order = torch.empty_like(keys), torch.empty_like(keys)
-            ws = self._workspace("keysort", int(L.pnx_sort_keys_workspace_bytes(n)), dev)
+            ws = self._keysort_ws.get(int(L.pnx_sort_keys_workspace_bytes(n)), dev)
             check(L.pnx_sort_keys(ptr(keys), n, S, ptr(skeys), ptr(order), ptr(ws), ws.numel(), stream_ptr()), "pnx_sort_keys")
         seg_start = torch.searchsorted(skeys ^ _SIGN, lay.bounds)
         seg_total = (seg_start[1:] - seg_start[:-1]).to(torch.int32)
@@ -259,7 +253,7 @@ class PackedDecoder:
             scratch = {"keys": (n_keys, i64), "sorted_keys": (n_rows, i64), "order": (n_rows, i64), "seg_start": (S, i64), "local": (n_rows, i64),
                        "seg_len": (S, i32), "seg_total": (S, i32), "cand": (n_rows * 10, f32), "boxes9": (n_rows * 9, f32), "boxes7": (n_rows * 7, f32),
                        "scores": (n_rows, f32), "flag": (1, i32), "keep": (n_rows, i32), "keep_count": (S, i32), "out": (S * self.post_max * 10, f32),
-                       "topk_ws": (int(L.pnx_decode_topk_workspace_bytes(n_keys, S)) + 256, u8),
+                       "topk_ws": (int(L.pnx_decode_topk_workspace_bytes(n_keys, S)), u8),
                        "nms_ws": (max(int(L.pnx_nms_workspace_bytes(n_rows, S, self.pre_max)), 1), u8)}
             d = _PnxLazyDecode()
             d.n_tasks, d.n_classes_total, d.batch, d.pre_max, d.post_max, d.dtype = T, self.nc_total, B, self.pre_max, self.post_max, ops._DT[dtype]

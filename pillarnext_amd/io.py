@@ -89,7 +89,9 @@ class SweepMerger:
     the collated (N, 2+n_copy) point buffer of the reader, in one stable compaction (csrc/merge.hip)."""
 
     def __init__(self):
-        self._ws = None
+        from . import ops
+
+        self._ws = ops.Workspace()
 
     def descriptors(self, segments, device):
         """Segment descriptors on the device (build once per segment layout, reuse every step)."""
@@ -109,14 +111,12 @@ class SweepMerger:
         assert raw.is_cuda and raw.dtype == torch.float32 and raw.is_contiguous()
         n, stride = raw.shape
         desc, nseg = segments if isinstance(segments, tuple) else self.descriptors(segments, raw.device)
-        need = int(L.pnx_merge_sweeps_workspace_bytes(n)) + 256
-        if self._ws is None or self._ws.numel() < need or self._ws.device != raw.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=raw.device)
+        ws = self._ws.get(int(L.pnx_merge_sweeps_workspace_bytes(n)), raw.device)
         if out is None:
             out = torch.empty((n, n_copy + 2), dtype=torch.float32, device=raw.device)
         assert out.shape[0] >= n and out.shape[1] == n_copy + 2 and out.is_contiguous()
         if n_out is None:
             n_out = torch.zeros(1, dtype=torch.int32, device=raw.device)
-        _lib.check(L.pnx_merge_sweeps(_lib.ptr(raw), n, stride, n_copy, _lib.ptr(desc), nseg, _lib.ptr(out), _lib.ptr(n_out), _lib.ptr(self._ws),
-                                      self._ws.numel(), _lib.stream_ptr()), "pnx_merge_sweeps")
+        _lib.check(L.pnx_merge_sweeps(_lib.ptr(raw), n, stride, n_copy, _lib.ptr(desc), nseg, _lib.ptr(out), _lib.ptr(n_out), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_ptr()), "pnx_merge_sweeps")
         return out[:n], n_out

@@ -115,7 +115,7 @@ class _CenterLossFn(torch.autograd.Function):
             raise ops.PnxError(f"fused center loss: label shapes disagree (ind {tuple(ind.shape)}, cat {tuple(cat.shape)}, mask {tuple(mask.shape)}, "
                                f"anno_box {tuple(anno.shape)}, gt_boxes {tuple(gtb.shape)})")
         losses = torch.empty(16, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.pnx_center_loss_workspace_bytes(B, M)) + 256, dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(L.pnx_center_loss_workspace_bytes(B, M)), dtype=torch.uint8, device=dev)
         arr = (ctypes.c_void_p * 7)(*[t.data_ptr() if t is not None else None for t in maps])
         g4 = (ctypes.c_float * 4)(*[float(v) for v in geom4])
         check(L.pnx_center_loss_forward(arr, ptr(hm_t), ptr(ind), ptr(mask), ptr(cat), ptr(anno), ptr(gtb), B, C, H, W, M, g4, int(bool(with_reg_iou)),

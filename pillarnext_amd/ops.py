@@ -18,15 +18,30 @@ def _need_cuda(t, name):
 
 
 class Workspace:
-    """Grow-only device scratch buffer, one per (device, stream user)."""
+    """Grow-only device scratch, one buffer per (device, current stream): the include/pnx.h contract (256-byte aligned, one workspace per stream).
+    Scratch that persists between calls uses a Workspace.  Scratch that lives as long as one call or one autograd ctx is a plain
+    torch.empty(nbytes, dtype=torch.uint8) of exactly the size the library asks for."""
 
-    def __init__(self):
-        self.buf = None
+    def __init__(self, headroom=1.25):
+        self._bufs, self._headroom = {}, headroom   # a request that depends on the data (point counts) creeps: over-allocate; one that follows from layer shapes: 1.0
+
+    @staticmethod
+    def _key(device=None):
+        dev = torch.cuda.current_device() if device is None or device.index is None else device.index
+        return dev, torch.cuda.current_stream(dev).cuda_stream
+
+    @property
+    def buf(self):
+        """The buffer of the current device and stream, or None."""
+        return self._bufs.get(self._key())
 
     def get(self, nbytes, device):
-        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
-            self.buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-        return self.buf
+        key = self._key(torch.device(device))
+        buf = self._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._bufs[key] = torch.empty(max(int(nbytes * self._headroom), 256), dtype=torch.uint8, device=device)  # never empty: a null base is an error
+        assert buf.data_ptr() % 256 == 0
+        return buf
 
 
 # --------------------------------------------------------------------------------------------- reader
@@ -351,8 +366,7 @@ class PointLayer(torch.autograd.Function):
         if dy is None and dgmax is None:
             return (None,) * 10
         nbytes = lib().pnx_point_layer_workspace_bytes(n, cin, cout, 1)
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)       # holds dxpre (n, cout): a transient of this call, not kept
-        ws = ws[(-ws.data_ptr()) % 256:]
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)       # holds dxpre (n, cout): a transient of this call, not kept
         sums = torch.empty((2, cout), dtype=torch.float64, device=dev)
         grad = (ptr(dy), _ld(dy) if dy is not None else cout, ptr(inv) if dgmax is not None else None, G, ptr(dgmax), ptr(arg) if dgmax is not None else None)
         check(lib().pnx_point_layer_backward_stats(ptr(x), _ld(x), n, cin, ptr(w), cout, ptr(prm), *grad, ptr(sums), ptr(ws), ws.numel(), stream_ptr()),
@@ -655,16 +669,9 @@ def sephead_lazy(tasks, class_task, batch, local, seg_len, pre_max):
     return out
 
 
-_WGRAD_WS = {}
-
-
-def _wgrad_workspace(nbytes, device):
-    """The weight-gradient kernels' partial sums live until their reduction ran: one uint8 buffer per (size, device, stream), kept."""
-    key = (nbytes, device, torch.cuda.current_stream().cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+# The weight-gradient kernels' partial sums: written and reduced inside one C call on one stream, so one buffer per stream serves every layer.  75 MB for
+# every 3x3 layer whatever its channels: no headroom, or the step's peak memory grows by a quarter of that.
+_PARTIALS_WS = Workspace(headroom=1.0)
 
 
 # The training convolutions run on 1, 2 or 3 bf16 pieces per operand: one bf16 tensor (bf16 autocast), or the (hi, lo) / (hi, mid, lo) pieces of an fp32
@@ -757,7 +764,7 @@ def conv3x3_wgrad(x, dy, mask, stride=1):
     nbytes = int(lib().pnx_conv3x3_wgrad_workspace_bytes(ci, co))
     if nbytes == 0:
         raise PnxError(f"conv3x3_wgrad: no kernel for {ci} -> {co} channels")
-    ws = _wgrad_workspace(nbytes, xs[0].device)
+    ws = _PARTIALS_WS.get(nbytes, xs[0].device)
     dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=xs[0].device)
     name = "pnx_conv3x3_wgrad_" + _PIECES_TAG[len(xs)]
     check(getattr(lib(), name)(*map(ptr, xs), *map(ptr, gs), ptr(mask), ptr(dw), B, H, W, ci, co, stride, ptr(ws), ws.numel(), stream_ptr()), name)
@@ -814,7 +821,7 @@ def conv3x3_smallk_wgrad(x, dy, want_bias=True):
         raise PnxError("conv3x3_smallk_wgrad: x (B,64,H,W), dy (B,k,H,W) of the same dtype, k <= 4")
     dyc = dy.permute(0, 2, 3, 1).contiguous()    # NHWC with k channels (a no-op for a channels_last gradient)
     nbytes = int(lib().pnx_conv3x3_smallk_wgrad_workspace_bytes(k))
-    ws = _wgrad_workspace(nbytes, x.device)
+    ws = _PARTIALS_WS.get(nbytes, x.device)
     dw = torch.empty((k, 64, 3, 3), dtype=torch.float32, device=x.device)
     db = torch.empty((k,), dtype=torch.float32, device=x.device) if want_bias else None
     check(lib().pnx_conv3x3_smallk_wgrad(ptr(x), ptr(dyc), ptr(dw), ptr(db), B, H, W, 64, k, 0 if x.dtype == torch.float32 else 1, ptr(ws), ws.numel(), stream_ptr()),

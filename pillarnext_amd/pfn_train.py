@@ -49,7 +49,7 @@ class FusedPFNTrain(torch.autograd.Function):
         geom = mod._geom
         group = mod.sync_group if mod.sync else False
         eps = float(mod.pfn_layers[0].norm.eps)
-        ws = torch.empty(int(L.pnx_reader_workspace_bytes(n, batch, ctypes.byref(geom))) + 256, dtype=torch.uint8, device=dev)
+        ws = torch.empty(int(L.pnx_reader_workspace_bytes(n, batch, ctypes.byref(geom))), dtype=torch.uint8, device=dev)
         cap = max(min(n, batch * int(geom.gx) * int(geom.gy)), 1)
         coords = torch.empty((cap, 3), dtype=torch.int32, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)

@@ -83,7 +83,7 @@ def test_backward_entry_point_validates_before_launching():
     assert call(pld=1) == -1 and b"bad arguments" in L.pnx_last_error()
     assert call(c=0, ld=0) == -1 and b"bad arguments" in L.pnx_last_error()
     assert call(b=1 << 15, h=1 << 8, w=1 << 8) == -2 and b"32-bit" in L.pnx_last_error()
-    assert call(ws=ctypes.c_void_p(p.value + 4)) == -1 and b"aligned" in L.pnx_last_error()
+    assert call(ws=ctypes.c_void_p(p.value + 4), wsb=1 << 20) == -1 and b"aligned" in L.pnx_last_error()   # the size is checked first: give it enough
     assert call() == -3 and b"workspace" in L.pnx_last_error()                                          # 8 bytes of workspace
     need = L.pnx_bilinear_gather_backward_workspace_bytes(10, 2, 9, 11)
     assert need >= 3 * 10 * 4 + (2 * 9 * 11 + 1) * 4 and need % 256 == 0
