@@ -457,6 +457,10 @@ size_t pnx_nms_workspace_bytes(int64_t total_boxes, int32_t num_segments, int32_
  * the tiles that do not fit down the tile-by-tile path, whose keep indices must be identical.  Changes the layout pnx_nms_workspace_bytes describes:
  * query the workspace size again after calling it.  Not thread-safe. */
 int32_t pnx_debug_nms_pair_cap(int32_t cap);
+/* Test hook: csrc/pnx_detmath.h element by element, sin_a[i], cos_a[i] = sin, cos of a[i] and atan2_ab[i] = atan2(a[i], b[i]).  on_device != 0: device
+ * pointers, one kernel on `stream`; on_device == 0: HOST pointers, evaluated by the host twins' build of the header, synchronous, no GPU needed.
+ * The two must agree bit for bit (tests/test_detmath_cpu.py, tests/test_gpu_iou_degenerate.py). */
+int pnx_debug_detmath(const float* a, const float* b, int64_t n, float* sin_a, float* cos_a, float* atan2_ab, int32_t on_device, pnx_stream_t stream);
 int pnx_nms_rotated_batched(const float* boxes, const int32_t* seg_offsets, const int32_t* seg_len, int32_t num_segments, int32_t max_seg_len,
                             const float* thresh, int32_t post_max, int32_t* keep, int32_t* keep_count, void* workspace,
                             size_t workspace_bytes, pnx_stream_t stream);

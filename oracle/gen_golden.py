@@ -291,6 +291,63 @@ def gen_ref_random():
     print("[golden] ref_iou_random:", {k: v.shape for k, v in out.items()})
 
 
+def gen_degenerate():
+    """tests/golden/iou_degenerate.npz: the degenerate pair families and NMS lists of tests/iou_cases.py, the compiled reference's aligned IoU, a 17 x 19
+    N x M block and keep lists on them, and per family how far the reference sits from true geometry (tests/iou_exact_ref.py) and the host twin from the
+    reference.  Inputs and recorded results only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import iou_cases as C
+    import iou_exact_ref as X
+
+    out, rows = {}, []
+    for name in C.FAMILIES:
+        a, b = C.family(name)
+        ref = O.ref_boxes_aligned_iou_bev(a, b)
+        out[name + "_a"], out[name + "_b"], out[name + "_ref_iou"] = a, b, ref
+        out[name + "_ref_nm"] = O.ref_boxes_iou_bev(a[:17], b[:19])
+        assert np.array_equal(ref.view(np.uint32), O.boxes_aligned_iou_bev(a, b, "libm").view(np.uint32)), name   # the oracle stays pinned on these too
+        row = X.deviations(ref, C.host_aligned_iou(a, b), X.aligned(a, b)[1])
+        rows.append(row)
+        if name == "tiny_heading":
+            print(f"[golden] degenerate tiny_heading: share of pairs at 16 vertices {np.mean(O.overlap_vertex_count(a, b) == 16):.3f}")
+        print(f"[golden] degenerate {name:20s} n={len(a):3d} max|ref-exact| {row[0]:.3e}  share ref>1 {row[1]:.3f}  max|host-ref| {row[2]:.3e}")
+    out["dev_names"] = np.asarray(list(C.FAMILIES))
+    out["dev_ref_exact_max"], out["dev_share_gt1"], out["dev_host_ref_max"] = (np.asarray(c, np.float64) for c in zip(*rows))
+
+    def nms_case(key, boxes, thr, margin=None):
+        keep = O.ref_nms_rotated(boxes, thr)
+        assert np.array_equal(keep, O.nms_rotated(boxes, thr, "det")), key      # a pair between libm's and the deterministic value: pick another list
+        out[f"nms_{key}_boxes"], out[f"nms_{key}_thr"], out[f"nms_{key}_keep"] = boxes, np.float32(thr), keep.astype(np.int32)
+        print(f"[golden] degenerate nms {key}: kept {len(keep)} of {len(boxes)} at {thr!r}" + (f" (margin {margin:.2e})" if margin is not None else ""))
+
+    third = np.float32(1.0) / np.float32(3.0)
+    assert third.view(np.uint32) == 0x3EAAAAAB
+    for tag, thr in (("lo", np.nextafter(third, np.float32(0))), ("at", third), ("hi", np.nextafter(third, np.float32(1)))):
+        nms_case(f"chain_x_{tag}", C.chain(200), thr)
+        nms_case(f"chain_x130_{tag}", C.chain(200)[:130].copy(), thr)
+        nms_case(f"chain_y_{tag}", C.chain(200, along_y=True), thr)
+    nms_case("spread_neg", C.spread_130(), -1.0)
+    for tag, thr in (("t020", 0.2), ("t070", 0.7), ("t090", 0.9)):
+        # gen_iou_nms re-draws until no pair is within 1e-4 of the threshold; with 6e5 overlapping pairs in one cluster no seed achieves that at 0.7 or
+        # 0.9.  What the margin is for is that libm and the deterministic transcendentals decide every pair alike: re-draw until the two keep lists
+        # agree (nms_case asserts it) and record the margin that the seed has.
+        for seed in range(7000, 7040):
+            boxes = C.dense_cluster(seed)
+            if np.array_equal(O.ref_nms_rotated(boxes, thr), O.nms_rotated(boxes, thr, "det")):
+                break
+        m = min_margin(O.ref_boxes_iou_bev(boxes, boxes), thr)
+        out[f"nms_dense_{tag}_seed"], out[f"nms_dense_{tag}_margin"] = np.int64(seed), np.float64(m)
+        nms_case(f"dense_{tag}", boxes, thr, m)
+    bad, rows_bad = C.with_bad_rows()
+    out["nms_bad_rows_which"] = rows_bad
+    nms_case("bad_rows", bad, 0.2)
+    nms_case("identical_list", C.family_as_list("identical"), 0.5)
+    nms_case("tiny_heading_list", C.family_as_list("tiny_heading"), 0.5)
+    path = os.path.join(OUT, "iou_degenerate.npz")
+    np.savez_compressed(path, **out)
+    print(f"[golden] iou_degenerate: {os.path.getsize(path)} bytes")
+
+
 # --------------------------------------------------------------------------- decode fixture
 def ns(**k):
     return types.SimpleNamespace(**k)
@@ -613,7 +670,7 @@ def main():
     install_numba_identity()
     install_iou3d_nms()
     sys.path.insert(0, REF)
-    what = sys.argv[1:] or ["reader", "train", "iou", "decode", "decode_lazy", "loss", "voxel", "mvf", "merge", "ref_random"]
+    what = sys.argv[1:] or ["reader", "train", "iou", "decode", "decode_lazy", "loss", "voxel", "mvf", "merge", "ref_random", "degenerate"]
     if "reader" in what:
         gen_reader()
     if "train" in what:
@@ -634,6 +691,8 @@ def main():
         gen_merge()
     if "ref_random" in what:
         gen_ref_random()
+    if "degenerate" in what:
+        gen_degenerate()
 
 
 if __name__ == "__main__":

@@ -112,6 +112,23 @@ def boxes_aligned_iou3d(a, b, math="libm"):
     return out
 
 
+def overlap_vertex_count(a, b):
+    """Vertices the reference's polygon collects per aligned pair (edge crossings + contained corners), deterministic math."""
+    a, b = _boxes(a), _boxes(b)
+    out = np.zeros((a.shape[0],), np.int32)
+    lib().orc_overlap_vertex_count_det(_p(a, _f32p), _p(b, _f32p), ctypes.c_int64(a.shape[0]), _p(out, _i32p))
+    return out
+
+
+def detmath(a, b):
+    """pnx_detmath.h as the oracle's build sees it: sin(a), cos(a), atan2(a, b) element by element (fp32)."""
+    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
+    assert a.shape == b.shape
+    s, c, t = np.zeros_like(a), np.zeros_like(a), np.zeros_like(a)
+    lib().orc_detmath(_p(a, _f32p), _p(b, _f32p), ctypes.c_int64(a.size), _p(s, _f32p), _p(c, _f32p), _p(t, _f32p))
+    return s, c, t
+
+
 def nms_rotated(boxes, thresh, math="libm", return_mask=False):
     """boxes must already be score-sorted (descending). Returns kept indices (int64)."""
     boxes = _boxes(boxes)

@@ -73,6 +73,39 @@ static inline void orc_sincos_libm(float a, float* s, float* c) {
 #undef ORC_SINCOS
 #undef ORC_ATAN2
 
+/* pnx_detmath.h itself, element by element, as this build sees it (tests/test_detmath_cpu.py: the library's host build must agree bit for bit). */
+void orc_detmath(const float* a, const float* b, int64_t n, float* sin_a, float* cos_a, float* atan2_ab) {
+  for (int64_t i = 0; i < n; i++) {
+    pnx_sincosf(a[i], sin_a + i, cos_a + i);
+    atan2_ab[i] = pnx_atan2f(a[i], b[i]);
+  }
+}
+
+/* Number of vertices the reference's polygon collects for a pair (cu:151-194): edge crossings + contained corners, deterministic math. */
+void orc_overlap_vertex_count_det(const float* a, const float* b, int64_t n, int32_t* out) {
+  for (int64_t p = 0; p < n; p++) {
+    const float *box_a = a + p * 7, *box_b = b + p * 7;
+    orc_pt A[5], B[5], ca = {box_a[0], box_a[1]}, cb = {box_b[0], box_b[1]}, tmp;
+    const float hx[4] = {-1, 1, 1, -1}, hy[4] = {-1, -1, 1, 1};
+    float as, ac, bs, bc;
+    pnx_sincosf(box_a[6], &as, &ac);
+    pnx_sincosf(box_b[6], &bs, &bc);
+    for (int k = 0; k < 4; k++) {
+      orc_pt pa = {box_a[0] + hx[k] * (box_a[3] / 2), box_a[1] + hy[k] * (box_a[4] / 2)};
+      orc_pt pb = {box_b[0] + hx[k] * (box_b[3] / 2), box_b[1] + hy[k] * (box_b[4] / 2)};
+      A[k] = rot_about_det(ca, ac, as, pa);
+      B[k] = rot_about_det(cb, bc, bs, pb);
+    }
+    A[4] = A[0];
+    B[4] = B[0];
+    int cnt = 0;
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) cnt += seg_isect_det(A[i + 1], A[i], B[j + 1], B[j], &tmp);
+    for (int k = 0; k < 4; k++) cnt += in_box2d_det(box_a, B[k]) + in_box2d_det(box_b, A[k]);
+    out[p] = cnt;
+  }
+}
+
 /* Axis-aligned IoU (iou_normal cu:327-338) and its NMS (nms_normal_kernel cu:341-385). */
 static float orc_iou_normal1(const float* a, const float* b) {
   float left = fmaxf(a[0] - a[3] / 2, b[0] - b[3] / 2), right = fminf(a[0] + a[3] / 2, b[0] + b[3] / 2);

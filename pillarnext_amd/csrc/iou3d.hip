@@ -20,7 +20,18 @@
 #define PNX_GEOM __device__ __forceinline__
 #include "iou3d_geom.h"
 
+void pnx_detmath_host(const float* a, const float* b, int64_t n, float* sin_a, float* cos_a, float* atan2_ab);  // iou3d_host.cpp
+
 namespace {
+
+// pnx_debug_detmath: pnx_detmath.h as the kernels of this file see it, element by element
+__global__ __launch_bounds__(256) void k_detmath(const float* __restrict__ a, const float* __restrict__ b, int64_t n, float* __restrict__ sin_a,
+                                                 float* __restrict__ cos_a, float* __restrict__ atan2_ab) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  pnx_sincosf(a[i], sin_a + i, cos_a + i);
+  atan2_ab[i] = pnx_atan2f(a[i], b[i]);
+}
 
 // ---- N x M pairs (boxes_overlap_kernel cu:236-249, boxes_iou_bev_kernel cu:264-278) and aligned pairs
 enum { MODE_OVERLAP = 0, MODE_IOU = 1, MODE_IOU3D = 2 };
@@ -470,6 +481,20 @@ int32_t pnx_debug_nms_pair_cap(int32_t cap) {  // test hook: capacity of the rot
   const int prev = g_nms_pair_cap_dbg;
   g_nms_pair_cap_dbg = cap > 0 ? cap : 0;
   return prev;
+}
+
+int pnx_debug_detmath(const float* a, const float* b, int64_t n, float* sin_a, float* cos_a, float* atan2_ab, int32_t on_device, pnx_stream_t s) {
+  PNX_REQUIRE(n >= 0, PNX_ERR_INVALID, "negative size");
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(a && b && sin_a && cos_a && atan2_ab, PNX_ERR_INVALID, "null pointer");
+  if (!on_device) {
+    pnx_detmath_host(a, b, n, sin_a, cos_a, atan2_ab);
+    return PNX_OK;
+  }
+  PNX_REQUIRE(n < ((int64_t)1 << 31) * 256, PNX_ERR_UNSUPPORTED, "too many elements");
+  k_detmath<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)s>>>(a, b, n, sin_a, cos_a, atan2_ab);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
 }
 
 size_t pnx_nms_workspace_bytes(int64_t total_boxes, int32_t num_segments, int32_t max_seg_len) {

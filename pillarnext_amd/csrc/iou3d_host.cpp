@@ -26,6 +26,14 @@ void rows_iou(const float* a, int64_t r0, int64_t r1, const float* b, int64_t m,
 
 }  // namespace
 
+// the host half of pnx_debug_detmath (iou3d.hip): pnx_detmath.h as the twins of this file see it
+void pnx_detmath_host(const float* a, const float* b, int64_t n, float* sin_a, float* cos_a, float* atan2_ab) {
+  for (int64_t i = 0; i < n; i++) {
+    pnx_sincosf(a[i], sin_a + i, cos_a + i);
+    atan2_ab[i] = pnx_atan2f(a[i], b[i]);
+  }
+}
+
 extern "C" int pnx_boxes_iou_bev_cpu(const float* boxes_a_host, int64_t n, const float* boxes_b_host, int64_t m, float* out_host) {
   PNX_REQUIRE(n >= 0 && m >= 0, PNX_ERR_INVALID, "negative sizes");
   if (n == 0 || m == 0) return PNX_OK;

@@ -7,8 +7,15 @@
 // fp64 + - * / and floor, in a fixed order, so the HIP device code and any host build produce
 // bit-identical fp32 results (both sides must be compiled with -ffp-contract=off).
 //
-// Accuracy: results are the fp64 value (abs err < 1e-15) rounded once to fp32, i.e. correctly
-// rounded except on ~1e-8 of inputs.  Arguments with |a| >= 1e9 (or non-finite) give NaN.
+// Accuracy: results are the fp64 value (abs err < 1e-15) rounded once to fp32, for every
+// |a| < 1e9 (sin, cos) and every pair (atan2).  Rounding twice can miss the correctly rounded
+// fp32 value only where the exact value lies within ~1e-8 ulp of a rounding boundary: an
+// ESTIMATE (~1e-8 of inputs), not a measurement.  What is measured: tests/test_detmath_cpu.py
+// holds both routines to the correctly rounded value on all 38 665 cases of
+// tests/golden/detmath_cases.npz (tools/gen_detmath_golden.py), without exception, with this limit.
+// Arguments with |a| >= 1e9 (or non-finite) give NaN.
+// Zeros: sin(+-0) = +-0 (the argument itself, as libm does), cos(+-0) = 1; atan2's signed-zero,
+// inf and NaN cases are IEEE atan2's.
 #ifndef PNX_DETMATH_H
 #define PNX_DETMATH_H
 
@@ -18,8 +25,12 @@
 
 PNX_HD double pnx_dm_floor(double x) { return __builtin_floor(x); }
 
-// sin and cos of a (radians).  Cody-Waite 3-term reduction by pi/2 (33+33+53 bits), then the
-// classic degree-13 / degree-14 minimax kernels on [-pi/4, pi/4].
+// sin and cos of a (radians).  Cody-Waite reduction by pi/2, then the classic degree-13 /
+// degree-14 minimax kernels on [-pi/4, pi/4].  The reduction needs every product k * C_i but the
+// last to be exact: three terms of 33+33+53 bits while |k| <= 2^20 (|a| < ~1.6e6), four terms of
+// 23+23+23+53 bits beyond (|k| < 2^30 for |a| < 1e9).  With the three terms alone, on the
+// fixture's arguments, 9 % of the results in [5e6, 1e8) and 62 % of those in [1e8, 1e9) were not
+// correctly rounded (none below 5e6).
 PNX_HD void pnx_sincosf(float a, float* s_out, float* c_out) {
   double x = (double)a;
   double ax = x < 0.0 ? -x : x;
@@ -29,11 +40,24 @@ PNX_HD void pnx_sincosf(float a, float* s_out, float* c_out) {
     *c_out = qnan;
     return;
   }
+  if (x == 0.0) {  // sin keeps the zero's sign: it can reach atan2(+-0, x < 0) = +-pi and reorder a polygon's vertices
+    *s_out = a;
+    *c_out = 1.0f;
+    return;
+  }
   double t = x * 0.63661977236758134308;  // 2/pi
   double k = pnx_dm_floor(t + 0.5);
-  double r = x - k * 1.57079632673412561417e+00;
-  r = r - k * 6.07710050630396597660e-11;
-  r = r - k * 2.02226624879595063154e-21;
+  double r;
+  if (k >= -1048576.0 && k <= 1048576.0) {
+    r = x - k * 1.57079632673412561417e+00;
+    r = r - k * 6.07710050630396597660e-11;
+    r = r - k * 2.02226624879595063154e-21;
+  } else {  // x - k*C1 and the next difference are exact (multiples of 2^-22 / 2^-46 below 2^9 / 2), the last two round at the size of r
+    r = x - k * 1.57079625129699707031e+00;  // 0x1.921fb4p+0
+    r = r - k * 7.54978941586159635335e-08;  // 0x1.4442dp-24
+    r = r - k * 5.39030252995776476554e-15;  // 0x1.846988p-48
+    r = r - k * 3.28200354287350047444e-22;  // 0x1.8cc51701b839ap-72
+  }
   long long q = (long long)k;
   double z = r * r;
   // sin kernel
