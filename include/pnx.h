@@ -705,6 +705,17 @@ size_t pnx_lazy_decode_bytes(void);
  *   (workspace = pnx_sp3_wgrad_workspace_bytes = P * T * cin * cout floats, at least 256 bytes) are added in index order by a second
  *   kernel.  No floating-point atomics: bit-identical run to run.
  * pnx_sp3_dense_backward: dfeat (n, channels)[row][c] = dout[b][c*D + z][y][x], the gradient of pnx_sp3_dense.
+ * Training in 16 bits (dtype = PNX_BF16 or PNX_F16; csrc/sparse3d_half_train.h): operands are padded 16-bit rows as below, results fp32.
+ * pnx_sp3_conv_h_f32: pnx_sp3_conv_h without shift, residual and ReLU whose y (n_out, cout) fp32, unpadded, receives the fp32 accumulators
+ *   unrounded.  A map entry < 0 or >= n_in contributes zero, a row no input reaches is exactly 0.0f, bit-identical run to run.  With the map
+ *   transposed (or, for a submanifold layer, the taps mirrored) and the weights packed the other way round it is the data gradient.
+ * pnx_sp3_wgrad_h: dw (cout, T, cin) fp32 = sum over output rows o of dy[o][co] * x[map[o][t]][ci], x (n_in, cin_pad) and dy (n_out, cout_pad)
+ *   in `dtype`, on v_mfma_f32_16x16x32 with fp32 accumulators; cin, cout <= 144, taps <= 27.  Rows are split statically: with tiles, mt, groups
+ *   and p0 as for pnx_sp3_wgrad, a workgroup owns R = clamp(round_up(ceil(n_out / p0), 32), 256, 4096) consecutive rows, which one wave per tap
+ *   accumulates in K steps of 32 rows, in step order (a chain of min(R, n_out) terms at most); the P = ceil(n_out / R) fp32 partials
+ *   (partials = pnx_sp3_wgrad_h_partials_bytes = P * T * cin * cout floats rounded up to a multiple of 256 bytes, at least 256; 0 for
+ *   shapes without a kernel) are added in index order by a second kernel.  No floating-point atomics: bit-identical run to run.  A map entry
+ *   < 0 or >= n_in contributes zero; n_out == 0 or n_in == 0 writes a zero dw.
  * Inference in 16 bits (dtype = PNX_BF16 or PNX_F16; csrc/sparse3d_half.h).  Rows are stored in that type with the channel count rounded up to
  * a multiple of 8 (cin_pad, cout_pad, channels_pad: anything else is PNX_ERR_INVALID), pad columns exactly zero, 16-byte aligned.
  * pnx_sp3_conv_h: pnx_sp3_conv on such rows: x (n_in, cin_pad), residual / y (n_out, cout_pad), the same map; v_mfma_f32_16x16x32 with fp32
@@ -742,6 +753,11 @@ int pnx_sp3_transpose_map(const int32_t* map, int64_t n_out, int32_t taps, int64
 size_t pnx_sp3_wgrad_workspace_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout);
 int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, int32_t cout, const int32_t* map, int64_t n_out, int32_t taps, float* dw,
                   void* workspace, size_t workspace_bytes, pnx_stream_t stream);
+int pnx_sp3_conv_h_f32(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const int32_t* map, int64_t n_out, int32_t taps, const void* w_packed,
+                       float* y, int32_t cout, int32_t dtype, pnx_stream_t stream);
+size_t pnx_sp3_wgrad_h_partials_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout);
+int pnx_sp3_wgrad_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const void* dy, int32_t cout, int32_t cout_pad, const int32_t* map,
+                    int64_t n_out, int32_t taps, float* dw, int32_t dtype, void* partials, size_t partials_bytes, pnx_stream_t stream);
 int pnx_sp3_dense_backward(const float* dout, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* dfeat,
                            pnx_stream_t stream);
 

@@ -171,6 +171,9 @@ PROTOTYPES = {
     "pnx_sp3_transpose_map": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
     "pnx_sp3_wgrad_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "pnx_sp3_wgrad": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pnx_sp3_conv_h_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "pnx_sp3_wgrad_h_partials_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "pnx_sp3_wgrad_h": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp]),
     "pnx_sp3_dense_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i3p, _vp, _vp]),
 }
 

@@ -10,6 +10,7 @@
 //   pnx_sp3_transpose_map   tmap (N_in, T): tmap[map[o][t]][t] = o, -1 elsewhere -- the data gradient is pnx_sp3_conv_train on dy, tmap and w^T
 //   pnx_sp3_wgrad           dw[co][t][ci] = sum_o dy[o][co] * x[map[o][t]][ci]: split-K gather-GEMM, fp32 partials added in a fixed order
 //   pnx_sp3_dense_backward  the gather that undoes pnx_sp3_dense
+//   pnx_sp3_conv_h_f32, pnx_sp3_wgrad_h   forward / data gradient and weight gradient on bf16 / fp16 operands, fp32 results (sparse3d_half_train.h)
 //
 // A site's key is ((b*D + z)*H + y)*W + x (64-bit), one bit of the bitmap; its rank (the row it occupies) is the number of set bits
 // below it: blk[word >> PNX_SCAN_SHIFT] + pre[word] + popc(bitmap[word] & below).  Ranks follow [b, z, y, x] lexicographic order, which
@@ -412,6 +413,8 @@ void sp3_wgrad_nt(int nt, dim3 grid, hipStream_t st, const float* x, int64_t n_i
   }
 }
 
+#include "sparse3d_half_train.h"  // the 16-bit training form: k_sp3_wgrad_h, its split and its partials buffer
+
 int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
   *ix = sp3_carve(index, g);
   return pnx_check_workspace(index, index_bytes, ix->bytes, "sparse3d index");
@@ -685,6 +688,68 @@ int pnx_sp3_wgrad(const float* x, int64_t n_in, int32_t cin, const float* dy, in
   }
   PNX_LAUNCH_CHECK();
   k_sp3_wgrad_sum<<<sp3_blocks(E), kBlock, 0, st>>>(part, (int)sp.P, E, dw);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+// the argument checks pnx_sp3_conv_h_f32 and pnx_sp3_wgrad_h share
+static int sp3_half_train_args(const char* name, int32_t dtype, int32_t cin, int32_t cin_pad, int32_t cout, int32_t cout_pad, int32_t taps, int64_t n_in,
+                               int64_t n_out) {
+  PNX_REQUIRE(dtype == PNX_BF16 || dtype == PNX_F16, PNX_ERR_UNSUPPORTED, "%s: dtype %d (PNX_BF16 or PNX_F16)", name, dtype);
+  PNX_REQUIRE(cin >= 1 && cin <= 144 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
+              "%s: %d -> %d channels over %d taps (channels 1..144, taps 1..27)", name, cin, cout, taps);
+  PNX_REQUIRE(cin_pad == ((cin + 7) & ~7) && cout_pad == ((cout + 7) & ~7), PNX_ERR_INVALID,
+              "%s: padded channel counts %d / %d for %d -> %d channels (each the count rounded up to a multiple of 8)", name, cin_pad, cout_pad, cin, cout);
+  PNX_REQUIRE(n_in >= 0 && n_in < ((int64_t)1 << 31) && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "%s: %lld -> %lld rows", name,
+              (long long)n_in, (long long)n_out);
+  return PNX_OK;
+}
+
+int pnx_sp3_conv_h_f32(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const int32_t* map, int64_t n_out, int32_t taps, const void* w_packed,
+                       float* y, int32_t cout, int32_t dtype, pnx_stream_t stream) {
+  const int cout_pad = (cout + 7) & ~7;
+  if (const int rc = sp3_half_train_args("pnx_sp3_conv_h_f32", dtype, cin, cin_pad, cout, cout_pad, taps, n_in, n_out); rc != PNX_OK) return rc;
+  if (n_out == 0) return PNX_OK;
+  PNX_REQUIRE(map && w_packed && y && (n_in == 0 || x), PNX_ERR_INVALID, "pnx_sp3_conv_h_f32: null pointer");
+  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed) & 15) == 0 && ((uintptr_t)y & 3) == 0, PNX_ERR_INVALID,
+              "pnx_sp3_conv_h_f32: x and w_packed must be 16-byte aligned, y 4-byte aligned");
+  const int cpc = cin_pad / 8, S = (taps * cpc + 3) / 4, nt = (cout + 15) / 16;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PNX_BF16)
+    sp3_conv_h_nt<PNX_BF16, true>(nt, st, x, n_in, cpc, map, n_out, taps, w_packed, S, nullptr, nullptr, 0, y, cout, cout_pad);
+  else
+    sp3_conv_h_nt<PNX_F16, true>(nt, st, x, n_in, cpc, map, n_out, taps, w_packed, S, nullptr, nullptr, 0, y, cout, cout_pad);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_sp3_wgrad_h_partials_bytes(int64_t n_out, int32_t taps, int32_t cin, int32_t cout) {
+  if (n_out < 0 || n_out >= ((int64_t)1 << 31) || taps < 1 || taps > 27 || cin < 1 || cin > 144 || cout < 1 || cout > 144) return 0;
+  return sp3_wgrad_h_carve(nullptr, n_out, taps, cin, cout).bytes;
+}
+
+int pnx_sp3_wgrad_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, const void* dy, int32_t cout, int32_t cout_pad, const int32_t* map,
+                    int64_t n_out, int32_t taps, float* dw, int32_t dtype, void* partials, size_t partials_bytes, pnx_stream_t stream) {
+  if (const int rc = sp3_half_train_args("pnx_sp3_wgrad_h", dtype, cin, cin_pad, cout, cout_pad, taps, n_in, n_out); rc != PNX_OK) return rc;
+  PNX_REQUIRE(dw != nullptr, PNX_ERR_INVALID, "pnx_sp3_wgrad_h: dw is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t E = (int64_t)cout * taps * cin;
+  if (n_out == 0 || n_in == 0) {
+    PNX_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)E * sizeof(float), st));
+    return PNX_OK;
+  }
+  PNX_REQUIRE(x && dy && map, PNX_ERR_INVALID, "pnx_sp3_wgrad_h: null pointer");
+  PNX_REQUIRE((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, PNX_ERR_INVALID, "pnx_sp3_wgrad_h: x and dy must be 16-byte aligned");
+  const Sp3WgradHWs ws = sp3_wgrad_h_carve(partials, n_out, taps, cin, cout);
+  PNX_CHECK_WORKSPACE(partials, partials_bytes, ws.bytes, "pnx_sp3_wgrad_h");
+  const dim3 grid((unsigned)ws.sp.P, (unsigned)ws.sp.groups);
+  const int nt = (cin + 15) / 16;
+  if (dtype == PNX_BF16)
+    sp3_wgrad_h_mt<PNX_BF16>(ws.sp.mt, nt, grid, st, x, n_in, cin, cin_pad / 8, dy, cout, cout_pad / 8, map, n_out, taps, ws.sp.R, ws.part);
+  else
+    sp3_wgrad_h_mt<PNX_F16>(ws.sp.mt, nt, grid, st, x, n_in, cin, cin_pad / 8, dy, cout, cout_pad / 8, map, n_out, taps, ws.sp.R, ws.part);
+  PNX_LAUNCH_CHECK();
+  k_sp3_wgrad_sum<<<sp3_blocks(E), kBlock, 0, st>>>(ws.part, (int)ws.sp.P, E, dw);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

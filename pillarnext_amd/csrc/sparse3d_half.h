@@ -40,7 +40,8 @@ constexpr int kSp3HalfUnroll = 4;          // K steps whose map entries and rows
 constexpr size_t kSp3HalfLdsMax = 65536;   // weights up to this size are staged in LDS (no opt-in needed)
 
 // x (n_in, 8 cpc), y / res (n_out, cout_pad), wf (S, NT, 64, 8) in the 16-bit type DT; S = ceil(T cpc / 4) K steps; ntiles = ceil(n_out / 64).
-template <int DT, int NT, bool LDS>
+// F32 (training, sparse3d_half_train.h): y is (n_out, cout) fp32 and receives the accumulators as they are -- no shift, residual, ReLU or rounding.
+template <int DT, int NT, bool LDS, bool F32 = false>
 __global__ __launch_bounds__(kBlock) void k_sp3_conv_h(const void* __restrict__ x_, int64_t n_in, int cpc, const int32_t* __restrict__ map, int64_t n_out, int T,
                                                        const void* __restrict__ wf_, int S, const float* __restrict__ shift, const void* __restrict__ res_,
                                                        int relu, void* __restrict__ y_, int cout, int cout_pad, int64_t ntiles) {
@@ -109,6 +110,13 @@ __global__ __launch_bounds__(kBlock) void k_sp3_conv_h(const void* __restrict__ 
       const int c0 = j * 16 + kk * 4;  // acc[j][i] = output row r, channel c0 + i
       if (c0 >= cout_pad) continue;    // cout_pad is a multiple of 8: a group of four is inside the padded row or outside it
       f32x4 v = acc[j];
+      if constexpr (F32) {
+        float* yf = static_cast<float*>(y_) + row * cout + c0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (c0 + i < cout) yf[i] = v[i];
+        continue;
+      }
 #pragma unroll
       for (int i = 0; i < 4; i++) v[i] += c0 + i < cout ? shift[c0 + i] : 0.f;
       if (res) {
@@ -152,7 +160,7 @@ inline int sp3_half_cus() {
   return n;
 }
 
-template <int DT, int NT>
+template <int DT, int NT, bool F32 = false>
 void sp3_conv_h_launch(hipStream_t st, const void* x, int64_t n_in, int cpc, const int32_t* map, int64_t n_out, int T, const void* wf, int S,
                        const float* shift, const void* res, int relu, void* y, int cout, int cout_pad) {
   const int64_t ntiles = (n_out + 63) / 64;
@@ -160,24 +168,24 @@ void sp3_conv_h_launch(hipStream_t st, const void* x, int64_t n_in, int cpc, con
   if (wbytes <= kSp3HalfLdsMax) {
     const int64_t per_cu = std::min<int64_t>(8, (160 * 1024) / (int64_t)wbytes);
     const int64_t nb = std::min<int64_t>(ntiles, per_cu * sp3_half_cus());
-    k_sp3_conv_h<DT, NT, true><<<(unsigned)nb, kBlock, wbytes, st>>>(x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad, ntiles);
+    k_sp3_conv_h<DT, NT, true, F32><<<(unsigned)nb, kBlock, wbytes, st>>>(x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad, ntiles);
   } else {
-    k_sp3_conv_h<DT, NT, false><<<(unsigned)ntiles, kBlock, 0, st>>>(x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad, ntiles);
+    k_sp3_conv_h<DT, NT, false, F32><<<(unsigned)ntiles, kBlock, 0, st>>>(x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad, ntiles);
   }
 }
 
-template <int DT>
+template <int DT, bool F32 = false>
 void sp3_conv_h_nt(int nt, hipStream_t st, const void* x, int64_t n_in, int cpc, const int32_t* map, int64_t n_out, int T, const void* wf, int S,
                    const float* shift, const void* res, int relu, void* y, int cout, int cout_pad) {
   switch (nt) {
-    case 1: sp3_conv_h_launch<DT, 1>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 2: sp3_conv_h_launch<DT, 2>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 3: sp3_conv_h_launch<DT, 3>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 4: sp3_conv_h_launch<DT, 4>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 5: sp3_conv_h_launch<DT, 5>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 6: sp3_conv_h_launch<DT, 6>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 7: sp3_conv_h_launch<DT, 7>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    case 8: sp3_conv_h_launch<DT, 8>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
-    default: sp3_conv_h_launch<DT, 9>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 1: sp3_conv_h_launch<DT, 1, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 2: sp3_conv_h_launch<DT, 2, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 3: sp3_conv_h_launch<DT, 3, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 4: sp3_conv_h_launch<DT, 4, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 5: sp3_conv_h_launch<DT, 5, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 6: sp3_conv_h_launch<DT, 6, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 7: sp3_conv_h_launch<DT, 7, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    case 8: sp3_conv_h_launch<DT, 8, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
+    default: sp3_conv_h_launch<DT, 9, F32>(st, x, n_in, cpc, map, n_out, T, wf, S, shift, res, relu, y, cout, cout_pad); break;
   }
 }

@@ -1261,6 +1261,59 @@ def sp3_dense_h(feat, coords, batch, grid, channels):
     return out
 
 
+# 16-bit training form (csrc/sparse3d_half_train.h): the same padded 16-bit operands, fp32 results
+def sp3_conv_h_f32(x, nbmap, w_packed, cin, cout):
+    """pnx_sp3_conv_h_f32: x (N_in, round_up(cin, 8)) bf16 / fp16 padded rows, nbmap (N_out, T) int32, w_packed from sp3_pack_weight_h in x's dtype
+    -> (N_out, cout) fp32, the accumulators of the 16-bit gather-GEMM as they are (no shift, residual, ReLU or rounding)."""
+    for t, name in ((x, "x"), (nbmap, "nbmap"), (w_packed, "w_packed")):
+        _need_cuda(t, name)
+    dt = _sp3_half(x.dtype, "sp3_conv_h_f32")
+    if w_packed.dtype != x.dtype or nbmap.dtype != torch.int32 or x.dim() != 2 or nbmap.dim() != 2:
+        raise PnxError("sp3_conv_h_f32: features and weights of one 16-bit dtype, int32 map")
+    if not (x.is_contiguous() and nbmap.is_contiguous() and w_packed.is_contiguous()):
+        raise PnxError("sp3_conv_h_f32: every operand must be contiguous")
+    n_out, T = nbmap.shape
+    ci, co = int(cin), int(cout)
+    if x.shape[1] != _cpad(ci):
+        raise PnxError(f"sp3_conv_h_f32: rows of {x.shape[1]} columns for {ci} channels (padded rows have {_cpad(ci)})")
+    n = lib().pnx_sp3_packed_weight_halfs(T, ci, co)
+    if n == 0 or w_packed.numel() != n:
+        raise PnxError(f"sp3_conv_h_f32: packed weight {tuple(w_packed.shape)} does not fit {T} taps x {ci} -> {co}")
+    y = torch.empty((n_out, co), dtype=torch.float32, device=x.device)
+    check(lib().pnx_sp3_conv_h_f32(ptr(x), x.shape[0], ci, x.shape[1], ptr(nbmap), n_out, T, ptr(w_packed), ptr(y), co, dt, stream_ptr()),
+          "pnx_sp3_conv_h_f32")
+    return y
+
+
+def sp3_wgrad_h_partials_bytes(n_out, taps, cin, cout):
+    n = lib().pnx_sp3_wgrad_h_partials_bytes(int(n_out), int(taps), int(cin), int(cout))
+    if n == 0:
+        raise PnxError(f"sp3_wgrad_h: no kernel for {cin} -> {cout} channels over {taps} taps and {n_out} rows")
+    return n
+
+
+def sp3_wgrad_h(x, nbmap, dy, cin, cout):
+    """pnx_sp3_wgrad_h: x (N_in, round_up(cin, 8)) and dy (N_out, round_up(cout, 8)) padded rows of one 16-bit dtype, nbmap (N_out, T) int32
+    -> dw (cout, T, cin) fp32."""
+    for t, name in ((x, "x"), (nbmap, "nbmap"), (dy, "dy")):
+        _need_cuda(t, name)
+    dt = _sp3_half(x.dtype, "sp3_wgrad_h")
+    if dy.dtype != x.dtype or nbmap.dtype != torch.int32 or x.dim() != 2 or dy.dim() != 2 or nbmap.dim() != 2:
+        raise PnxError("sp3_wgrad_h: (N, C) features and gradients of one 16-bit dtype, int32 map")
+    if dy.shape[0] != nbmap.shape[0] or not (x.is_contiguous() and dy.is_contiguous() and nbmap.is_contiguous()):
+        raise PnxError("sp3_wgrad_h: dy and nbmap must have one row per output site, and every operand must be contiguous")
+    n_out, T = nbmap.shape
+    ci, co = int(cin), int(cout)
+    if x.shape[1] != _cpad(ci) or dy.shape[1] != _cpad(co):
+        raise PnxError(f"sp3_wgrad_h: rows of {x.shape[1]} / {dy.shape[1]} columns for {ci} -> {co} channels (padded rows have {_cpad(ci)} / {_cpad(co)})")
+    nbytes = sp3_wgrad_h_partials_bytes(n_out, T, ci, co)
+    part = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)  # call-lifetime scratch
+    dw = torch.empty((co, T, ci), dtype=torch.float32, device=x.device)
+    check(lib().pnx_sp3_wgrad_h(ptr(x), x.shape[0], ci, x.shape[1], ptr(dy), co, dy.shape[1], ptr(nbmap), n_out, T, ptr(dw), dt, ptr(part), nbytes,
+                                stream_ptr()), "pnx_sp3_wgrad_h")
+    return dw
+
+
 # --------------------------------------------------------------------------------------------- label assignment
 _ASSIGN_OUT = (("hm", torch.float32), ("anno_box", torch.float32), ("ind", torch.int64), ("mask", torch.uint8), ("cat", torch.int64),
                ("gt_boxes", torch.float32))

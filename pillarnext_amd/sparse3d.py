@@ -19,6 +19,10 @@ and neighbour maps, which forward and backward share.
 use_half_precision(dtype) moves the folded eval path onto bf16 / fp16 rows and the 16-bit matrix cores (pnx_sp3_conv_h): the fp32 input features
 are rounded once, every layer reads and writes padded 16-bit rows over the same index, output sets and neighbour maps, and the dense output
 stays fp32.  The default, training and any call that wants gradients are untouched.
+
+use_half_precision(dtype, training=True) also moves the autograd path's convolutions onto the 16-bit matrix cores (SparseConvHalfFunction:
+pnx_sp3_conv_h_f32 for y and dx, pnx_sp3_wgrad_h for dw): the node's boundary stays fp32, its operands are rounded once, BatchNorm, residual
+and ReLU remain the module's fp32 torch ops.
 """
 import math
 
@@ -126,6 +130,52 @@ class SparseConvFunction(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
+class SparseConvHalfFunction(torch.autograd.Function):
+    """SparseConvFunction on the 16-bit matrix cores.  The boundary is fp32 (x, weight, y, dy, dx, dw); inside, every operand is rounded once to
+    `dtype` (nearest even) into padded rows and products are accumulated in fp32: y = the accumulators of pnx_sp3_conv_h_f32 on rows_h(x) and the
+    packed weight `wp`; dx = the same kernel on rows_h(dy) and the weights packed the other way round (own map and mirrored taps for a
+    submanifold layer, the transposed map otherwise); dw = pnx_sp3_wgrad_h on the saved rows_h(x) and rows_h(dy).  The node saves the 16-bit
+    rows, half of what SparseConvFunction keeps -- which does not lower a step's peak memory while the fp32 rows stay alive in the BatchNorm /
+    ReLU that produced them.
+    torch.float16: gradients below fp16's range (6e-8) underflow to zero when dy is rounded -- scale the loss (torch.amp.GradScaler); bf16
+    keeps fp32's range."""
+
+    @staticmethod
+    def forward(ctx, x, weight, nbmap, subm, tick, dtype, wp):
+        w = weight.detach()
+        cout, cin = w.shape[0], w.shape[-1]
+        xh = ops.sp3_rows_h(x, dtype)
+        y = ops.sp3_conv_h_f32(xh, nbmap, wp, cin, cout)
+        ctx.save_for_backward(xh, w, nbmap)
+        ctx.subm, ctx.tick, ctx.dtype = subm, tick, dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xh, w, nbmap = ctx.saved_tensors
+        cout, cin = w.shape[0], w.shape[-1]
+        dx = dw = None
+        ctx.tick("bwd")
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dyh = ops.sp3_rows_h(dy.contiguous(), ctx.dtype)  # rounded once, serves both gradients
+        if ctx.needs_input_grad[0]:
+            dx = sparse_conv_dgrad_h(dyh, w, nbmap, xh.shape[0], ctx.subm)
+            ctx.tick("dgrad")
+        if ctx.needs_input_grad[1]:
+            dw = ops.sp3_wgrad_h(xh, nbmap, dyh, cin, cout).view(w.shape)
+            ctx.tick("wgrad")
+        return dx, dw, None, None, None, None, None
+
+
+def sparse_conv_dgrad_h(dyh, weight, nbmap, n_in, subm):
+    """sparse_conv_dgrad on the 16-bit matrix cores: dyh (n_out, round_up(Cout, 8)) padded 16-bit rows -> dx (n_in, Cin) fp32.  The weights are
+    packed the other way round (w.permute(4, 1, 2, 3, 0)) by the forward's own packing; subm: own map, taps mirrored."""
+    cout, cin = weight.shape[0], weight.shape[-1]
+    wt = weight.permute(4, 1, 2, 3, 0)
+    tmap = nbmap if subm else ops.sp3_transpose_map(nbmap, n_in)
+    return ops.sp3_conv_h_f32(dyh, tmap, ops.sp3_pack_weight_h(wt.flip(1, 2, 3) if subm else wt, dyh.dtype), cout, cin)
+
+
 class SparseDenseFunction(torch.autograd.Function):
     """ops.sp3_dense with its gradient, the gather back into rows."""
 
@@ -169,17 +219,26 @@ class SparseResNet3D(nn.Module):
         self.extra_conv = nn.Sequential(SparseConv3d(c, c, (3, 1, 1), (2, 1, 1), 0), nn.BatchNorm1d(c, eps=1e-3, momentum=0.01), nn.ReLU())
         self.profile = None  # a list: every phase of the next forwards appends (name, end event) -- tools/bench_voxel18.py
         self.half_dtype = None  # None: fp32; torch.bfloat16 / float16: the folded eval path runs in 16 bits (use_half_precision)
+        self.half_train_dtype = None  # None: fp32; torch.bfloat16 / float16: the autograd path's convolutions run in 16 bits
 
-    def use_half_precision(self, dtype=torch.bfloat16):
+    def use_half_precision(self, dtype=torch.bfloat16, training=False):
         """Inference on 16-bit rows and the 16-bit matrix cores (pnx_sp3_conv_h), as MVFFeatureNet.use_hip_convs is for the view nets: eval-mode
         forwards that want no gradient round the fp32 input features once, run every layer in `dtype` (fp32 accumulation, BN shift, residual and
         ReLU in fp32, one rounding per layer) and return the fp32 dense map; forward_sparse then returns its features in `dtype`.  Training and any
         call that wants gradients keep the fp32 autograd path.  dtype=None switches back to fp32.
         torch.float16 has 5 exponent bits: activations above 65504 become inf, which real checkpoints can reach -- bf16, the default, keeps fp32's
-        range at 8 bits of precision."""
+        range at 8 bits of precision.
+        training=True: the autograd path (training mode, or any call that wants gradients) runs its convolutions on the 16-bit matrix cores
+        as well (SparseConvHalfFunction): fp32 at every node's boundary, operands rounded once to `dtype`, fp32 accumulation; BatchNorm1d,
+        residual and ReLU stay fp32 torch ops and forward_sparse still returns fp32 features there.  training=False leaves (or puts back)
+        the autograd path in fp32.  Under torch.float16 gradients below its range underflow when dy is rounded: scale the loss
+        (torch.amp.GradScaler); bf16, the default, needs none."""
         if dtype is not None and dtype not in ops._HALF:
             raise PnxError("use_half_precision: torch.bfloat16, torch.float16 or None")
+        if training and dtype is None:
+            raise PnxError("use_half_precision: training=True needs torch.bfloat16 or torch.float16 (dtype=None switches both paths back to fp32)")
         self.half_dtype = dtype
+        self.half_train_dtype = dtype if training else None
         return self
 
     # ------------------------------------------------------------------------------------------ plan
@@ -197,6 +256,17 @@ class SparseResNet3D(nn.Module):
             layers["extra_conv"] = _fold(self.extra_conv[0], self.extra_conv[1], dtype)
             layers["mapping"] = _fold(self.mapping.conv, self.mapping.norm, dtype)
             f = cache[dtype] = (_params_version(self), layers)
+        return f[1]
+
+    def _train_packed(self, dtype):
+        """The 16-bit training path's forward weights in fragment order, packed once per version of the convolution weights and element type
+        (the BatchNorm buffers, which every training forward moves, do not count)."""
+        cache = self.__dict__.setdefault("_train_packed_cache", {})  # dtype -> (weight versions, {conv module: packed weight})
+        convs = [m for m in self.modules() if isinstance(m, SparseConv3d)]
+        version = tuple((c.weight.data_ptr(), c.weight._version) for c in convs)
+        f = cache.get(dtype)
+        if f is None or f[0] != version:
+            f = cache[dtype] = (version, {c: ops.sp3_pack_weight_h(c.weight.detach(), dtype) for c in convs})
         return f[1]
 
     def _tick(self, name):
@@ -243,7 +313,14 @@ class SparseResNet3D(nn.Module):
     def _conv(self, x, m, conv, norm, folded, name, residual=None):
         """One layer.  folded: the plan of packed weights and shifts (eval), or None: conv -> BatchNorm1d -> (+ residual) -> ReLU under autograd."""
         if folded is None:
-            y = SparseConvFunction.apply(x, conv.weight, m, conv.subm, lambda phase: self._tick(f"{name}.{phase}"))
+            def tick(phase):
+                self._tick(f"{name}.{phase}")
+
+            if self.half_train_dtype is None:
+                y = SparseConvFunction.apply(x, conv.weight, m, conv.subm, tick)
+            else:
+                y = SparseConvHalfFunction.apply(x.contiguous(), conv.weight, m, conv.subm, tick, self.half_train_dtype,
+                                                 self._train_packed(self.half_train_dtype)[conv])
             self._tick(name + ".conv")
             y = norm(y)
             y = torch.relu(y if residual is None else y + residual)

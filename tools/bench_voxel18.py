@@ -11,7 +11,11 @@ each prints its own per-layer table, and the convolution phases are compared by 
 --train times forward + backward of the backbone in training mode instead (loss = sum of the dense output x a fixed random tensor): ms per step,
 the split into forward convolutions / data gradients / weight gradients / everything else (index, maps, BatchNorm, ReLU, residual, dense: torch
 glue included) from HIP events, peak memory, the weight-gradient workspace per stage, and the same torch statement under autograd, alternating
-with the HIP step in one process (--torch-frames: fewer frames for the statement if it does not fit; its time is then also given per frame)."""
+with the HIP step in one process (--torch-frames: fewer frames for the statement if it does not fit; its time is then also given per frame).
+
+--train --dtype bf16 / fp16 times the training step under use_half_precision(dtype, training=True) against the fp32 training step instead of
+the torch statement: the two arms alternate step by step in one process and each reports the same phases with its spread (min .. max over the
+iterations), its wall time and the peak memory of one step of its own; the phases are compared by the A/B rule."""
 import argparse
 import collections
 import os
@@ -132,6 +136,8 @@ def train(a, reader, bb):
         ev, bb.profile = bb.profile, None
         return ev
 
+    if a.dtype != "fp32":
+        return train_arms(a, bb, hip_step, B)
     tb, tf_, tc, tg = (a.torch_frames or B), None, None, None
     if tb != B:
         _, tf_, tc, tg = _inputs(reader, tb)
@@ -181,12 +187,74 @@ def train(a, reader, bb):
     print(f"peak memory above inputs (both steps in the process): {peak / 2**30:.2f} GiB")
 
 
+def train_arms(a, bb, hip_step, B):
+    """fp32 and 16-bit training steps alternating in one process."""
+    arms = [("fp32", None), (a.dtype, HALF[a.dtype])]
+
+    def switch(dt):
+        if dt is None:
+            bb.use_half_precision(None)
+        else:
+            bb.use_half_precision(dt, training=True)
+
+    for _, dt in arms:  # warm-up
+        switch(dt)
+        hip_step(False), hip_step(False)
+    torch.cuda.synchronize()
+    keys = ("forward conv", "dgrad", "wgrad", "the rest", "step (events)")
+    runs = {n: {k: [] for k in keys} for n, _ in arms}
+    walls = {n: [] for n, _ in arms}
+    for _ in range(a.iters):  # the arms alternate: both see the same clocks and the same allocator state
+        for arm, dt in arms:
+            switch(dt)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev = hip_step(True)
+            torch.cuda.synchronize()
+            walls[arm].append((time.perf_counter() - t0) * 1e3)
+            per = collections.defaultdict(float)
+            for (_, e0), (name, e1) in zip(ev[:-1], ev[1:]):
+                per[name.rsplit(".", 1)[-1]] += e0.elapsed_time(e1)
+            total = sum(per.values())
+            for k, v in (("forward conv", per["conv"]), ("dgrad", per["dgrad"]), ("wgrad", per["wgrad"])):
+                runs[arm][k].append(v)
+            runs[arm]["the rest"].append(total - per["conv"] - per["dgrad"] - per["wgrad"])
+            runs[arm]["step (events)"].append(total)
+    peaks = {}
+    for arm, dt in arms:  # one step of each arm alone
+        switch(dt)
+        bb.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        hip_step(False)
+        torch.cuda.synchronize()
+        peaks[arm] = torch.cuda.max_memory_allocated() - base
+    bb.use_half_precision(None)
+    mean = {n: {k: sum(v) / len(v) for k, v in runs[n].items()} for n, _ in arms}
+    for arm, _ in arms:
+        w = sorted(walls[arm])
+        print(f"## arm {arm}: HIP step by phase (HIP events, mean of {a.iters} [min .. max]; the rest = index, maps, BatchNorm / ReLU / residual, dense, "
+              "autograd glue, 16-bit row conversions outside the gradients)")
+        for k in keys:
+            v = runs[arm][k]
+            print(f"  {k:14s} {mean[arm][k]:8.2f} ms  [{min(v):.2f} .. {max(v):.2f}]")
+        print(f"  forward + backward: {w[len(w) // 2]:.2f} ms per batch of {B} (median wall; min {w[0]:.2f}, max {w[-1]:.2f}), {w[len(w) // 2] / B:.2f} ms per frame; "
+              f"peak memory of one step above inputs {peaks[arm] / 2**30:.2f} GiB")
+    (n0, _), (n1, _) = arms
+    for k in keys:
+        spread = max(max(runs[n][k]) - min(runs[n][k]) for n in (n0, n1))
+        d = mean[n0][k] - mean[n1][k]
+        print(f"{k}: {n0} {mean[n0][k]:.2f} ms vs {n1} {mean[n1][k]:.2f} ms: difference {d:.2f} ms = {d / max(spread, 1e-9):.1f} x the larger spread "
+              f"({spread:.2f} ms; the A/B rule asks for more than 3 x), ratio {mean[n0][k] / max(mean[n1][k], 1e-9):.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32",
-                    help="bf16 / fp16: time SparseResNet3D.use_half_precision as well, its forwards alternating with the fp32 ones in this run")
+                    help="bf16 / fp16: time SparseResNet3D.use_half_precision as well, its forwards (--train: training steps) alternating with the fp32 ones in this run")
     ap.add_argument("--train", action="store_true", help="time forward + backward in training mode")
     ap.add_argument("--torch-frames", type=int, default=0, help="--train: frames of the torch statement (default: --frames)")
     a = ap.parse_args()
