@@ -716,6 +716,23 @@ size_t pnx_lazy_decode_bytes(void);
  *   (partials = pnx_sp3_wgrad_h_partials_bytes = P * T * cin * cout floats rounded up to a multiple of 256 bytes, at least 256; 0 for
  *   shapes without a kernel) are added in index order by a second kernel.  No floating-point atomics: bit-identical run to run.  A map entry
  *   < 0 or >= n_in contributes zero; n_out == 0 or n_in == 0 writes a zero dw.
+ * Train-mode BatchNorm1d + residual + ReLU over the rows (csrc/sparse3d_bn.h): y, out, gout, dy, dresidual are (n, channels) fp32 unpadded rows,
+ *   channels 1..256 (any value), n >= 0 (n == 0 launches nothing), every row pointer 16-byte aligned.  residual is NULL, fp32 (n, channels)
+ *   (residual_dtype PNX_F32) or padded 16-bit rows (n, round_up(channels, 8)) of residual_dtype PNX_BF16 / PNX_F16, pad columns zero.  The per-channel
+ *   arithmetic between the passes is pnx_masked_bn_reduce / _finalize / _bwd_finalize, which take any channel count <= 256.
+ * pnx_sp3_bn_split: split3_host = [blocks, rows_per_pass, passes] with cpc = ceil(channels / 8), rows_per_pass = 256 / cpc, tiles = ceil(n /
+ *   rows_per_pass), blocks = min(tiles, 1024), passes = ceil(tiles / blocks).  Workgroup b walks the tiles b, b + blocks, ...; a thread owns one
+ *   chunk of 8 channels of one row of each tile and adds its terms in walk order (<= passes terms), then one thread per channel adds the
+ *   rows_per_pass thread sums in row order: the longest fp32 chain of a partial is passes + rows_per_pass terms, each formed with at most 3
+ *   roundings.  No floating-point atomics: bit-identical run to run.
+ * pnx_sp3_bn_partials_bytes: blocks * (2 channels + 1) floats (backward: 2 channels), rounded up to a multiple of 256 bytes, at least 256; 0 for
+ *   arguments out of range.  The partials buffer follows the workspace contract.
+ * pnx_sp3_bn_stats: partials (blocks, 2 channels + 1) fp32 = per workgroup [sum d | sum d^2 | rows], d = y - center[c] (center NULL: 0).
+ * pnx_sp3_bn_apply: z = y * scale + shift (+ residual), out = relu ? max(z, 0) : z, each operation rounded to fp32 in that order; out_h (NULL, or
+ *   (n, round_up(channels, 8)) of `dtype`) = out rounded once to nearest even, pad columns exactly zero.  A 16-bit residual and out_h share one dtype.
+ * pnx_sp3_bn_bwd_stats: partials (blocks, 2 channels) = per workgroup [sum g | sum g xhat], g = relu ? gout * [z > 0] : gout with z recomputed by
+ *   the forward's own operations from y, scale, shift and the same residual; xhat = (y - mean) * invstd.
+ * pnx_sp3_bn_bwd_apply: dy = scale * (g - mean_g - xhat * mean_gx); dresidual (NULL or fp32 (n, channels)) = g.
  * Inference in 16 bits (dtype = PNX_BF16 or PNX_F16; csrc/sparse3d_half.h).  Rows are stored in that type with the channel count rounded up to
  * a multiple of 8 (cin_pad, cout_pad, channels_pad: anything else is PNX_ERR_INVALID), pad columns exactly zero, 16-byte aligned.
  * pnx_sp3_conv_h: pnx_sp3_conv on such rows: x (n_in, cin_pad), residual / y (n_out, cout_pad), the same map; v_mfma_f32_16x16x32 with fp32
@@ -760,6 +777,17 @@ int pnx_sp3_wgrad_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, c
                     int64_t n_out, int32_t taps, float* dw, int32_t dtype, void* partials, size_t partials_bytes, pnx_stream_t stream);
 int pnx_sp3_dense_backward(const float* dout, const int32_t* coords, int64_t n, int32_t channels, int32_t batch, const int32_t* grid3_host, float* dfeat,
                            pnx_stream_t stream);
+int pnx_sp3_bn_split(int64_t n, int32_t channels, int32_t* split3_host);
+size_t pnx_sp3_bn_partials_bytes(int64_t n, int32_t channels, int32_t backward);
+int pnx_sp3_bn_stats(const float* y, int64_t n, int32_t channels, const float* center, float* partials, size_t partials_bytes, pnx_stream_t stream);
+int pnx_sp3_bn_apply(const float* y, int64_t n, int32_t channels, const float* scale, const float* shift, const void* residual, int32_t residual_dtype,
+                     int32_t relu, float* out, void* out_h, int32_t dtype, pnx_stream_t stream);
+int pnx_sp3_bn_bwd_stats(const float* gout, const float* y, const void* residual, int32_t residual_dtype, int64_t n, int32_t channels, const float* scale,
+                         const float* shift, const float* mean, const float* invstd, int32_t relu, float* partials, size_t partials_bytes,
+                         pnx_stream_t stream);
+int pnx_sp3_bn_bwd_apply(const float* gout, const float* y, const void* residual, int32_t residual_dtype, int64_t n, int32_t channels, const float* scale,
+                         const float* shift, const float* mean, const float* invstd, int32_t relu, const float* mean_g, const float* mean_gx, float* dy,
+                         float* dresidual, pnx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------
  * GT-database paste and the four global augmentations (csrc/augment.hip): det3d/datasets/base.py:72-99 of the reference, i.e.

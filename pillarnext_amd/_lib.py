@@ -175,6 +175,12 @@ PROTOTYPES = {
     "pnx_sp3_wgrad_h_partials_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "pnx_sp3_wgrad_h": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp]),
     "pnx_sp3_dense_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i3p, _vp, _vp]),
+    "pnx_sp3_bn_split": (ctypes.c_int, [_i64, _i32, _i3p]),
+    "pnx_sp3_bn_partials_bytes": (_sz, [_i64, _i32, _i32]),
+    "pnx_sp3_bn_stats": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pnx_sp3_bn_apply": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "pnx_sp3_bn_bwd_stats": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "pnx_sp3_bn_bwd_apply": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -11,6 +11,7 @@
 //   pnx_sp3_wgrad           dw[co][t][ci] = sum_o dy[o][co] * x[map[o][t]][ci]: split-K gather-GEMM, fp32 partials added in a fixed order
 //   pnx_sp3_dense_backward  the gather that undoes pnx_sp3_dense
 //   pnx_sp3_conv_h_f32, pnx_sp3_wgrad_h   forward / data gradient and weight gradient on bf16 / fp16 operands, fp32 results (sparse3d_half_train.h)
+//   pnx_sp3_bn_stats, _apply, _bwd_stats, _bwd_apply   train-mode BatchNorm1d + residual + ReLU over the rows, forward and backward (sparse3d_bn.h)
 //
 // A site's key is ((b*D + z)*H + y)*W + x (64-bit), one bit of the bitmap; its rank (the row it occupies) is the number of set bits
 // below it: blk[word >> PNX_SCAN_SHIFT] + pre[word] + popc(bitmap[word] & below).  Ranks follow [b, z, y, x] lexicographic order, which
@@ -414,6 +415,7 @@ void sp3_wgrad_nt(int nt, dim3 grid, hipStream_t st, const float* x, int64_t n_i
 }
 
 #include "sparse3d_half_train.h"  // the 16-bit training form: k_sp3_wgrad_h, its split and its partials buffer
+#include "sparse3d_bn.h"          // train-mode BatchNorm + residual + ReLU over the rows: k_sp3_bn_*, their split and their partials buffer
 
 int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
   *ix = sp3_carve(index, g);
@@ -750,6 +752,107 @@ int pnx_sp3_wgrad_h(const void* x, int64_t n_in, int32_t cin, int32_t cin_pad, c
     sp3_wgrad_h_mt<PNX_F16>(ws.sp.mt, nt, grid, st, x, n_in, cin, cin_pad / 8, dy, cout, cout_pad / 8, map, n_out, taps, ws.sp.R, ws.part);
   PNX_LAUNCH_CHECK();
   k_sp3_wgrad_sum<<<sp3_blocks(E), kBlock, 0, st>>>(ws.part, (int)ws.sp.P, E, dw);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+// the argument checks the four pnx_sp3_bn_* passes share; *dt = the 16-bit type in play (PNX_F32: none)
+static int sp3_bn_args(const char* name, int64_t n, int32_t channels, const void* residual, int32_t residual_dtype, const void* out_h, int32_t dtype,
+                       int32_t* dt) {
+  PNX_REQUIRE(channels >= 1 && channels <= 256, PNX_ERR_UNSUPPORTED, "%s: %d channels (1..256)", name, channels);
+  PNX_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), PNX_ERR_INVALID, "%s: %lld rows", name, (long long)n);
+  const bool res_h = residual != nullptr && residual_dtype != PNX_F32;
+  PNX_REQUIRE(residual == nullptr || residual_dtype == PNX_F32 || residual_dtype == PNX_BF16 || residual_dtype == PNX_F16, PNX_ERR_UNSUPPORTED,
+              "%s: residual dtype %d (PNX_F32, PNX_BF16 or PNX_F16)", name, residual_dtype);
+  PNX_REQUIRE(out_h == nullptr || dtype == PNX_BF16 || dtype == PNX_F16, PNX_ERR_UNSUPPORTED, "%s: out_h dtype %d (PNX_BF16 or PNX_F16)", name, dtype);
+  PNX_REQUIRE(!(res_h && out_h != nullptr) || residual_dtype == dtype, PNX_ERR_INVALID, "%s: 16-bit residual and out_h must have one dtype", name);
+  PNX_REQUIRE(((uintptr_t)residual & 15) == 0 && ((uintptr_t)out_h & 15) == 0, PNX_ERR_INVALID, "%s: rows must be 16-byte aligned", name);
+  *dt = res_h ? residual_dtype : (out_h != nullptr ? dtype : PNX_F32);
+  return PNX_OK;
+}
+
+int pnx_sp3_bn_split(int64_t n, int32_t channels, int32_t* split3_host) {
+  PNX_REQUIRE(split3_host && channels >= 1 && channels <= 256 && n >= 0 && n < ((int64_t)1 << 31), PNX_ERR_INVALID,
+              "pnx_sp3_bn_split: %lld rows of %d channels (rows < 2^31, channels 1..256)", (long long)n, channels);
+  const Sp3BnSplit s = sp3_bn_split(n, channels);
+  split3_host[0] = s.blocks, split3_host[1] = s.rpp, split3_host[2] = (int32_t)s.passes;
+  return PNX_OK;
+}
+
+size_t pnx_sp3_bn_partials_bytes(int64_t n, int32_t channels, int32_t backward) {
+  if (n < 0 || n >= ((int64_t)1 << 31) || channels < 1 || channels > 256) return 0;
+  return sp3_bn_carve(nullptr, n, channels, backward != 0).bytes;
+}
+
+int pnx_sp3_bn_stats(const float* y, int64_t n, int32_t channels, const float* center, float* partials, size_t partials_bytes, pnx_stream_t stream) {
+  int32_t dt;
+  if (const int rc = sp3_bn_args("pnx_sp3_bn_stats", n, channels, nullptr, PNX_F32, nullptr, PNX_F32, &dt); rc != PNX_OK) return rc;
+  const Sp3BnWs ws = sp3_bn_carve(partials, n, channels, false);
+  PNX_CHECK_WORKSPACE(partials, partials_bytes, ws.bytes, "pnx_sp3_bn_stats");
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(y && ((uintptr_t)y & 15) == 0, PNX_ERR_INVALID, "pnx_sp3_bn_stats: y is NULL or not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+#define GO(V, DT) k_sp3_bn_stats<V><<<(unsigned)ws.sp.blocks, kBlock, 0, st>>>(y, n, channels, ws.sp.rpp, center, ws.part)
+  SP3_BN_DISPATCH(channels, PNX_F32, GO);
+#undef GO
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_bn_apply(const float* y, int64_t n, int32_t channels, const float* scale, const float* shift, const void* residual, int32_t residual_dtype,
+                     int32_t relu, float* out, void* out_h, int32_t dtype, pnx_stream_t stream) {
+  int32_t dt;
+  if (const int rc = sp3_bn_args("pnx_sp3_bn_apply", n, channels, residual, residual_dtype, out_h, dtype, &dt); rc != PNX_OK) return rc;
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(y && scale && shift && out && (((uintptr_t)y | (uintptr_t)out) & 15) == 0, PNX_ERR_INVALID,
+              "pnx_sp3_bn_apply: null pointer, or rows not 16-byte aligned");
+  const Sp3BnSplit sp = sp3_bn_split(n, channels);
+  const Sp3BnRes res = {residual_dtype == PNX_F32 ? (const float*)residual : nullptr, residual_dtype == PNX_F32 ? nullptr : residual};
+  hipStream_t st = (hipStream_t)stream;
+#define GO(V, DT) k_sp3_bn_apply<V, DT><<<(unsigned)sp.blocks, kBlock, 0, st>>>(y, n, channels, sp.rpp, scale, shift, res, relu, out, out_h)
+  SP3_BN_DISPATCH(channels, dt, GO);
+#undef GO
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_bn_bwd_stats(const float* gout, const float* y, const void* residual, int32_t residual_dtype, int64_t n, int32_t channels, const float* scale,
+                         const float* shift, const float* mean, const float* invstd, int32_t relu, float* partials, size_t partials_bytes,
+                         pnx_stream_t stream) {
+  int32_t dt;
+  if (const int rc = sp3_bn_args("pnx_sp3_bn_bwd_stats", n, channels, residual, residual_dtype, nullptr, PNX_F32, &dt); rc != PNX_OK) return rc;
+  const Sp3BnWs ws = sp3_bn_carve(partials, n, channels, true);
+  PNX_CHECK_WORKSPACE(partials, partials_bytes, ws.bytes, "pnx_sp3_bn_bwd_stats");
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(gout && y && scale && shift && mean && invstd && (((uintptr_t)y | (uintptr_t)gout) & 15) == 0, PNX_ERR_INVALID,
+              "pnx_sp3_bn_bwd_stats: null pointer, or rows not 16-byte aligned");
+  const Sp3BnRes res = {residual_dtype == PNX_F32 ? (const float*)residual : nullptr, residual_dtype == PNX_F32 ? nullptr : residual};
+  hipStream_t st = (hipStream_t)stream;
+#define GO(V, DT) \
+  k_sp3_bn_bwd_stats<V, DT><<<(unsigned)ws.sp.blocks, kBlock, 0, st>>>(gout, y, res, n, channels, ws.sp.rpp, scale, shift, mean, invstd, relu, ws.part)
+  SP3_BN_DISPATCH(channels, dt, GO);
+#undef GO
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_bn_bwd_apply(const float* gout, const float* y, const void* residual, int32_t residual_dtype, int64_t n, int32_t channels, const float* scale,
+                         const float* shift, const float* mean, const float* invstd, int32_t relu, const float* mean_g, const float* mean_gx, float* dy,
+                         float* dresidual, pnx_stream_t stream) {
+  int32_t dt;
+  if (const int rc = sp3_bn_args("pnx_sp3_bn_bwd_apply", n, channels, residual, residual_dtype, nullptr, PNX_F32, &dt); rc != PNX_OK) return rc;
+  if (n == 0) return PNX_OK;
+  PNX_REQUIRE(gout && y && scale && shift && mean && invstd && mean_g && mean_gx && dy, PNX_ERR_INVALID, "pnx_sp3_bn_bwd_apply: null pointer");
+  PNX_REQUIRE((((uintptr_t)y | (uintptr_t)gout | (uintptr_t)dy | (uintptr_t)dresidual) & 15) == 0, PNX_ERR_INVALID,
+              "pnx_sp3_bn_bwd_apply: rows must be 16-byte aligned");
+  const Sp3BnSplit sp = sp3_bn_split(n, channels);
+  const Sp3BnRes res = {residual_dtype == PNX_F32 ? (const float*)residual : nullptr, residual_dtype == PNX_F32 ? nullptr : residual};
+  hipStream_t st = (hipStream_t)stream;
+#define GO(V, DT)                                                                                                                                   \
+  k_sp3_bn_bwd_apply<V, DT><<<(unsigned)sp.blocks, kBlock, 0, st>>>(gout, y, res, n, channels, sp.rpp, scale, shift, mean, invstd, relu, mean_g, mean_gx, dy, \
+                                                                    dresidual)
+  SP3_BN_DISPATCH(channels, dt, GO);
+#undef GO
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

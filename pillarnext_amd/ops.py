@@ -931,30 +931,61 @@ def masked_bn_stats(x, mask, center):
     return part
 
 
-def masked_bn_reduce(part):
-    """fp64 (cols): the rows of a partials array added in a fixed order -- what is all-reduced under SyncBatchNorm."""
-    if not (part.is_cuda and part.dtype == torch.float32 and part.dim() == 2 and part.is_contiguous() and part.shape[1] // 2 in MASKED_BN_CHANNELS):
-        raise PnxError(f"masked_bn_reduce: the partials must be a contiguous fp32 CUDA matrix of 2C or 2C + 1 columns with C in {MASKED_BN_CHANNELS}")
+def _masked_channels(c):
+    return c in MASKED_BN_CHANNELS
+
+
+def _bn_reduce(what, part, channels_ok, channels):
+    """Shared body of masked_bn_reduce / sp3_bn_reduce; no rows (an empty set of rows): zeros."""
+    if not (part.is_cuda and part.dtype == torch.float32 and part.dim() == 2 and part.is_contiguous() and channels_ok(part.shape[1] // 2)):
+        raise PnxError(f"{what}: the partials must be a contiguous fp32 CUDA matrix of 2C or 2C + 1 columns with {channels}")
     rows, cols = part.shape
+    if rows == 0:
+        return torch.zeros((cols,), dtype=torch.float64, device=part.device)
     s = torch.empty((cols,), dtype=torch.float64, device=part.device)
     check(lib().pnx_masked_bn_reduce(ptr(part), rows, cols, ptr(s), stream_ptr()), "pnx_masked_bn_reduce")
     return s
 
 
-def masked_bn_finalize(sums, center, weight, bias, eps, momentum, running_mean, running_var, num_batches_tracked):
-    """(mean, invstd, scale, shift (C each), count (1)) fp32 from sums = [sum d | sum d^2 | count] around `center` (None = 0), and torch's update of the
-    running statistics in place (num_batches_tracked += 1 when given)."""
+def _bn_finalize(what, channels_ok, channels, sums, center, weight, bias, eps, momentum, running_mean, running_var, num_batches_tracked):
+    """Shared body of masked_bn_finalize / sp3_bn_finalize."""
     C = (sums.numel() - 1) // 2
-    _bn_vecs("masked_bn_finalize", 2 * C + 1, sums, dtype=torch.float64)
-    _bn_vecs("masked_bn_finalize", C, center, weight, bias, running_mean, running_var)
+    _bn_vecs(what, 2 * C + 1, sums, dtype=torch.float64)
+    _bn_vecs(what, C, center, weight, bias, running_mean, running_var)
     nbt = num_batches_tracked
-    if C not in MASKED_BN_CHANNELS or (nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1)):
-        raise PnxError(f"masked_bn_finalize: 2C + 1 sums with C in {MASKED_BN_CHANNELS}, num_batches_tracked an int64 CUDA scalar")
+    if not channels_ok(C) or (nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1)):
+        raise PnxError(f"{what}: 2C + 1 sums with {channels}, num_batches_tracked an int64 CUDA scalar")
     vec = torch.empty((4 * C + 1,), dtype=torch.float32, device=sums.device)
     mean, invstd, scale, shift, cnt = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:4 * C], vec[4 * C:]
     check(lib().pnx_masked_bn_finalize(ptr(sums), C, ptr(center), ptr(weight), ptr(bias), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
                                        ptr(nbt), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(cnt), stream_ptr()), "pnx_masked_bn_finalize")
     return mean, invstd, scale, shift, cnt
+
+
+def _bn_bwd_finalize(what, channels_ok, channels, sums_local, sums_global, count):
+    """Shared body of masked_bn_bwd_finalize / sp3_bn_bwd_finalize."""
+    C = sums_local.numel() // 2
+    _bn_vecs(what, 2 * C, sums_local, sums_global, dtype=torch.float64)
+    _bn_vecs(what, 1, count)
+    if not channels_ok(C):
+        raise PnxError(f"{what}: 2C sums with {channels}")
+    vec = torch.empty((4 * C,), dtype=torch.float32, device=sums_local.device)
+    dgamma, dbeta, mg, mgx = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:]
+    check(lib().pnx_masked_bn_bwd_finalize(ptr(sums_local), ptr(sums_global), C, ptr(count), ptr(dgamma), ptr(dbeta), ptr(mg), ptr(mgx), stream_ptr()),
+          "pnx_masked_bn_bwd_finalize")
+    return dgamma, dbeta, mg, mgx
+
+
+def masked_bn_reduce(part):
+    """fp64 (cols): the rows of a partials array added in a fixed order -- what is all-reduced under SyncBatchNorm."""
+    return _bn_reduce("masked_bn_reduce", part, _masked_channels, f"C in {MASKED_BN_CHANNELS}")
+
+
+def masked_bn_finalize(sums, center, weight, bias, eps, momentum, running_mean, running_var, num_batches_tracked):
+    """(mean, invstd, scale, shift (C each), count (1)) fp32 from sums = [sum d | sum d^2 | count] around `center` (None = 0), and torch's update of the
+    running statistics in place (num_batches_tracked += 1 when given)."""
+    return _bn_finalize("masked_bn_finalize", _masked_channels, f"C in {MASKED_BN_CHANNELS}", sums, center, weight, bias, eps, momentum, running_mean,
+                        running_var, num_batches_tracked)
 
 
 def masked_bn_apply(x, residual, mask, scale, shift, relu):
@@ -980,16 +1011,7 @@ def masked_bn_bwd_stats(gy, x, residual, mask, scale, shift, mean, invstd, relu)
 def masked_bn_bwd_finalize(sums_local, sums_global, count):
     """(dgamma, dbeta, mean_g, mean_gx) fp32 (C each): the parameter gradients from the LOCAL sums [sum g | sum g xhat] (fp64 (2C)), the means over
     `count` active sites from the global ones (None: the local ones)."""
-    C = sums_local.numel() // 2
-    _bn_vecs("masked_bn_bwd_finalize", 2 * C, sums_local, sums_global, dtype=torch.float64)
-    _bn_vecs("masked_bn_bwd_finalize", 1, count)
-    if C not in MASKED_BN_CHANNELS:
-        raise PnxError(f"masked_bn_bwd_finalize: 2C sums with C in {MASKED_BN_CHANNELS}")
-    vec = torch.empty((4 * C,), dtype=torch.float32, device=sums_local.device)
-    dgamma, dbeta, mg, mgx = vec[:C], vec[C:2 * C], vec[2 * C:3 * C], vec[3 * C:]
-    check(lib().pnx_masked_bn_bwd_finalize(ptr(sums_local), ptr(sums_global), C, ptr(count), ptr(dgamma), ptr(dbeta), ptr(mg), ptr(mgx), stream_ptr()),
-          "pnx_masked_bn_bwd_finalize")
-    return dgamma, dbeta, mg, mgx
+    return _bn_bwd_finalize("masked_bn_bwd_finalize", _masked_channels, f"C in {MASKED_BN_CHANNELS}", sums_local, sums_global, count)
 
 
 def masked_bn_bwd_apply(gy, x, residual, mask, scale, shift, mean, invstd, relu, mean_g, mean_gx, want_residual_grad=False):
@@ -1312,6 +1334,124 @@ def sp3_wgrad_h(x, nbmap, dy, cin, cout):
     check(lib().pnx_sp3_wgrad_h(ptr(x), x.shape[0], ci, x.shape[1], ptr(dy), co, dy.shape[1], ptr(nbmap), n_out, T, ptr(dw), dt, ptr(part), nbytes,
                                 stream_ptr()), "pnx_sp3_wgrad_h")
     return dw
+
+
+# Train-mode BatchNorm1d + residual + ReLU over the rows (csrc/sparse3d_bn.h).  y, out, gout, dy: (n, C) fp32 rows, C in 1..SP3_BN_MAX_CHANNELS;
+# residual: None, fp32 (n, C), or padded 16-bit rows (n, round_up(C, 8)).  The per-channel passes are masked_bn's kernels, which take any C <= 256.
+SP3_BN_MAX_CHANNELS = 256
+
+
+def _sp3_bn_rows(what, y, *like_y):
+    """Validator -> (n, C): y and every other fp32 operand that is given are contiguous CUDA (n, C) fp32 rows."""
+    if not (y.is_cuda and y.dim() == 2 and y.dtype == torch.float32 and y.is_contiguous() and 1 <= y.shape[1] <= SP3_BN_MAX_CHANNELS):
+        raise PnxError(f"{what}: y must be contiguous CUDA (n, C) fp32 rows with C in 1..{SP3_BN_MAX_CHANNELS}")
+    for t in like_y:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == y.shape and t.is_contiguous()):
+            raise PnxError(f"{what}: the gradient and an fp32 residual must be contiguous CUDA fp32 rows of y's shape")
+    return y.shape[0], y.shape[1]
+
+
+def _sp3_bn_residual(what, y, residual):
+    """Validator -> the residual's PNX dtype: None, fp32 rows like y, or padded 16-bit rows (n, round_up(C, 8))."""
+    if residual is None or residual.dtype == torch.float32:
+        _sp3_bn_rows(what, y, residual)
+        return PNX_F32
+    if not (residual.is_cuda and residual.dtype in _HALF and tuple(residual.shape) == (y.shape[0], _cpad(y.shape[1])) and residual.is_contiguous()):
+        raise PnxError(f"{what}: a 16-bit residual must be contiguous CUDA bf16 / fp16 rows (n, round_up(C, 8))")
+    return _DT[residual.dtype]
+
+
+def sp3_bn_split(n, channels):
+    """(blocks, rows_per_pass, passes) of the four passes over n rows of `channels`: the rows of the partials, the rows a workgroup covers per pass
+    and the passes of the busiest workgroup (include/pnx.h: pnx_sp3_bn_split; the longest fp32 chain of a partial is passes + rows_per_pass terms)."""
+    s = (ctypes.c_int32 * 3)()
+    check(lib().pnx_sp3_bn_split(int(n), int(channels), s), "pnx_sp3_bn_split")
+    return int(s[0]), int(s[1]), int(s[2])
+
+
+def sp3_bn_partials_bytes(n, channels, backward=False):
+    nbytes = lib().pnx_sp3_bn_partials_bytes(int(n), int(channels), 1 if backward else 0)
+    if nbytes == 0:
+        raise PnxError(f"sp3_bn: no kernel for {n} rows of {channels} channels")
+    return nbytes
+
+
+def _sp3_bn_partials(n, C, backward, device):
+    """(buffer, its bytes, the (blocks, cols) fp32 view the kernel fills): call-lifetime scratch of exactly the size the library asks for."""
+    nbytes = sp3_bn_partials_bytes(n, C, backward)
+    buf = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    cols = 2 * C + (0 if backward else 1)
+    blocks = sp3_bn_split(n, C)[0]
+    return buf, nbytes, buf[: blocks * cols * 4].view(torch.float32).view(blocks, cols)
+
+
+def sp3_bn_stats(y, center):
+    """partials fp32 (blocks, 2C + 1): per workgroup [sum d | sum d^2 | rows] with d = y - center (fp32 (C), or None = 0)."""
+    n, C = _sp3_bn_rows("sp3_bn_stats", y)
+    _bn_vecs("sp3_bn_stats", C, center)
+    buf, nbytes, part = _sp3_bn_partials(n, C, False, y.device)
+    check(lib().pnx_sp3_bn_stats(ptr(y), n, C, ptr(center), ptr(buf), nbytes, stream_ptr()), "pnx_sp3_bn_stats")
+    return part
+
+
+def _sp3_bn_channels(c):
+    return 1 <= c <= SP3_BN_MAX_CHANNELS
+
+
+def sp3_bn_reduce(part):
+    """fp64 (cols): the rows of a partials array added in a fixed order (pnx_masked_bn_reduce) -- what is all-reduced under SyncBatchNorm.
+    No rows (an empty set): zeros."""
+    return _bn_reduce("sp3_bn_reduce", part, _sp3_bn_channels, f"C in 1..{SP3_BN_MAX_CHANNELS}")
+
+
+def sp3_bn_finalize(sums, center, weight, bias, eps, momentum, running_mean, running_var, num_batches_tracked):
+    """masked_bn_finalize at any C in 1..SP3_BN_MAX_CHANNELS (pnx_masked_bn_finalize never depended on the channel count)."""
+    return _bn_finalize("sp3_bn_finalize", _sp3_bn_channels, f"C in 1..{SP3_BN_MAX_CHANNELS}", sums, center, weight, bias, eps, momentum, running_mean,
+                        running_var, num_batches_tracked)
+
+
+def sp3_bn_apply(y, residual, scale, shift, relu, out_dtype=None):
+    """(out (n, C) fp32, out_h): out = [relu](y * scale + shift [+ residual]); out_dtype bf16 / fp16: out_h (n, round_up(C, 8)) = out rounded once to
+    nearest even, pad columns zero -- bit for bit sp3_rows_h(out, out_dtype) -- written in the same pass; None: out_h is None."""
+    n, C = _sp3_bn_rows("sp3_bn_apply", y)
+    rdt = _sp3_bn_residual("sp3_bn_apply", y, residual)
+    _bn_vecs("sp3_bn_apply", C, scale, shift)
+    odt = PNX_F32 if out_dtype is None else _sp3_half(out_dtype, "sp3_bn_apply")
+    if rdt != PNX_F32 and odt != PNX_F32 and rdt != odt:
+        raise PnxError("sp3_bn_apply: a 16-bit residual and out_h must have one dtype")
+    out = torch.empty_like(y)
+    out_h = None if out_dtype is None else torch.empty((n, _cpad(C)), dtype=out_dtype, device=y.device)
+    check(lib().pnx_sp3_bn_apply(ptr(y), n, C, ptr(scale), ptr(shift), ptr(residual), rdt, 1 if relu else 0, ptr(out), ptr(out_h), odt, stream_ptr()),
+          "pnx_sp3_bn_apply")
+    return out, out_h
+
+
+def sp3_bn_bwd_stats(gout, y, residual, scale, shift, mean, invstd, relu):
+    """partials fp32 (blocks, 2C): [sum g | sum g * xhat] with g = gout * [pre-activation > 0] (relu) or gout, xhat = (y - mean) * invstd."""
+    n, C = _sp3_bn_rows("sp3_bn_bwd_stats", y, gout)
+    rdt = _sp3_bn_residual("sp3_bn_bwd_stats", y, residual)
+    _bn_vecs("sp3_bn_bwd_stats", C, scale, shift, mean, invstd)
+    buf, nbytes, part = _sp3_bn_partials(n, C, True, y.device)
+    check(lib().pnx_sp3_bn_bwd_stats(ptr(gout), ptr(y), ptr(residual), rdt, n, C, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), 1 if relu else 0,
+                                     ptr(buf), nbytes, stream_ptr()), "pnx_sp3_bn_bwd_stats")
+    return part
+
+
+def sp3_bn_bwd_finalize(sums_local, sums_global, count):
+    """masked_bn_bwd_finalize at any C in 1..SP3_BN_MAX_CHANNELS (`count`: the rows behind the global sums)."""
+    return _bn_bwd_finalize("sp3_bn_bwd_finalize", _sp3_bn_channels, f"C in 1..{SP3_BN_MAX_CHANNELS}", sums_local, sums_global, count)
+
+
+def sp3_bn_bwd_apply(gout, y, residual, scale, shift, mean, invstd, relu, mean_g, mean_gx, want_residual_grad=False):
+    """(dy (n, C) fp32, the residual's gradient g (n, C) fp32 or None) of sp3_bn_apply from the upstream gradient and the means of sp3_bn_bwd_finalize."""
+    n, C = _sp3_bn_rows("sp3_bn_bwd_apply", y, gout)
+    rdt = _sp3_bn_residual("sp3_bn_bwd_apply", y, residual)
+    _bn_vecs("sp3_bn_bwd_apply", C, scale, shift, mean, invstd, mean_g, mean_gx)
+    dy = torch.empty_like(y)
+    gres = torch.empty_like(y) if want_residual_grad else None
+    check(lib().pnx_sp3_bn_bwd_apply(ptr(gout), ptr(y), ptr(residual), rdt, n, C, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), 1 if relu else 0,
+                                     ptr(mean_g), ptr(mean_gx), ptr(dy), ptr(gres), stream_ptr()), "pnx_sp3_bn_bwd_apply")
+    return dy, gres
 
 
 # --------------------------------------------------------------------------------------------- label assignment

@@ -23,13 +23,18 @@ stays fp32.  The default, training and any call that wants gradients are untouch
 use_half_precision(dtype, training=True) also moves the autograd path's convolutions onto the 16-bit matrix cores (SparseConvHalfFunction:
 pnx_sp3_conv_h_f32 for y and dx, pnx_sp3_wgrad_h for dw): the node's boundary stays fp32, its operands are rounded once, BatchNorm, residual
 and ReLU remain the module's fp32 torch ops.
+
+use_fused_norm() replaces those torch ops, in training mode, by one autograd node per layer on the kernels of csrc/sparse3d_bn.h
+(SparseBNActFunction: pnx_sp3_bn_stats / _apply / _bwd_stats / _bwd_apply): batch statistics, running-statistics update, residual and ReLU in four
+streaming passes; with 16-bit training on it also writes the next convolution's padded 16-bit rows, so no fp32 activation but the convolution
+output survives a layer's forward.  Off by default; the default path is untouched.
 """
 import math
 
 import torch
 from torch import nn
 
-from . import ops
+from . import dist_utils, ops
 from ._lib import PnxError
 from .mvf_encoder import _params_version
 
@@ -141,13 +146,16 @@ class SparseConvHalfFunction(torch.autograd.Function):
     keeps fp32's range."""
 
     @staticmethod
-    def forward(ctx, x, weight, nbmap, subm, tick, dtype, wp):
+    def forward(ctx, x, weight, nbmap, subm, tick, dtype, wp, *rows):
+        """rows: nothing, or (xh,) = rows_h(x) as the layer before already wrote it (SparseBNActFunction's out_h); x then only carries the graph."""
         w = weight.detach()
         cout, cin = w.shape[0], w.shape[-1]
-        xh = ops.sp3_rows_h(x, dtype)
+        xh = rows[0] if rows and rows[0] is not None else ops.sp3_rows_h(x, dtype)
+        if xh.dtype != dtype or xh.shape[0] != x.shape[0]:
+            raise PnxError(f"SparseConvHalfFunction: 16-bit rows {tuple(xh.shape)} of {xh.dtype} for x {tuple(x.shape)} in {dtype}")
         y = ops.sp3_conv_h_f32(xh, nbmap, wp, cin, cout)
         ctx.save_for_backward(xh, w, nbmap)
-        ctx.subm, ctx.tick, ctx.dtype = subm, tick, dtype
+        ctx.subm, ctx.tick, ctx.dtype, ctx.extra = subm, tick, dtype, len(rows)
         return y
 
     @staticmethod
@@ -164,7 +172,7 @@ class SparseConvHalfFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = ops.sp3_wgrad_h(xh, nbmap, dyh, cin, cout).view(w.shape)
             ctx.tick("wgrad")
-        return dx, dw, None, None, None, None, None
+        return (dx, dw, None, None, None, None, None) + (None,) * ctx.extra
 
 
 def sparse_conv_dgrad_h(dyh, weight, nbmap, n_in, subm):
@@ -188,6 +196,77 @@ class SparseDenseFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         return ops.sp3_dense_backward(dout, ctx.saved_tensors[0], ctx.channels), None, None, None
+
+
+class SparseBNActFunction(torch.autograd.Function):
+    """out = relu?(BatchNorm1d_train(y) [+ residual]) over the (n, C) fp32 rows of an active set in ONE autograd node on the kernels of
+    csrc/sparse3d_bn.h: stats -> reduce -> [all-reduce] -> finalize -> apply forward, bwd_stats -> reduce -> [all-reduce] -> bwd_finalize ->
+    bwd_apply backward.
+
+        forward(y, gamma, beta, residual, residual_h, norm, relu, dtype) -> (out (n, C) fp32, out_h or None)
+
+    norm (nn.BatchNorm1d or nn.SyncBatchNorm, in training mode) gives eps and momentum and has its running_mean, running_var and
+    num_batches_tracked moved exactly as torch's training-mode BatchNorm1d moves them (unbiased variance); n <= 1 without synchronisation raises
+    as torch does, n == 0 returns empty outputs and leaves the buffers alone.  The node saves y, the residual operand it read and the per-channel
+    vectors -- not out: the backward recomputes the ReLU gate from them.
+    dtype (bf16 / fp16, or None): out_h = out rounded once into padded 16-bit rows, written by the same pass and marked non-differentiable --
+    what SparseConvHalfFunction takes in place of ops.sp3_rows_h(out, dtype).
+    residual_h (16-bit mode): the padded 16-bit rows of `residual`, i.e. the out_h of the block's input.  The node then READS THE ROUNDED ROWS,
+    as the 16-bit eval path (pnx_sp3_conv_h) does, so training and inference add the same residual, and keeps only them for the backward
+    (the next convolution holds them anyway: no fp32 activation but y survives the forward); the fp32 `residual` only carries the graph, and
+    its gradient passes the rounding straight through: dresidual = g.  Without residual_h (fp32 mode) the fp32 residual is read, as before.
+    nn.SyncBatchNorm: [sum x | sum x^2 | n] is all-reduced in fp64 once in the forward (this rank's sums re-centred from its running mean to
+    0 first), [sum g | sum g xhat] once in the backward, through dist_utils.all_reduce_sum(t, norm.process_group) looked up at call time;
+    dgamma and dbeta stay the local sums (DDP averages them).  A rank without rows issues both collectives all the same."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, residual, residual_h, norm, relu, dtype):
+        if norm.momentum is None or not norm.track_running_stats or norm.running_mean is None:
+            raise PnxError("SparseBNActFunction: the norm must track running statistics with a fixed momentum")
+        y = y.contiguous()
+        n, C = y.shape
+        sync = isinstance(norm, nn.SyncBatchNorm)
+        group = norm.process_group if sync else False
+        res = residual_h if residual_h is not None else (None if residual is None else residual.contiguous())
+        ctx.relu, ctx.group, ctx.empty = bool(relu), group, n == 0 and not sync
+        if ctx.empty:
+            out_h = None if dtype is None else torch.zeros((0, ops._cpad(C)), dtype=dtype, device=y.device)
+            if out_h is not None:
+                ctx.mark_non_differentiable(out_h)
+            return torch.zeros_like(y), out_h
+        if n == 1 and not sync:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(y.shape)}")
+        center = norm.running_mean  # sums of deviations from the running mean: E[d^2] - E[d]^2 does not cancel when |mean| >> std
+        s = ops.sp3_bn_reduce(ops.sp3_bn_stats(y, center))  # [sum d | sum d^2 | n], fp64
+        if sync:
+            # the batch statistics must not depend on a rank's buffers: sum x = S1 + n c, sum x^2 = S2 + 2 c S1 + n c^2, then finalize around 0
+            c = center.double()
+            s[C:2 * C] += 2.0 * c * s[:C] + s[2 * C] * c * c
+            s[:C] += s[2 * C] * c
+            dist_utils.all_reduce_sum(s, group)
+            center = None
+        mean, invstd, scale, shift, cnt = ops.sp3_bn_finalize(s, center, gamma.detach(), beta.detach(), norm.eps, norm.momentum, norm.running_mean,
+                                                              norm.running_var, norm.num_batches_tracked)
+        out, out_h = ops.sp3_bn_apply(y, res, scale, shift, relu, dtype)
+        ctx.save_for_backward(y, res, mean, invstd, cnt, scale, shift)
+        if out_h is not None:
+            ctx.mark_non_differentiable(out_h)
+        return out, out_h
+
+    @staticmethod
+    def backward(ctx, gout, _gout_h=None):
+        if ctx.empty:
+            return gout, None, None, (gout if ctx.needs_input_grad[3] else None), None, None, None, None
+        y, res, mean, invstd, cnt, scale, shift = ctx.saved_tensors
+        gout = gout.contiguous()
+        sg = ops.sp3_bn_reduce(ops.sp3_bn_bwd_stats(gout, y, res, scale, shift, mean, invstd, ctx.relu))  # [sum g | sum g xhat], fp64
+        sg_all = None
+        if ctx.group is not False:
+            sg_all = sg.clone()
+            dist_utils.all_reduce_sum(sg_all, ctx.group)
+        dgamma, dbeta, mg, mgx = ops.sp3_bn_bwd_finalize(sg, sg_all, cnt)
+        dy, gres = ops.sp3_bn_bwd_apply(gout, y, res, scale, shift, mean, invstd, ctx.relu, mg, mgx, want_residual_grad=ctx.needs_input_grad[3])
+        return dy, dgamma, dbeta, gres, None, None, None, None
 
 
 def _fold(conv, bn, dtype=None):
@@ -220,6 +299,18 @@ class SparseResNet3D(nn.Module):
         self.profile = None  # a list: every phase of the next forwards appends (name, end event) -- tools/bench_voxel18.py
         self.half_dtype = None  # None: fp32; torch.bfloat16 / float16: the folded eval path runs in 16 bits (use_half_precision)
         self.half_train_dtype = None  # None: fp32; torch.bfloat16 / float16: the autograd path's convolutions run in 16 bits
+        self.fused_norm = False  # True: training-mode BatchNorm1d + residual + ReLU of the autograd path run in SparseBNActFunction (use_fused_norm)
+
+    def use_fused_norm(self, enabled=True):
+        """Training: every layer's BatchNorm1d (or SyncBatchNorm) + residual + ReLU of the autograd path runs as ONE node on the HIP kernels of
+        csrc/sparse3d_bn.h (SparseBNActFunction) instead of torch's batch_norm, add and relu: the same batch statistics, running-statistics
+        update and gradients up to fp32 rounding in another order, fewer passes over the rows, and only y kept per layer for the backward.
+        Together with use_half_precision(dtype, training=True) the node also writes the next convolution's padded 16-bit rows in the same pass
+        (no ops.sp3_rows_h between layers), and a block's second layer adds the ROUNDED rows of the block input, as the 16-bit eval path does,
+        with the gradient passed straight through the rounding.  A norm in eval mode (fixed statistics) keeps torch's ops.  Off by default;
+        returns self."""
+        self.fused_norm = bool(enabled)
+        return self
 
     def use_half_precision(self, dtype=torch.bfloat16, training=False):
         """Inference on 16-bit rows and the 16-bit matrix cores (pnx_sp3_conv_h), as MVFFeatureNet.use_hip_convs is for the view nets: eval-mode
@@ -310,29 +401,38 @@ class SparseResNet3D(nn.Module):
         self._tick(name + ".map")
         return oix, oc, m
 
-    def _conv(self, x, m, conv, norm, folded, name, residual=None):
-        """One layer.  folded: the plan of packed weights and shifts (eval), or None: conv -> BatchNorm1d -> (+ residual) -> ReLU under autograd."""
+    def _conv(self, x, m, conv, norm, folded, name, residual=None, rows=None, residual_rows=None):
+        """One layer -> (its output, that output's padded 16-bit rows or None).  folded: the plan of packed weights and shifts (eval), or None:
+        conv -> BatchNorm1d -> (+ residual) -> ReLU under autograd.  rows / residual_rows: the 16-bit rows of x / residual where the layer
+        before wrote them (use_fused_norm with 16-bit training), else None."""
         if folded is None:
             def tick(phase):
                 self._tick(f"{name}.{phase}")
 
             if self.half_train_dtype is None:
                 y = SparseConvFunction.apply(x, conv.weight, m, conv.subm, tick)
-            else:
+            elif rows is None:
                 y = SparseConvHalfFunction.apply(x.contiguous(), conv.weight, m, conv.subm, tick, self.half_train_dtype,
                                                  self._train_packed(self.half_train_dtype)[conv])
+            else:
+                y = SparseConvHalfFunction.apply(x, conv.weight, m, conv.subm, tick, self.half_train_dtype,
+                                                 self._train_packed(self.half_train_dtype)[conv], rows)
             self._tick(name + ".conv")
+            if self.fused_norm and norm.training:
+                y, yh = SparseBNActFunction.apply(y, norm.weight, norm.bias, residual, residual_rows, norm, True, self.half_train_dtype)
+                self._tick(name + ".rest")
+                return y, yh
             y = norm(y)
             y = torch.relu(y if residual is None else y + residual)
             self._tick(name + ".rest")
-            return y
+            return y, None
         wp, shift = folded[name]
         if wp.dtype != torch.float32:  # the 16-bit plan: padded 16-bit rows in and out
             y = ops.sp3_conv_h(x, m, wp, shift, conv.in_channels, conv.out_channels, residual=residual, relu=True)
         else:
             y = ops.sp3_conv(x, m, wp, shift, conv.out_channels, residual=residual, relu=True)
         self._tick(name + ".conv")
-        return y
+        return y, None
 
     def forward_sparse(self, pillar_features, coors, input_shape, batch_size=None):
         """The active sets: [(coords (N, 4) int32, features (N, C) fp32, grid (D, H, W))] after stage 0, 1, ..., extra_conv and mapping.
@@ -374,6 +474,7 @@ class SparseResNet3D(nn.Module):
             x = ops.sp3_rows_h(x, half)  # the one conversion of the input: rounded, channels padded to a multiple of 8
             self._tick("input.rows")
         sets = []
+        xh = None  # x's padded 16-bit rows where the layer before wrote them (use_fused_norm with 16-bit training), else None
         for i, seq in enumerate(self.blocks):
             conv = seq[0].conv
             if conv.subm:
@@ -382,22 +483,22 @@ class SparseResNet3D(nn.Module):
             else:
                 ix, coords, m = self._strided(x, coords, ix, rows, B, conv, f"blocks.{i}.0")
             rows = None  # a layer's output rows are in rank order
-            x = self._conv(x, m, conv, seq[0].norm, folded, f"blocks.{i}.0")
+            x, xh = self._conv(x, m, conv, seq[0].norm, folded, f"blocks.{i}.0", rows=xh)
             if len(seq) > 1:
                 k = seq[1].conv2.kernel_size
                 m = ops.sp3_neighbor_map(coords, ix, None, k, (1, 1, 1), tuple(a // 2 for a in k))  # shared by the stage's SubM layers
                 self._tick(f"blocks.{i}.subm.map")
                 for j, blk in enumerate(seq[1:], 1):
-                    y = self._conv(x, m, blk.block1.conv, blk.block1.norm, folded, f"blocks.{i}.{j}.block1")
-                    x = self._conv(y, m, blk.conv2, blk.norm2, folded, f"blocks.{i}.{j}.conv2", residual=x)
+                    y, yh = self._conv(x, m, blk.block1.conv, blk.block1.norm, folded, f"blocks.{i}.{j}.block1", rows=xh)
+                    x, xh = self._conv(y, m, blk.conv2, blk.norm2, folded, f"blocks.{i}.{j}.conv2", residual=x, rows=yh, residual_rows=xh)
             sets.append((coords, x, ix.grid))
         ix, coords, m = self._strided(x, coords, ix, rows, B, self.extra_conv[0], "extra_conv")
-        x = self._conv(x, m, self.extra_conv[0], self.extra_conv[1], folded, "extra_conv")
+        x, xh = self._conv(x, m, self.extra_conv[0], self.extra_conv[1], folded, "extra_conv", rows=xh)
         sets.append((coords, x, ix.grid))
         mc = self.mapping.conv
         m = ops.sp3_neighbor_map(coords, ix, None, mc.kernel_size, (1, 1, 1), mc.padding)
         self._tick("mapping.map")
-        x = self._conv(x, m, mc, self.mapping.norm, folded, "mapping")
+        x, xh = self._conv(x, m, mc, self.mapping.norm, folded, "mapping", rows=xh)
         sets.append((coords, x, ix.grid))
         return sets
 

@@ -15,7 +15,12 @@ with the HIP step in one process (--torch-frames: fewer frames for the statement
 
 --train --dtype bf16 / fp16 times the training step under use_half_precision(dtype, training=True) against the fp32 training step instead of
 the torch statement: the two arms alternate step by step in one process and each reports the same phases with its spread (min .. max over the
-iterations), its wall time and the peak memory of one step of its own; the phases are compared by the A/B rule."""
+iterations), its wall time and the peak memory of one step of its own; the phases are compared by the A/B rule.
+
+--train [--dtype bf16 / fp16] --fused-norm adds one more arm to that run: the last arm's step again under use_fused_norm (BatchNorm + residual +
+ReLU as one HIP node).  The arm in front of it -- the same step without the option -- is its yardstick.  Every arm splits "everything else"
+into the norm / residual / ReLU passes, forward (the name.rest phases) and backward (what runs in front of each convolution's backward), and
+what remains (index, maps, dense scatter)."""
 import argparse
 import collections
 import os
@@ -136,7 +141,7 @@ def train(a, reader, bb):
         ev, bb.profile = bb.profile, None
         return ev
 
-    if a.dtype != "fp32":
+    if a.dtype != "fp32" or a.fused_norm:
         return train_arms(a, bb, hip_step, B)
     tb, tf_, tc, tg = (a.torch_frames or B), None, None, None
     if tb != B:
@@ -188,25 +193,32 @@ def train(a, reader, bb):
 
 
 def train_arms(a, bb, hip_step, B):
-    """fp32 and 16-bit training steps alternating in one process."""
-    arms = [("fp32", None), (a.dtype, HALF[a.dtype])]
+    """The training steps of the arms alternating in one process: fp32, the 16-bit type of --dtype, and with --fused-norm the last of them again
+    under use_fused_norm -- the arm in front of it, the same step without the option, is its yardstick."""
+    arms = [("fp32", None, False)] + ([(a.dtype, HALF[a.dtype], False)] if a.dtype != "fp32" else [])
+    if a.fused_norm:
+        arms.append((arms[-1][0] + " + fused norm", arms[-1][1], True))
 
-    def switch(dt):
+    def switch(dt, fused):
         if dt is None:
             bb.use_half_precision(None)
         else:
             bb.use_half_precision(dt, training=True)
+        bb.use_fused_norm(fused)
 
-    for _, dt in arms:  # warm-up
-        switch(dt)
+    for _, dt, fused in arms:  # warm-up
+        switch(dt, fused)
         hip_step(False), hip_step(False)
     torch.cuda.synchronize()
-    keys = ("forward conv", "dgrad", "wgrad", "the rest", "step (events)")
-    runs = {n: {k: [] for k in keys} for n, _ in arms}
-    walls = {n: [] for n, _ in arms}
-    for _ in range(a.iters):  # the arms alternate: both see the same clocks and the same allocator state
-        for arm, dt in arms:
-            switch(dt)
+    # "the rest" = norm forward (the name.rest phases: BatchNorm + residual + ReLU; the 16-bit row conversions are inside the convolution phases) + norm
+    # backward (what runs in front of each convolution's backward: the BatchNorm / ReLU / residual backward and autograd's glue; before the last
+    # layer's also the dense gather and the loss) + everything else (index, maps, dense scatter)
+    keys = ("forward conv", "dgrad", "wgrad", "the rest", "  norm forward", "  norm backward", "  everything else", "step (events)")
+    runs = {n: {k: [] for k in keys} for n, _, _ in arms}
+    walls = {n: [] for n, _, _ in arms}
+    for _ in range(a.iters):  # the arms alternate: all see the same clocks and the same allocator state
+        for arm, dt, fused in arms:
+            switch(dt, fused)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             ev = hip_step(True)
@@ -218,11 +230,15 @@ def train_arms(a, bb, hip_step, B):
             total = sum(per.values())
             for k, v in (("forward conv", per["conv"]), ("dgrad", per["dgrad"]), ("wgrad", per["wgrad"])):
                 runs[arm][k].append(v)
-            runs[arm]["the rest"].append(total - per["conv"] - per["dgrad"] - per["wgrad"])
+            rest = total - per["conv"] - per["dgrad"] - per["wgrad"]
+            runs[arm]["the rest"].append(rest)
+            runs[arm]["  norm forward"].append(per["rest"])
+            runs[arm]["  norm backward"].append(per["bwd"])
+            runs[arm]["  everything else"].append(rest - per["rest"] - per["bwd"])
             runs[arm]["step (events)"].append(total)
     peaks = {}
-    for arm, dt in arms:  # one step of each arm alone
-        switch(dt)
+    for arm, dt, fused in arms:  # one step of each arm alone
+        switch(dt, fused)
         bb.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
@@ -230,23 +246,25 @@ def train_arms(a, bb, hip_step, B):
         hip_step(False)
         torch.cuda.synchronize()
         peaks[arm] = torch.cuda.max_memory_allocated() - base
-    bb.use_half_precision(None)
-    mean = {n: {k: sum(v) / len(v) for k, v in runs[n].items()} for n, _ in arms}
-    for arm, _ in arms:
+    switch(None, False)
+    mean = {n: {k: sum(v) / len(v) for k, v in runs[n].items()} for n, _, _ in arms}
+    for arm, _, _ in arms:
         w = sorted(walls[arm])
         print(f"## arm {arm}: HIP step by phase (HIP events, mean of {a.iters} [min .. max]; the rest = index, maps, BatchNorm / ReLU / residual, dense, "
               "autograd glue, 16-bit row conversions outside the gradients)")
         for k in keys:
             v = runs[arm][k]
-            print(f"  {k:14s} {mean[arm][k]:8.2f} ms  [{min(v):.2f} .. {max(v):.2f}]")
+            print(f"  {k:18s} {mean[arm][k]:8.2f} ms  [{min(v):.2f} .. {max(v):.2f}]")
         print(f"  forward + backward: {w[len(w) // 2]:.2f} ms per batch of {B} (median wall; min {w[0]:.2f}, max {w[-1]:.2f}), {w[len(w) // 2] / B:.2f} ms per frame; "
               f"peak memory of one step above inputs {peaks[arm] / 2**30:.2f} GiB")
-    (n0, _), (n1, _) = arms
-    for k in keys:
-        spread = max(max(runs[n][k]) - min(runs[n][k]) for n in (n0, n1))
-        d = mean[n0][k] - mean[n1][k]
-        print(f"{k}: {n0} {mean[n0][k]:.2f} ms vs {n1} {mean[n1][k]:.2f} ms: difference {d:.2f} ms = {d / max(spread, 1e-9):.1f} x the larger spread "
-              f"({spread:.2f} ms; the A/B rule asks for more than 3 x), ratio {mean[n0][k] / max(mean[n1][k], 1e-9):.2f}")
+    for (n0, _, _), (n1, _, _) in zip(arms[:-1], arms[1:]):
+        print(f"# {n0} vs {n1}")
+        for k in keys:
+            spread = max(max(runs[n][k]) - min(runs[n][k]) for n in (n0, n1))
+            d = mean[n0][k] - mean[n1][k]
+            print(f"{k.strip()}: {n0} {mean[n0][k]:.2f} ms vs {n1} {mean[n1][k]:.2f} ms: difference {d:.2f} ms = {d / max(spread, 1e-9):.1f} x the larger spread "
+                  f"({spread:.2f} ms; the A/B rule asks for more than 3 x), ratio {mean[n0][k] / max(mean[n1][k], 1e-9):.2f}")
+        print(f"peak memory of one step: {n0} {peaks[n0] / 2**30:.2f} GiB vs {n1} {peaks[n1] / 2**30:.2f} GiB")
 
 
 def main():
@@ -257,6 +275,8 @@ def main():
                     help="bf16 / fp16: time SparseResNet3D.use_half_precision as well, its forwards (--train: training steps) alternating with the fp32 ones in this run")
     ap.add_argument("--train", action="store_true", help="time forward + backward in training mode")
     ap.add_argument("--torch-frames", type=int, default=0, help="--train: frames of the torch statement (default: --frames)")
+    ap.add_argument("--fused-norm", action="store_true",
+                    help="--train: one more arm, the last one again under SparseResNet3D.use_fused_norm, alternating with the others in this run")
     a = ap.parse_args()
     torch.manual_seed(0)
     B = a.frames

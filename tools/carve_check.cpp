@@ -81,6 +81,8 @@ int main() {
     if (sp3_grid(2, grid3, &g) != PNX_OK) return 2;
     check("sp3_carve", [&](void* b) { return sp3_carve(b, g).bytes; });
     for (int cout : {18, 72, 144}) check("sp3_wgrad_h_carve", [&](void* b) { return sp3_wgrad_h_carve(b, n, 27, 18, cout).bytes; });
+    for (int backward : {0, 1})
+      for (int c : {1, 18, 144, 256}) check("sp3_bn_carve", [&](void* b) { return sp3_bn_carve(b, n * 40, c, backward != 0).bytes; });
 #elif defined(UNIT_point_layer)
     for (int backward : {0, 1})
       for (int c : {20, 576}) check("pl_carve", [&](void* b) { return pl_carve(b, n, c, c < 256 ? 24 : 256, backward != 0).bytes; });
