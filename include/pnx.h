@@ -268,6 +268,13 @@ int pnx_scatter_canvas(const float* feat_max, const int32_t* coords, const int32
  *              `T.dot(vstack(p, 1))[:3]` assigned into a float32 array), has_transform, close-point radius (0: keep every point; the
  *              reference removes |x| < 1 AND |y| < 1 from PAST sweeps only), time value (time_lag / timestamp), batch index
  *   out        (n_raw, n_copy + 2) fp32 rows [b, x', y', z', c3 .. c(n_copy-1), time]; the first *n_out rows are valid, in input order
+ * Every row of `out` is written by every call: the tail rows [*n_out, n_raw) are [-1, +0, .., +0].  The readers, the grouping and the paste drop
+ * a row whose batch index lies outside [0, B), so `out` can be handed on whole, with N = n_raw from the shape and without reading *n_out.
+ * With n_raw = 0 only *n_out (= 0) is written.  Columns of `raw` at or beyond n_copy are never read.
+ * Exactness: x' = fp32(((t0 * x + t1 * y) + t2 * z) + t3) with every product and sum in fp64, in this order (the library is built without
+ * contraction); without a transform x, y, z pass through bit for bit.  A row is dropped iff radius > 0 and |x'| < radius and |y'| < radius on the
+ * fp32 results (a NaN fails the comparison: the row is kept).  The segments must tile the rows: begin[0] = 0, end[s] = begin[s + 1], begin <= end,
+ * end[last] = n_raw -- a row is looked up by `end` alone and the table is trusted here; io.py::pack_segments refuses a table that does not.
  */
 size_t pnx_merge_sweeps_desc_bytes(void);
 size_t pnx_merge_sweeps_workspace_bytes(int64_t n_raw);

@@ -70,11 +70,28 @@ class PointUploader:
 
 
 # --------------------------------------------------------------------------------------------- multi-sweep merge on the device
+def check_segments(segments, n_rows=None):
+    """ValueError unless the segments start at row 0, are contiguous (end[s] == begin[s+1]) and have begin <= end (empty segments are fine);
+    with n_rows, the last segment must also end there.  A row outside every segment would be stamped with a neighbour's transform, time and batch."""
+    o = 0
+    for k, s in enumerate(segments):
+        b, e = int(s["begin"]), int(s["end"])
+        if b != o:
+            raise ValueError(f"segment {k} begins at row {b}, expected {o}: segments must start at row 0 and be contiguous ({'overlap' if b < o else 'gap'})")
+        if e < b:
+            raise ValueError(f"segment {k} has begin {b} > end {e}")
+        o = e
+    if n_rows is not None and o != int(n_rows):
+        raise ValueError(f"the segments cover rows [0, {o}) but the raw buffer has {int(n_rows)} rows")
+
+
 def pack_segments(segments):
     """segments: list of dicts {begin, end, batch, time, radius=0.0, transform=None (4x4 or 3x4 array)} in row order ->
-    bytes matching `struct SegDesc` of csrc/merge.hip."""
+    bytes matching `struct SegDesc` of csrc/merge.hip.  The kernel looks a row's segment up by `end` alone and trusts the table, so a table
+    that does not tile the rows from 0 on -- a gap, an overlap, begin > end -- is refused here with a ValueError."""
     import struct
 
+    check_segments(segments)
     blob = b""
     for s in segments:
         T = s.get("transform")
@@ -104,12 +121,18 @@ class SweepMerger:
     def __call__(self, raw, segments, n_copy=4, out=None, n_out=None):
         """segments: list of dicts (pack_segments) or the (tensor, count) pair of descriptors().  Returns (out (n, n_copy+2), n_out (1,) int32):
         rows [0, n_out) are the merged cloud, rows [n_out, n) carry batch index -1 (the reader drops them), so `out` can be handed to
-        the reader as a whole without a host sync."""
+        the reader as a whole without a host sync.  Tail rows are [-1, 0, .., 0]; rows of a larger `out` beyond n are left alone.
+        ValueError on a segment list that does not tile rows [0, n) (check_segments) and on n_copy outside [3, raw.shape[1]]; the pair form
+        was checked when descriptors() built it, against no row count."""
         from . import _lib
 
+        n, stride = raw.shape
+        if not 3 <= int(n_copy) <= stride:
+            raise ValueError(f"n_copy = {n_copy} must lie in [3, {stride}] (x, y, z and the copied columns of a {stride}-column raw buffer)")
+        if not isinstance(segments, tuple):
+            check_segments(segments, n)
         L = _lib.lib()
         assert raw.is_cuda and raw.dtype == torch.float32 and raw.is_contiguous()
-        n, stride = raw.shape
         desc, nseg = segments if isinstance(segments, tuple) else self.descriptors(segments, raw.device)
         ws = self._ws.get(int(L.pnx_merge_sweeps_workspace_bytes(n)), raw.device)
         if out is None:

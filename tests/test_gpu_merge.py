@@ -1,30 +1,14 @@
-"""GPU: on-device multi-sweep merge + collation (csrc/merge.hip) against the numpy restatement of
-nusc.py:76-121 / waymo.py:49-67 / collate.py:15-22 (oracle.merge_sweeps): row order and kept set exact, coordinates exact up to the
-fp64 dot product's summation order (<= 1 ulp of fp32), and the merged buffer drives the reader to the same canvas as the host path."""
+"""GPU: on-device multi-sweep merge + collation (csrc/merge.hip) against its exact twin (tests/merge_ref.py: the whole buffer, bit for
+bit) and against the numpy restatement of nusc.py:76-121 / waymo.py:49-67 / collate.py:15-22 (oracle.merge_sweeps): row order and kept set exact,
+coordinates exact up to the fp64 dot product's summation order (<= 1 ulp of fp32), and the merged buffer drives the reader to the same canvas as the
+host path.  The seams of the kernels and the sizes past one level-2 scan pass are in tests/test_gpu_merge_seams.py."""
+import merge_ref as M
 import numpy as np
 import pytest
+from merge_ref import sample as _sample  # noqa: F401  (tests/test_gpu_workspace.py imports it from here)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-
-def _sample(rng, b, nsweeps, n_per, with_tf=True, radius=1.0):
-    sweeps = []
-    for s in range(nsweeps):
-        pts = np.empty((n_per + 17 * s, 5), np.float32)
-        pts[:, :2] = rng.uniform(-40, 40, (len(pts), 2))
-        pts[: len(pts) // 20, :2] = rng.uniform(-1.5, 1.5, (len(pts) // 20, 2))     # points near the ego vehicle (close filter)
-        pts[:, 2] = rng.uniform(-3, 1, len(pts))
-        pts[:, 3] = rng.uniform(0, 255, len(pts))
-        pts[:, 4] = rng.integers(0, 32, len(pts))                                     # ring index: dropped (n_copy = 4)
-        T = None
-        if s > 0 and with_tf:
-            a = 0.01 * s
-            T = np.eye(4)
-            T[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
-            T[:3, 3] = [0.4 * s, -0.1 * s, 0.02 * s]
-        sweeps.append(dict(points=pts, batch=b, time=0.05 * s, radius=radius if s > 0 else 0.0, transform=T))
-    return sweeps
 
 
 @pytest.mark.parametrize("dataset", ["nuscenes", "waymo"])
@@ -43,6 +27,9 @@ def test_merge_matches_the_host_path(oracle, dataset):
         o += len(s["points"])
     out, n_out = SweepMerger()(torch.from_numpy(raw).cuda(), segs, n_copy=4)
     n = int(n_out.item())
+    twin, n_twin = M.merge(raw, segs, 4)
+    assert n == n_twin
+    M.assert_same_bits(out.cpu().numpy(), twin, dataset)                                             # every row, the tail included, bit for bit
     assert n == len(ref) and n < len(raw) or dataset == "waymo"
     got = out[:n].cpu().numpy()
     assert np.array_equal(got[:, 0], ref[:, 0]) and np.array_equal(got[:, 4:], ref[:, 4:])       # batch, intensity, time: exact, same order

@@ -205,3 +205,37 @@ def test_scatter_max_and_its_backward_are_exact(pillars, C):
         dropped = (index < 0) | (index >= pillars)
         assert not np.any(wgx[dropped].view(np.uint32)) and (n < 2 or int(dropped.sum()) == n // 16)
     print(f"[scatter_max {C} channels, {pillars} pillars] forward, argmax and backward equal the twin exactly at n = {P.SM_ROWS}")
+
+
+def test_scatter_max_past_one_pass_of_the_block_scan():
+    """526 500 pillars are 258 scan blocks of 2048: the level-2 scan of the pillar offsets (SCAN_IDENT, as in the sweep merge) takes a second pass through its
+    carry loop.  Rows on both sides of that seam (pillars 524 287 and 524 288) and on the last pillar; most pillars are empty."""
+    from pillarnext_amd import ops
+    from pillarnext_amd._lib import check, lib, ptr, stream_ptr
+
+    pillars, n, C = 526_500, 20_000, 4
+    assert -(-pillars // 2048) > 256
+    rng = np.random.default_rng(526)
+    x = np.clip(np.round(rng.standard_normal((n, C)) * 4.0) / 4.0, -2.0, 2.0).astype(np.float32)
+    index = rng.integers(0, pillars, n).astype(np.int64)
+    index[:3000] = rng.integers(524_000, 524_600, 3000)                                        # a crowd around the seam of the two passes
+    index[3000:3040] = np.repeat([524_287, 524_288, pillars - 1, 0], 10)
+    index[3040:3100] = np.array([-1, pillars, 1 << 40], np.int64)[np.arange(60) % 3]
+    rng.shuffle(index)
+    x[index == 524_288] = -np.abs(x[index == 524_288]) - np.float32(0.25)                      # an all-negative pillar right behind the seam
+    want, warg = P.scatter_max(x, index, pillars)
+    assert all((warg[p] < n).all() for p in (0, 524_287, 524_288, pillars - 1)) and int((warg[:, 0] < n).sum()) < pillars // 20
+    xt, it = torch.from_numpy(x).cuda(), torch.from_numpy(index).cuda()
+    out, arg = ops.scatter_max(xt, it, pillars)
+    assert np.array_equal(arg.cpu().numpy(), warg) and np.array_equal(out.cpu().numpy().view(np.uint32), want.view(np.uint32))
+    ops._SM_WS.buf.fill_(0xFF)
+    out2, arg2 = ops.scatter_max(xt, it, pillars)
+    assert torch.equal(_bits(out2), _bits(out)) and torch.equal(arg2, arg)
+    g = torch.from_numpy(rng.standard_normal((pillars, C)).astype(np.float32)).cuda()
+    wgx = P.scatter_max_backward(g.cpu().numpy(), warg, n)
+    gx = torch.full((n, C), float("nan"), device="cuda")
+    check(lib().pnx_scatter_max_backward(ptr(g), ptr(arg), n, C, pillars, ptr(gx), stream_ptr()), "pnx_scatter_max_backward")
+    assert np.array_equal(gx.cpu().numpy().view(np.uint32), wgx.view(np.uint32))
+    xr = xt.clone().requires_grad_(True)
+    ops.scatter_max(xr, it, pillars)[0].backward(g)
+    assert np.array_equal(xr.grad.cpu().numpy().view(np.uint32), wgx.view(np.uint32))

@@ -1,7 +1,9 @@
 """The multi-sweep merge pinned to the REFERENCE: tests/golden/merge_sweeps.npz holds raw sweep files and the output of the reference's own
 NuScenesDataset.load_pointcloud (nusc.py:76-121: fp64 4x4 transform stored back as fp32, remove_close on past sweeps, time-lag column) and
 WaymoDataset.load_pointcloud (waymo.py:49-67: nlz filter, inv(pose) @ sweep_pose, timestamp column), made by oracle/gen_golden.py merge.
-CPU: the numpy restatement oracle.merge_sweeps; GPU: the device merge (csrc/merge.hip behind io.SweepMerger)."""
+CPU: the numpy restatement oracle.merge_sweeps; GPU: the device merge (csrc/merge.hip behind io.SweepMerger), also bit for bit against its exact twin
+(tests/merge_ref.py, which tests/test_merge_ref_cpu.py holds to this same golden file)."""
+import merge_ref
 import numpy as np
 import pytest
 
@@ -59,6 +61,9 @@ def test_device_merge_equals_the_reference(ds):
     out, n_out = SweepMerger()(torch.from_numpy(raw).cuda(), segs, n_copy=4)
     n = int(n_out.item())
     got = out[:n].cpu().numpy()
+    twin, n_twin = merge_ref.merge(raw, segs, 4)                              # the exact twin of the kernel: the whole buffer, bit for bit
+    assert n == n_twin
+    merge_ref.assert_same_bits(out.cpu().numpy(), twin, ds)
     assert n == len(ref) and bool((got[:, 0] == 1).all())
     assert np.array_equal(got[:, 4:], ref[:, 3:])
     np.testing.assert_allclose(got[:, 1:4], ref[:, :3], rtol=0, atol=8e-6)    # <= 1 ulp of fp32 at |x| <= 75 m
