@@ -305,14 +305,23 @@ int pnx_deconv2x2_bf16(const void* x, const void* wfrag, const float* bias, void
                        int32_t relu, pnx_stream_t stream);
 int pnx_deconv2x2_f16(const void* x, const void* wfrag, const float* bias, void* y, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout,
                        int32_t relu, pnx_stream_t stream); /* IEEE-half twin */
+/* Bytes of the row_dirty array of a (batch, ho, wo) output buffer of pnx_conv3x3_bf16 / _f16 (the layout is stated there); 0 for an empty shape. */
+size_t pnx_conv3x3_row_dirty_bytes(int32_t batch, int32_t ho, int32_t wo);
 /* Masked 3x3 convolution (pad 1, stride 1 or 2) with the same epilogue fused, bf16 NHWC, fp32 accumulation on MFMA:
  *   y = mask_out * [relu]( conv3x3(x, W) + bias [+ residual] ),  rows/tiles of the output without an active site are skipped.
  *   x (B,h,w,cin), y/residual (B,ho,wo,cout), mask uint8 (B,ho,wo) or NULL; wfrag = weights in MFMA-fragment order
  *   (pillarnext_amd/ops.py::conv3x3_pack_weights).  Built for (cin,cout) in {(64,64), (64,128), (128,128)} at stride 1|2 and {(64,320), (64,384), (64,448)} at stride 1.
- *   row_dirty (optional, with a mask): uint8 (B, ho, ceil(wo/32)), one flag per 32-pixel row segment of y -- "may hold non-zero
- *   data".  With it the kernel keeps y sparse-in-dense: segments without an active site are zero-filled only when their flag is
- *   set (then cleared), segments with active sites are written and flagged; an all-empty segment of a PERSISTENT output buffer
- *   costs no HBM traffic at all.  Contract: (y, row_dirty) start zeroed and y is only ever written through this function. */
+ *   row_dirty (optional, with a mask): the state of a PERSISTENT output buffer, pnx_conv3x3_row_dirty_bytes(B, ho, wo) bytes at a 256-byte
+ *   aligned address.  With n_seg = B * ho * ceil(wo/32) 32-pixel row segments of y it holds
+ *     [ uint8 flag[n_seg] ][ pad to a multiple of 256 ][ uint32 written[n_seg] ][ pad to a multiple of 256 ]
+ *   flag (B, ho, ceil(wo/32)): 1 = the segment holds an active site after the last call -- "may hold non-zero data"; written: bit p =
+ *   pixel p of the segment may hold non-zero data.  With it the kernel keeps y sparse-in-dense: a call zeroes only the pixels that are
+ *   written and not active now, stores the active ones and leaves written = the segment's active pixels, flag = (written != 0); an
+ *   all-empty segment costs no HBM traffic at all, and a second call with the same mask stores no zero.  PNX_CONV_STALE=0 (read once
+ *   per process) zeroes every inactive pixel of a segment with a written pixel instead -- the behaviour before the masks; they are kept
+ *   current all the same.  Contract: the whole array and y start zeroed and y is only ever written through this function.
+ *   (Until the written masks the array was the n_seg flag bytes alone: an array of that size is NO LONGER VALID -- the kernels read and
+ *   write the masks behind the flags.  Size it with pnx_conv3x3_row_dirty_bytes; pnx_conv_tile_list reads the flags as before.) */
 int pnx_conv3x3_bf16(const void* x, const void* wfrag, const float* bias, const void* residual, const uint8_t* mask, void* y, int32_t batch,
                      int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride, int32_t relu, uint8_t* row_dirty, const int32_t* tile_list,
                      const int32_t* tile_count, pnx_stream_t stream);

@@ -40,7 +40,7 @@ template <int CIN, int COUT, int STRIDE, bool W_LDS>
 __global__ __launch_bounds__(256, 2) void k_conv3x3(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                  const float* __restrict__ bias, const uint16_t* __restrict__ res,
                                                  const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W, int Ho,
-                                                 int Wo, int relu, uint8_t* __restrict__ row_dirty) {
+                                                 int Wo, int relu, RowDirty row_dirty) {
   constexpr int CB = CIN / 16, MT = COUT / 32, KSTEPS = 9 * CB;
   constexpr int NT = (MT <= 2) ? 4 : 2;  // rows of 32 pixels per wave: 8 accumulators either way
   extern __shared__ uint4 s_w[];         // KSTEPS * MT * 64 uint4 when W_LDS
@@ -69,17 +69,19 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const uint16_t* __restrict__
       any_row[j] = __ballot(act[j]) != 0;
       any = any || any_row[j];
     }
-    // rows without an active site are written (as zeros) only when the row segment may hold stale data (see pnx.h: row_dirty)
+    // rows without an active site are written (as zeros) only when the row segment may hold stale data (see pnx.h: row_dirty); a row form: what it
+    // writes it writes whole, so the written mask of a row is its row mask
     bool row_store[NT];
 #pragma unroll
     for (int j = 0; j < NT; j++) {
       const int oy = oy0 + j;
       row_store[j] = oy < Ho;
-      if (row_dirty != nullptr && oy < Ho) {
-        uint8_t* d = row_dirty + ((int64_t)b * Ho + oy) * tiles_x + tx;
-        const bool was = __builtin_amdgcn_readfirstlane((int)*d) != 0;
-        row_store[j] = any_row[j] || was;
-        if (lane == 0 && was != any_row[j]) *d = any_row[j] ? 1 : 0;
+      const uint32_t now = (uint32_t)__ballot(act[j]);  // lanes 32..63 repeat the 32 pixels
+      if (row_dirty.flag != nullptr && oy < Ho) {
+        const int64_t seg = ((int64_t)b * Ho + oy) * tiles_x + tx;
+        const uint32_t was = (uint32_t)__builtin_amdgcn_readfirstlane((int)rd_load(row_dirty, seg));
+        row_store[j] = any_row[j] || was != 0;
+        if (lane == 0) rd_store(row_dirty, seg, was, now);
       }
     }
     v16f acc[NT][MT];
@@ -317,6 +319,11 @@ int PNX_CONV_FN(pnx_deconv2x2)(const void* x, const void* wfrag, const float* bi
 }
 
 #ifndef PNX_CONV_F16  // type-independent helpers: in the bf16 object only
+size_t pnx_conv3x3_row_dirty_bytes(int32_t batch, int32_t ho, int32_t wo) {
+  if (batch <= 0 || ho <= 0 || wo <= 0) return 0;
+  return row_dirty_carve(nullptr, (int64_t)batch * ho * ((wo + 31) / 32)).bytes;
+}
+
 int pnx_conv3x3_tile_rows(int32_t cin, int32_t cout, int32_t stride) {
   if (stride != 1) return 0;
   if (cin == 64 && (cout == 64 || cout == 320 || cout == 384 || cout == 448)) return LDS_TH;
@@ -363,7 +370,16 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
               "16-byte alignment required");
   const int ho = (h + 2 - 3) / stride + 1, wo = (w + 2 - 3) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
-  const ConvArgs a = {(const uint16_t*)x, (const uint4*)wfrag, bias, (const uint16_t*)residual, mask, (uint16_t*)y, batch, h, w, relu, row_dirty, tile_list,
+  // PNX_CONV_STALE: 1 (default) zero only the pixels that went stale since the buffer's last launch (the written masks behind the flags); 0: every inactive
+  // pixel of a flagged segment, as before the masks (the cross-check)
+  static const int stale_mode = getenv("PNX_CONV_STALE") != nullptr ? atoi(getenv("PNX_CONV_STALE")) : 1;
+  RowDirty rd = {nullptr, nullptr, stale_mode != 0 ? 1 : 0};
+  if (row_dirty != nullptr) {
+    PNX_REQUIRE(((uintptr_t)row_dirty & 255) == 0, PNX_ERR_INVALID, "row_dirty must be 256-byte aligned (pnx_conv3x3_row_dirty_bytes: flags, then written masks)");
+    const RowDirtyWs rw = row_dirty_carve(row_dirty, (int64_t)batch * ho * ((wo + 31) / 32));
+    rd.flag = rw.flag, rd.written = rw.written;
+  }
+  const ConvArgs a = {(const uint16_t*)x, (const uint4*)wfrag, bias, (const uint16_t*)residual, mask, (uint16_t*)y, batch, h, w, relu, rd, tile_list,
                       tile_count, st};
   if (stride == 1 && getenv("PNX_CONV_DIRECT") == nullptr) {
     static const int pc_mode = getenv("PNX_CONV_PC") != nullptr ? atoi(getenv("PNX_CONV_PC")) : 1;  // bit 0: 64 -> 64 on the producer / consumer kernel (default), bit 1: 128 -> 128 and 256 -> 256, bit 2: 64 -> 320 / 384 / 448; 0: row-split kernels only (the cross-check)
@@ -392,9 +408,9 @@ int PNX_CONV_FN(pnx_conv3x3)(const void* x, const void* wfrag, const float* bias
     if (cin == 64 && cout == 448) return launch_lds<448>(a);
   }
   if (stride == 2 && residual == nullptr && getenv("PNX_CONV_DIRECT") == nullptr) {  // launch_s2 is shared with the fp32 training entries: pieces + plain arguments
-    if (cin == 64 && cout == 128) return launch_s2<64, 128, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
-    if (cin == 128 && cout == 256) return launch_s2<128, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
-    if (cin == 256 && cout == 256) return launch_s2<256, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, row_dirty, st);
+    if (cin == 64 && cout == 128) return launch_s2<64, 128, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, rd, st);
+    if (cin == 128 && cout == 256) return launch_s2<128, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, rd, st);
+    if (cin == 256 && cout == 256) return launch_s2<256, 256, 1>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, relu, rd, st);
   }
 #define PNX_CONV_CASE(CI, CO)                             \
   if (cin == CI && cout == CO) {                          \
@@ -443,9 +459,9 @@ int conv3x3_f32_impl(const char* name, PnxPieces<NP> x, PnxPieces<NP> wfrag, con
     if (cin == 256 && cout == 256) return launch_pc_f32<256, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, st);
   } else {
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    if (cin == 64 && cout == 128) return launch_s2<64, 128, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
-    if (cin == 128 && cout == 256) return launch_s2<128, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
-    if (cin == 256 && cout == 256) return launch_s2<256, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, nullptr, st);
+    if (cin == 64 && cout == 128) return launch_s2<64, 128, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, RowDirty{nullptr, nullptr, 1}, st);
+    if (cin == 128 && cout == 256) return launch_s2<128, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, RowDirty{nullptr, nullptr, 1}, st);
+    if (cin == 256 && cout == 256) return launch_s2<256, 256, NP>(x, wfrag, bias, mask, y, batch, h, w, ho, wo, 0, RowDirty{nullptr, nullptr, 1}, st);
   }
   pnx_set_error("%s: no kernel for %d -> %d channels, stride %d", name, cin, cout, stride);
   return PNX_ERR_UNSUPPORTED;

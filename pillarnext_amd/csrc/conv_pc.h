@@ -7,8 +7,8 @@
 // the MFMA pipe 28 % busy (profiles/r02_conv_sq_counters.md).  A wave cannot prefetch the next tile behind its own weight stream because
 // LDS-DMA and the weight-fragment loads share one in-order vmcnt.  Here the roles are separate waves of ONE 12-wave workgroup per CU:
 //   waves 8..11  producers: tile schedule (tickets three tiles ahead), mask bytes -> row masks, the deal of the tile's active rows to the row groups
-//                (producer 0; packed form: the list of the tile's active pixels), zero-fill of rows that went inactive (packed form: and of the
-//                inactive pixels of active rows), and the HBM -> LDS staging of the NEXT tile (global_load_lds) into a ring of
+//                (producer 0; packed form: the list of the tile's active pixels), zero-fill of rows that went inactive (packed form: of the pixels
+//                that went stale, in emptied and in active rows -- the written masks of pnx.h's row_dirty), and the HBM -> LDS staging of the NEXT tile (global_load_lds) into a ring of
 //                halo-tile slots, one fill ahead of the consumers; their vmcnt holds nothing else;
 //   waves 0..7   consumers: NRG row groups x NCG groups of 32 output channels; a wave = up to 4 row segments x 32 channels (64 accumulator
 //                registers, 140-167 in all and no scratch, so three waves fit a SIMD: two consumers + one producer), weights through a buffer
@@ -234,7 +234,7 @@ template <int CIN, int COUT, bool HAS_RES, int NP = 1, bool PACK = false>
 __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, const uint4* __restrict__ wfrag,
                                                        const uint4* __restrict__ wfrag2, const float* __restrict__ bias,
                                                        const uint16_t* __restrict__ res, const uint8_t* __restrict__ mask, uint16_t* __restrict__ y,
-                                                       int B, int H, int W, int relu, uint8_t* __restrict__ row_dirty, int slot,
+                                                       int B, int H, int W, int relu, RowDirty row_dirty, int slot,
                                                        const int32_t* __restrict__ tlist, const int32_t* __restrict__ tcount,
                                                        const uint16_t* __restrict__ x3 = nullptr, const uint4* __restrict__ wfrag3 = nullptr) {
   constexpr bool X3 = NP == 2, F32 = NP > 1;
@@ -282,11 +282,11 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       return tile_at(tlist, idx, n_tiles);
     };
     uint32_t mb[TH / 2];  // mask bytes of the tile whose meta data is in flight: rows 2k + (lane >> 5), pixel lane & 31
-    uint32_t dirty = 0;   // row_dirty flag of row `lane`
+    uint32_t wrt = 0;     // written mask (pnx.h: row_dirty) of row `lane`'s segment, as the last launch into y left it
     auto load_meta = [&](int64_t t) {
 #pragma unroll
       for (int k = 0; k < TH / 2; k++) mb[k] = 0;
-      dirty = 0;
+      wrt = 0;
       if (t < 0) return;
       const int tx = (int)(t % tiles_x), ty = (int)((t / tiles_x) % tiles_y), b = (int)(t / ((int64_t)tiles_x * tiles_y));
       const int ox = tx * 32 + (lane & 31);
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
         if (ox < W && oy < H) mb[k] = mask != nullptr ? (uint32_t)mask[((int64_t)b * H + oy) * W + ox] : 1u;
       }
       const int oy2 = ty * TH + lane;
-      if (lane < TH && oy2 < H) dirty = row_dirty != nullptr ? (uint32_t)row_dirty[((int64_t)b * H + oy2) * tiles_x + tx] : 1u;
+      if (lane < TH && oy2 < H) wrt = rd_load(row_dirty, ((int64_t)b * H + oy2) * tiles_x + tx);
     };
 
     int n = 0, f = 0, nf = 0, g = 0;
@@ -332,7 +332,8 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
         if (lane == 2 * k + 1) my_rm = hi;
         am |= (lo != 0 ? 1u : 0u) << (2 * k) | (hi != 0 ? 1u : 0u) << (2 * k + 1);
       }
-      const uint32_t was = (uint32_t)__ballot(dirty != 0) & ((1u << TH) - 1u);
+      const uint32_t was = (uint32_t)__ballot(wrt != 0) & ((1u << TH) - 1u);
+      const uint32_t my_wr = wrt;  // lane r < TH: written mask of row r before this launch (load_meta below overwrites wrt with the next tile's)
       if (pw == 0) {
         if (lane < TH) s_rowmask[n & 3][lane] = my_rm;
         if (lane == 0) s_tile[n & 3] = make_int4(cb, cy0, cx0, (int)(am | (uint32_t)n_px << 16));
@@ -354,34 +355,37 @@ __global__ __launch_bounds__(768, 3) void k_conv3x3_pc(const uint16_t* __restric
       t_next = tile_index(n + 1);
       load_meta(t_next);
       // rows of this producer (r = pw, pw + 4, ...): zero-fill what went inactive, keep row_dirty current
+      const uint32_t cols = W - cx0 >= 32 ? 0xffffffffu : (1u << (W - cx0)) - 1u;  // columns inside the image
+      const uint32_t my_stale = rd_held(row_dirty, my_wr) & ~my_rm & cols;         // lane r < TH: pixels of row r that may hold data and are inactive now
 #pragma unroll 1
       for (int r = pw; r < TH; r += 4) {
         const int oy = cy0 + r;
         if (oy >= H) break;
         const bool active = (am >> r) & 1u, w = (was >> r) & 1u;
-        if (!active && w) {
+        if (!PACK && !active && w) {  // the row form stores an active row whole, zeros included: only rows that lost all their sites are left
           char* dst = reinterpret_cast<char*>(y + (((int64_t)cb * H + oy) * W + cx0) * COUT * YS);
           const int nbytes = (W - cx0 < 32 ? W - cx0 : 32) * COUT * 2 * YS;
 #pragma unroll 1
           for (int o = lane * 16; o < nbytes; o += 1024) *reinterpret_cast<uint4*>(dst + o) = make_uint4(0, 0, 0, 0);
         }
         if constexpr (PACK) {
-          // inactive pixels of an active row: the row form stores their zeros with the row; the consumers of this form store listed pixels only, so they
-          // are zeroed here where the segment may hold stale values (row_dirty; without one, always).  Other lines than the consumers write, so the order
-          // between the two does not matter.  Lane L writes chunk L & 7 of pixel c0 + (L >> 3): every store instruction covers 8 complete 128-byte lines.
-          if (active && w) {
-            const uint32_t cols = W - cx0 >= 32 ? 0xffffffffu : (1u << (W - cx0)) - 1u;  // columns inside the image
-            const uint32_t idle = ~(uint32_t)__builtin_amdgcn_readlane((int)my_rm, r) & cols;
+          // The consumers of this form store listed pixels only, so the pixels that went stale -- written by the buffer's last launch (row_dirty; without
+          // one, all of them) and inactive now, in a row that is still active or in one that lost all its sites -- are zeroed here.  Other lines than the
+          // consumers write, so the order between the two does not matter.  Lane L writes chunk L & 7 of pixel c0 + (L >> 3): every store instruction
+          // covers 8 complete 128-byte lines.
+          const uint32_t stale = (uint32_t)__builtin_amdgcn_readlane((int)my_stale, r);
+          if (stale != 0) {
             char* dst = reinterpret_cast<char*>(y + (((int64_t)cb * H + oy) * W + cx0) * COUT);
 #pragma unroll 1
             for (int c0 = 0; c0 < 32; c0 += 8) {
-              if (((idle >> c0) & 255u) == 0) continue;
+              if (((stale >> c0) & 255u) == 0) continue;
               const int p = c0 + (lane >> 3);
-              if ((idle >> p) & 1u) *reinterpret_cast<uint4*>(dst + p * (COUT * 2) + (lane & 7) * 16) = make_uint4(0, 0, 0, 0);
+              if ((stale >> p) & 1u) *reinterpret_cast<uint4*>(dst + p * (COUT * 2) + (lane & 7) * 16) = make_uint4(0, 0, 0, 0);
             }
           }
         }
-        if (row_dirty != nullptr && lane == 0 && w != active) row_dirty[((int64_t)cb * H + oy) * tiles_x + tx] = active ? 1 : 0;
+        const uint32_t wr_r = (uint32_t)__builtin_amdgcn_readlane((int)my_wr, r), rm_r = (uint32_t)__builtin_amdgcn_readlane((int)my_rm, r);
+        if (lane == 0) rd_store(row_dirty, ((int64_t)cb * H + oy) * tiles_x + tx, wr_r, rm_r);
       }
       nf = am != 0 ? NFILL : 1;
       f = 0;
@@ -565,7 +569,7 @@ int launch_pc_f32(PnxPieces<NP> x, PnxPieces<NP> w, const float* bias, const uin
   if (nb > 256) nb = 256;
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   k_conv3x3_pc<CIN, COUT, false, NP><<<(unsigned)nb, 768, 0, st>>>((const uint16_t*)x.hi, (const uint16_t*)x.slot2(), (const uint4*)w.hi, (const uint4*)w.slot2(),
-                                                                   bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, nullptr, slot, nullptr, nullptr,
+                                                                   bias, nullptr, mask, (uint16_t*)y, B, H, W, 0, RowDirty{nullptr, nullptr, 1}, slot, nullptr, nullptr,
                                                                    (const uint16_t*)x.slot3(), (const uint4*)w.slot3());
   PNX_LAUNCH_CHECK();
   return PNX_OK;

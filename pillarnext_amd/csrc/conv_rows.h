@@ -66,7 +66,7 @@ template <int COUT, bool HAS_RES>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                      const float* __restrict__ bias, const uint16_t* __restrict__ res,
                                                      const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W,
-                                                     int relu, uint8_t* __restrict__ row_dirty, int slot, const int32_t* __restrict__ tlist,
+                                                     int relu, RowDirty row_dirty, int slot, const int32_t* __restrict__ tlist,
                                                       const int32_t* __restrict__ tcount) {
   constexpr int CIN = 64;
   constexpr int TH = LDS_TH, HW_ = LDS_HW;
@@ -78,10 +78,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restri
   const int px = lane & 31, kb = lane >> 5;
   const int tiles_x = (W + 31) >> 5, tiles_y = (H + TH - 1) / TH;
   const int64_t n_tiles = tlist != nullptr ? (int64_t)__builtin_amdgcn_readfirstlane(*tcount) : (int64_t)B * tiles_y * tiles_x;
-  // requests the mask bytes / row_dirty flags of the rows this wave looks at in tile t (t < 0: none)
+  // requests the mask bytes / written masks (pnx.h: row_dirty) of the rows this wave looks at in tile t (t < 0: none)
   auto load_mask = [&](int64_t t, bool (&a)[4], int (&wz)[4]) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) a[j] = false, wz[j] = 1;
+    for (int j = 0; j < 4; j++) a[j] = false, wz[j] = -1;
     if (t < 0) return;
     const int tx = (int)(t % tiles_x);
     const int ty = (int)((t / tiles_x) % tiles_y);
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restri
     for (int j = 0; j < 4; j++) {
       const int oy = ty * TH + wv * 4 + j;
       a[j] = ox < W && oy < H && (mask == nullptr || mask[((int64_t)b * H + oy) * W + ox] != 0);
-      if (row_dirty != nullptr && oy < H) wz[j] = (int)row_dirty[((int64_t)b * H + oy) * tiles_x + tx];
+      if (oy < H) wz[j] = (int)rd_load(row_dirty, ((int64_t)b * H + oy) * tiles_x + tx);
     }
   };
   int64_t idxB = (int64_t)blockIdx.x + gridDim.x, idxC = 0;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restri
   int wasP[4], wasN[4];
   load_mask(tileA, aP, wasP);
 #pragma unroll
-  for (int j = 0; j < 4; j++) aN[j] = false, wasN[j] = 1;
+  for (int j = 0; j < 4; j++) aN[j] = false, wasN[j] = -1;
   CT_DECL
   int it = 0;
   for (; tileA >= 0; tileA = tileB, tileB = tileC, idxB = idxC, it++) {
@@ -113,12 +113,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restri
     const int x0 = tx * 32, y0 = ty * TH;
     const int ox = x0 + px;
     CT_TOCK(7)
-    bool was[4];
+    uint32_t was[4], bal[4];  // written mask of the row segment before this launch, its active pixels now
 #pragma unroll
     for (int j = 0; j < 4; j++) {  // active sites: one 32-bit column mask per row of the tile, from the bytes requested one tile ago
-      was[j] = __builtin_amdgcn_readfirstlane(wasP[j]) != 0;
-      const uint32_t bal = (uint32_t)__ballot(aP[j]);
-      if (lane == 0) s_rowmask[wv * 4 + j] = bal;
+      was[j] = (uint32_t)__builtin_amdgcn_readfirstlane(wasP[j]);
+      bal[j] = (uint32_t)__ballot(aP[j]);
+      if (lane == 0) s_rowmask[wv * 4 + j] = bal[j];
     }
     __syncthreads();  // row masks visible; everybody is done reading the previous tile's s_in
     idxC = sched_next2(s_next, it, slot, idxB);
@@ -129,17 +129,17 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_lds(const uint16_t* __restri
     CT_TOCK(0)
     const uint32_t my_rm = s_rowmask[lane & 15];
     const uint32_t am = (uint32_t)__ballot(my_rm != 0) & 0xffffu;  // rows with an active site (wave-uniform, same in all waves)
-    // ---- rows without any active site: zero-fill where needed (natural rows of this wave)
+    // ---- rows without any active site: zero-fill the pixels that may hold data (natural rows of this wave); active rows are stored whole
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int rr = wv * 4 + j, oy = y0 + rr;
       const bool active = (am >> rr) & 1u;
-      if (!active && was[j] && oy < H && ox < W) {
+      if (!active && ((rd_held(row_dirty, was[j]) >> px) & 1u) && oy < H && ox < W) {
         uint4* dst = reinterpret_cast<uint4*>(y + (((int64_t)b * H + oy) * W + ox) * COUT);
 #pragma unroll 1
         for (int ch = kb; ch < COUT / 8; ch += 2) dst[ch] = make_uint4(0, 0, 0, 0);
       }
-      if (row_dirty != nullptr && oy < H && lane == 0 && was[j] != active) row_dirty[((int64_t)b * H + oy) * tiles_x + tx] = active ? 1 : 0;
+      if (oy < H && lane == 0) rd_store(row_dirty, ((int64_t)b * H + oy) * tiles_x + tx, was[j], bal[j]);
     }
     if (am == 0) continue;  // uniform over the workgroup
     // ---- the active rows, dealt round-robin to the waves (wave wv takes the active rows number wv, wv+4, ...)
@@ -365,7 +365,7 @@ template <int CIN, int COUT, bool HAS_RES, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                       const float* __restrict__ bias, const uint16_t* __restrict__ res,
                                                       const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W,
-                                                      int relu, uint8_t* __restrict__ row_dirty, int slot, const int32_t* __restrict__ tlist,
+                                                      int relu, RowDirty row_dirty, int slot, const int32_t* __restrict__ tlist,
                                                       const int32_t* __restrict__ tcount) {
   static_assert(CIN % 64 == 0 && (COUT % 128 == 0 || COUT == 64), "64-channel input slabs, 128-channel output passes (or one of 64)");
   constexpr int TH = L128_TH, HW_ = LDS_HW;
@@ -391,10 +391,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
     const int t = tlist != nullptr ? tlist[i / NH] : i / NH;
     return t * NH + i % NH;
   };
-  // requests the mask bytes / row_dirty flags of the rows this wave looks at in tile t (t < 0: none)
+  // requests the mask bytes / written masks (pnx.h: row_dirty) of the rows this wave looks at in tile t (t < 0: none)
   auto load_mask = [&](int t, bool (&a)[2], int (&wz)[2]) {
 #pragma unroll
-    for (int j = 0; j < 2; j++) a[j] = false, wz[j] = 1;
+    for (int j = 0; j < 2; j++) a[j] = false, wz[j] = -1;
     if (t < 0) return;
     const int tx = (int)(t % tiles_x);
     const int ty = (int)((t / tiles_x) % tiles_y);
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
     for (int j = 0; j < 2; j++) {
       const int oy = ty * TH + wv * 2 + j;
       a[j] = ox < W && oy < H && (mask == nullptr || mask[((int64_t)b * H + oy) * W + ox] != 0);
-      if (row_dirty != nullptr && oy < H) wz[j] = (int)row_dirty[((int64_t)b * H + oy) * tiles_x + tx];
+      if (oy < H) wz[j] = (int)rd_load(row_dirty, ((int64_t)b * H + oy) * tiles_x + tx);
     }
   };
   int64_t idxB = (int64_t)blockIdx.x + gridDim.x, idxC = 0;
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
   int wasP[2], wasN[2];
   load_mask(tileA >= 0 ? tileA / NH : -1, aP, wasP);
 #pragma unroll
-  for (int j = 0; j < 2; j++) aN[j] = false, wasN[j] = 1;
+  for (int j = 0; j < 2; j++) aN[j] = false, wasN[j] = -1;
   int it = 0;
   for (; tileA >= 0; tileA = tileB, tileB = tileC, idxB = idxC, it++) {
     const int unit = __builtin_amdgcn_readfirstlane(tileA);  // uniform by construction: everything derived from it (origins, row pointers) lives in scalar registers
@@ -426,11 +426,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
     const int b = (int)(tile / ((int64_t)tiles_x * tiles_y));
     const int x0 = tx * 32, y0 = ty * TH;
     const int ox = x0 + px;
-    bool was[2];
-    uint32_t bal[2];
+    uint32_t was[2], bal[2];  // written mask of the row segment before this launch, its active pixels now
 #pragma unroll
     for (int j = 0; j < 2; j++) {  // active sites: one 32-bit column mask per row of the tile, from the bytes requested one tile ago
-      was[j] = __builtin_amdgcn_readfirstlane(wasP[j]) != 0;
+      was[j] = (uint32_t)__builtin_amdgcn_readfirstlane(wasP[j]);
       bal[j] = (uint32_t)__ballot(aP[j]);
       if (lane == 0) s_rowmask[wv * 2 + j] = bal[j];
     }
@@ -443,16 +442,18 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
     const uint32_t my_rm = s_rowmask[lane & 7];
     const uint32_t am = (uint32_t)__ballot(my_rm != 0) & 0xffu;
 #pragma unroll
-    for (int j = 0; j < 2; j++) {  // rows without any active site: zero-fill where needed
+    for (int j = 0; j < 2; j++) {  // rows without any active site: zero-fill the pixels that may hold data
       const int rr = wv * 2 + j, oy = y0 + rr;
       const bool active = (am >> rr) & 1u;
-      if (hsel != 0) continue;  // the tile's bookkeeping belongs to its pass-0 unit
-      if (!active && was[j] && oy < H && ox < W) {
+      // The tile's zero-fill and bookkeeping belong to its pass-0 unit, for ALL the output channels: the units of a tile run on different workgroups in
+      // either order, and a pass that read the written masks after pass 0 had updated them would find nothing stale.
+      if (hsel != 0) continue;
+      if (!active && ((rd_held(row_dirty, was[j]) >> px) & 1u) && oy < H && ox < W) {
         uint4* dst = reinterpret_cast<uint4*>(y + (((int64_t)b * H + oy) * W + ox) * COUT);
 #pragma unroll 1
         for (int ch = kb; ch < COUT / 8; ch += 2) dst[ch] = make_uint4(0, 0, 0, 0);
       }
-      if (row_dirty != nullptr && oy < H && lane == 0 && was[j] != active) row_dirty[((int64_t)b * H + oy) * tiles_x + tx] = active ? 1 : 0;
+      if (oy < H && lane == 0) rd_store(row_dirty, ((int64_t)b * H + oy) * tiles_x + tx, was[j], bal[j]);
     }
     if (am == 0) continue;  // uniform over the workgroup
     if constexpr (PACK) {
@@ -493,23 +494,28 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_ldsx(const uint16_t* __restr
         default: PNX_PIX_X(4); break;
       }
 #undef PNX_PIX_X
-      // inactive pixels of active rows: the row form stores their zeros with the row; here they are zeroed (this pass's 128 channels) where the row
-      // segment may hold stale values (row_dirty; without one, always).  After the pass's stores: a store ahead of the tap loop's loads would stall them.
+      // inactive pixels of active rows: the row form stores their zeros with the row; here the pass-0 unit zeroes, for all COUT channels, those that went
+      // stale -- written before this launch (row_dirty; without one, all of them) and inactive now.  Other bytes than any pass's consumers write, so no order
+      // between the units is needed.  After the pass's stores: a store ahead of the tap loop's loads would stall them.
       // Lane L writes chunk L & 15 of pixel c0 + (L >> 4): a store instruction covers 4 consecutive pixels x 256 bytes = 8 complete 128-byte lines.
+      if (hsel != 0) continue;
       int l = lane;
       asm volatile("" : "+v"(l));  // opaque: the per-lane offset is recomputed here, not held across the tap loop
       const uint32_t cols = W - x0 >= 32 ? 0xffffffffu : (1u << (W - x0)) - 1u;  // columns inside the image
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const int rr = wvu * 2 + j;
-        const uint32_t idle = ~bal[j] & cols;  // inactive pixels of the row (wave-uniform)
-        if (!((am >> rr) & 1u) || !was[j] || y0 + rr >= H || idle == 0) continue;
-        char* const row = reinterpret_cast<char*>(y + t0) + (uint32_t)(rr * W * COUT * 2 + hsel * 256);
+        const uint32_t stale = rd_held(row_dirty, was[j]) & ~bal[j] & cols;  // wave-uniform
+        if (!((am >> rr) & 1u) || y0 + rr >= H || stale == 0) continue;
+        char* const row = reinterpret_cast<char*>(y + t0) + (uint32_t)(rr * W * COUT * 2);
 #pragma unroll 1
         for (int c0 = 0; c0 < 32; c0 += 4) {
-          if (((idle >> c0) & 15u) == 0) continue;
+          if (((stale >> c0) & 15u) == 0) continue;
           const int p = c0 + (l >> 4);
-          if ((idle >> p) & 1u) *reinterpret_cast<uint4*>(row + (uint32_t)(p * COUT * 2 + (l & 15) * 16)) = make_uint4(0, 0, 0, 0);
+          if ((stale >> p) & 1u) {
+#pragma unroll
+            for (int h = 0; h < NH; h++) *reinterpret_cast<uint4*>(row + (uint32_t)(p * COUT * 2 + h * 256 + (l & 15) * 16)) = make_uint4(0, 0, 0, 0);
+          }
         }
       }
       continue;

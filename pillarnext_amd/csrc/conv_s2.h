@@ -133,7 +133,7 @@ template <int CIN, int COUT, int NP = 1>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, const uint4* __restrict__ wfrag,
                                                     const uint4* __restrict__ wfrag2, const float* __restrict__ bias,
                                                     const uint8_t* __restrict__ mask, uint16_t* __restrict__ y, int B, int H, int W, int Ho, int Wo,
-                                                    int relu, uint8_t* __restrict__ row_dirty, int slot, const uint16_t* __restrict__ x3 = nullptr,
+                                                    int relu, RowDirty row_dirty, int slot, const uint16_t* __restrict__ x3 = nullptr,
                                                     const uint4* __restrict__ wfrag3 = nullptr) {
   static_assert(CIN % 64 == 0 && (COUT == 128 || COUT == 256), "64-channel input slabs; 4 groups of 32 or of 64 output channels");
   // Round 6: with 128 output channels the waves were 2 row groups x 2 groups of 64 channels, i.e. at most TWO rows per wave -- one 1 KiB weight fragment from
@@ -160,27 +160,27 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restric
     const int b = (int)(tile / ((int64_t)tiles_x * tiles_y));
     const int x0 = tx * 32, y0 = ty * TH;
     const int ox = x0 + px;
-    bool was = true;
+    uint32_t was = 0xffffffffu, bal;  // written mask of this wave's row segment before the launch (pnx.h: row_dirty), its active pixels now
     {  // active sites: wave wv looks at output row wv of the tile
       const int oy = y0 + wv;
       const bool a = ox < Wo && oy < Ho && (mask == nullptr || mask[((int64_t)b * Ho + oy) * Wo + ox] != 0);
-      if (row_dirty != nullptr && oy < Ho) was = __builtin_amdgcn_readfirstlane((int)row_dirty[((int64_t)b * Ho + oy) * tiles_x + tx]) != 0;
-      const uint32_t bal = (uint32_t)__ballot(a);
+      if (oy < Ho) was = (uint32_t)__builtin_amdgcn_readfirstlane((int)rd_load(row_dirty, ((int64_t)b * Ho + oy) * tiles_x + tx));
+      bal = (uint32_t)__ballot(a);
       if (lane == 0) s_rowmask[wv] = bal;
     }
     __syncthreads();  // row masks visible; everybody is done reading the previous tile's s_in
     next = sched_next(s_next, it, slot, tile);
     const uint32_t my_rm = s_rowmask[lane & 3];
     const uint32_t am = (uint32_t)__ballot(my_rm != 0) & 0xfu;
-    {  // a row without any active site: zero-fill where needed
+    {  // a row without any active site: zero-fill the pixels that may hold data; an active row is stored whole, so its written mask is its row mask
       const int oy = y0 + wv;
       const bool active = (am >> wv) & 1u;
-      if (!active && was && oy < Ho && ox < Wo) {
+      if (!active && ((rd_held(row_dirty, was) >> px) & 1u) && oy < Ho && ox < Wo) {
         uint4* dst = reinterpret_cast<uint4*>(y + (((int64_t)b * Ho + oy) * Wo + ox) * COUT * YS);
 #pragma unroll 1
         for (int ch = kb; ch < COUT * YS / 8; ch += 2) dst[ch] = make_uint4(0, 0, 0, 0);
       }
-      if (row_dirty != nullptr && oy < Ho && lane == 0 && was != active) row_dirty[((int64_t)b * Ho + oy) * tiles_x + tx] = active ? 1 : 0;
+      if (oy < Ho && lane == 0) rd_store(row_dirty, ((int64_t)b * Ho + oy) * tiles_x + tx, was, bal);
     }
     if (am == 0) continue;  // uniform over the workgroup
     int nr = 0;
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const uint16_t* __restric
 
 template <int CIN, int COUT, int NP>
 int launch_s2(PnxPieces<NP> x, PnxPieces<NP> wfrag, const float* bias, const uint8_t* mask, void* y, int B, int H, int W, int Ho, int Wo, int relu,
-              uint8_t* row_dirty, hipStream_t st) {
+              RowDirty row_dirty, hipStream_t st) {
   const int slot = mask != nullptr ? next_sched_slot() : -1;
   int64_t nb = (int64_t)B * ((Ho + S2_TH - 1) / S2_TH) * ((Wo + 31) / 32);
   if (nb > 512) nb = 512;  // resident workgroups: 2 per CU (LDS and registers)

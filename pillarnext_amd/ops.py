@@ -830,9 +830,34 @@ def conv3x3_smallk_wgrad(x, dy, want_bias=True):
 
 
 def conv3x3_workspace(batch, cout, ho, wo, device, dtype=torch.bfloat16):
-    """A persistent (output buffer, row_dirty flags) pair for conv3x3_masked(out=...): both start zeroed (pnx.h: row_dirty)."""
+    """A persistent (output buffer, row_dirty flags) pair for conv3x3_masked(out=...): both start zeroed (pnx.h: row_dirty).  The flags are the
+    (B, ho, segs) uint8 view at offset 0 of the row_dirty array; the written masks the kernels keep behind them are row_dirty_written(flags)."""
     y = torch.zeros((batch, cout, ho, wo), dtype=dtype, device=device).contiguous(memory_format=torch.channels_last)
-    return y, torch.zeros((batch, ho, (wo + 31) // 32), dtype=torch.uint8, device=device)
+    segs = (wo + 31) // 32
+    arr = torch.zeros((row_dirty_bytes(batch, ho, wo),), dtype=torch.uint8, device=device)
+    return y, arr[: batch * ho * segs].view(batch, ho, segs)
+
+
+def row_dirty_bytes(batch, ho, wo):
+    """Bytes of the row_dirty array of a (batch, *, ho, wo) output buffer: flag bytes, then one uint32 written mask per row segment (pnx.h)."""
+    return int(lib().pnx_conv3x3_row_dirty_bytes(batch, ho, wo))
+
+
+def _row_dirty_check(flags, batch, ho, wo):
+    """The flags must be the head of an array of row_dirty_bytes: the kernels read and write the written masks behind them."""
+    need = row_dirty_bytes(batch, ho, wo)
+    if (flags.dtype != torch.uint8 or tuple(flags.shape) != (batch, ho, (wo + 31) // 32) or not flags.is_contiguous()
+            or flags.untyped_storage().nbytes() - flags.storage_offset() < need):
+        raise PnxError(f"conv3x3: row_dirty must be the flags of conv3x3_workspace ({need} bytes: flags + written masks)")
+
+
+def row_dirty_written(flags, wo):
+    """The written masks behind the flags of a conv3x3_workspace pair: int32 (B, ho, segs), bit p = pixel p of the segment may hold data."""
+    B, ho, segs = flags.shape
+    _row_dirty_check(flags, B, ho, wo)
+    off = (B * ho * segs + 255) // 256 * 256     # pnx.h: the flag bytes, padded to a multiple of 256
+    whole = torch.empty(0, dtype=torch.uint8, device=flags.device).set_(flags.untyped_storage(), flags.storage_offset(), (row_dirty_bytes(B, ho, wo),))
+    return whole[off: off + 4 * B * ho * segs].view(torch.int32).view(B, ho, segs)
 
 
 def conv_tile_rows(cin, cout, stride=1):
@@ -882,6 +907,8 @@ def conv3x3_masked(x, wfrag, bias, cout, stride=1, mask=None, residual=None, rel
     tiles = conv_tile_list(mask, ...) of the same mask (stride 1 only): walk the listed tiles instead of all of them."""
     B, H, W, ci, _, Ho, Wo = _conv3x3_dims(x, wfrag, cout, stride, mask, residual, out, cuda=True)
     y, dirty = out if out is not None else (torch.empty((B, cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last), None)
+    if dirty is not None:   # the launch reads and writes the written masks behind the flags: an array of the flags alone is no longer valid
+        _row_dirty_check(dirty, B, Ho, Wo)
     tl, tc = tiles if tiles is not None else (None, None)
     check(_conv_fn("conv3x3", x.dtype)(ptr(x), ptr(wfrag), ptr(bias), ptr(residual), ptr(mask), ptr(y), B, H, W, ci, cout, stride, 1 if relu else 0,
                                        ptr(dirty), ptr(tl), ptr(tc), stream_ptr()), "pnx_conv3x3")

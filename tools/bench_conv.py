@@ -12,15 +12,16 @@ ap.add_argument("--density", type=float, default=1.0); ap.add_argument("--iters"
 ap.add_argument("--stride", type=int, default=1); ap.add_argument("--tiles", action="store_true"); ap.add_argument("--miopen", action="store_true"); ap.add_argument("--res", action="store_true")
 ap.add_argument("--dilate", action="store_true", help="with --lidar: the stage's active set after its entry SparseConv2d (3x3 dilation of the pooled occupancy) -- what the stage's blocks run on")
 ap.add_argument("--data", default="randn", help="randn | relu (post-ReLU: half the values zero) | zero -- operand toggling sets the power draw and with it the clock")
+ap.add_argument("--alternate", action="store_true", help="with --lidar, stride 1 and a workspace: the launches alternate between the masks of two consecutive frame batches -- what launches 1 to 3 of a stage see from step to step; without it every launch rewrites the buffer with the same mask (launches 4 and 5)")
 ap.add_argument("--lidar", type=int, default=-1, help="backbone stage (0..3): active sites = the C2 sweep occupancy pooled to that stage (sets --hw)")
 a = ap.parse_args()
 lidar_mask = None
-if a.lidar >= 0:
-    import numpy as np
+def stage_mask(frame0):
+    """(input occupancy, output mask) of backbone stage a.lidar on the C2 sweep frames frame0 .. frame0 + batch - 1"""
     from pillarnext_amd import synth
     cfg = synth.CONFIGS["C2"]
     r, v = cfg["pc_range"], cfg["voxel_size"]
-    pts = torch.from_numpy(synth.make_batch("C2", a.batch, "sweep")).cuda()
+    pts = torch.from_numpy(synth.make_batch("C2", a.batch, "sweep", frame0=frame0)).cuda()
     nx, ny = int(round((r[3] - r[0]) / v[0])), int(round((r[4] - r[1]) / v[1]))
     bi, xi, yi = pts[:, 0].long(), ((pts[:, 1] - r[0]) / v[0]).floor().long(), ((pts[:, 2] - r[1]) / v[1]).floor().long()
     ok = (xi >= 0) & (xi < nx) & (yi >= 0) & (yi < ny)
@@ -31,9 +32,10 @@ if a.lidar >= 0:
         occ_in, occ = occ, ops.mask_pool3(occ, 2)
     if a.dilate:
         occ = ops.mask_pool3(occ, 1)
+    return (occ if a.stride == 1 else occ_in), occ
+if a.lidar >= 0:
+    occ_in, occ = stage_mask(0)
     lidar_mask, a.hw = occ, occ.shape[-1]
-    if a.stride == 1:
-        occ_in = occ
     seg = torch.nn.functional.max_pool1d(occ.float(), 32, 32, ceil_mode=True)
     print(f"stage {a.lidar}: {a.hw}^2, active sites {occ.float().mean().item():.3f}, active 32-px row segments {seg.mean().item():.3f}")
 g = torch.Generator(device="cuda").manual_seed(0)
@@ -58,7 +60,25 @@ tiles = None
 if a.tiles and ws is not None and a.stride == 1:
     tiles = ops.conv_tile_list(mask, [ws[1]], ops.conv_tile_rows(a.cin, a.cout, 1))
     print(f"tile list: {int(tiles[1].item())} of {tiles[0].numel()} tiles")
+alt = None
+if a.alternate:
+    assert lidar_mask is not None and ws is not None and a.stride == 1 and not a.miopen, "--alternate: --lidar, stride 1, a workspace"
+    occ2 = stage_mask(a.batch)[1]
+    alt = [(x, mask, None), ((x * occ2.unsqueeze(1)).contiguous(memory_format=torch.channels_last), occ2, None)]
+    if a.tiles:   # lists over both masks' tiles: a tile of the other frame batch holds the rows that went stale
+        both = mask | occ2
+        tl = ops.conv_tile_list(both, [], ops.conv_tile_rows(a.cin, a.cout, 1))
+        alt = [(xx, mm, tl) for xx, mm, _ in alt]
+        print(f"alternating tile list: {int(tl[1].item())} of {tl[0].numel()} tiles")
+    gone = ((mask == 1) & (occ2 == 0)).float().sum().item() / max(occ2.float().sum().item(), 1.0)
+    print(f"alternate: pixels active in one frame batch and not in the next, per active pixel: {gone:.3f}")
+n_run = 0
 def run():
+    global n_run
+    if alt is not None:
+        xx, mm, tl = alt[n_run & 1]
+        n_run += 1
+        return ops.conv3x3_masked(xx, wf, bias, a.cout, 1, mm, res, True, out=ws, tiles=tl)
     if a.miopen:
         y = torch.nn.functional.conv2d(x, wcl, None, a.stride, 1)
         return ops.bias_act_mask_(y, bias, mask, res, True)
