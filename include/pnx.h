@@ -213,6 +213,27 @@ int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t
                                  int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host, const int32_t* cell_coords,
                                  const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* grad_image, void* workspace, size_t workspace_bytes,
                                  pnx_stream_t stream);
+/* The same sampling on the ROWS of an active set instead of a dense map (SingleView.use_sparse_rows): rows (n_rows, channels) fp32 in rank order
+ *   of the set whose index (pnx_sp3_index_build / pnx_sp3_out_index over grid (1, h, w); index_bytes = pnx_sp3_index_bytes) is given.  Sample image,
+ *   position, clamped corners and weights are pnx_bilinear_gather's (one device function); a corner is a bit test and a rank in the index: a present
+ *   corner adds weight * rows[rank], an absent one weight * 0, the four terms in the dense kernel's order -- out equals (==) pnx_bilinear_gather on
+ *   the (batch, h, w, channels) map scattered from the rows.  Any channel count; a point whose image index is outside [0, batch) gets a row of +0.
+ *   n = 0 launches nothing; n_rows = 0 (rows may be NULL) samples an empty map.
+ * pnx_sp3_bilinear_gather_backward: grad_rows (n_rows, channels) fp32, FULLY WRITTEN, = pnx_bilinear_gather_backward's grad_image read at
+ *   coords (n_rows, 4) int32 [b, 0, y, x] (16-byte aligned; the set's rows, pnx_sp3_index_coords), bit for bit: the same stable radix sort of
+ *   the point indices by base cell, then per ACTIVE ROW the bounds of the two runs of base cells (y - 1 .. y, x - 1 .. x) by binary search and one
+ *   wave walking them in the dense kernel's order.  Cost follows the points and the rows, not batch * h * w (which must still fit 32-bit keys).  No
+ *   floating-point atomics.  A row whose coords lie outside the map receives +0.  n = 0 zero-fills grad_rows; n_rows = 0 does nothing.
+ *   workspace = pnx_sp3_bilinear_gather_backward_scratch_bytes(n, n_rows) (0 = sizes beyond 32-bit indices). */
+int pnx_sp3_bilinear_gather(const float* rows, int64_t n_rows, int32_t channels, const void* index, size_t index_bytes, int32_t batch, int32_t h,
+                            int32_t w, const float* pos, int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host,
+                            const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* out, int32_t out_ld,
+                            pnx_stream_t stream);
+size_t pnx_sp3_bilinear_gather_backward_scratch_bytes(int64_t n, int64_t n_rows);
+int pnx_sp3_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, const int32_t* coords, int64_t n_rows, int32_t batch, int32_t h, int32_t w,
+                                     int32_t channels, const float* pos, int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host,
+                                     const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* grad_rows, void* workspace,
+                                     size_t workspace_bytes, pnx_stream_t stream);
 
 /* torch_scatter.scatter_max(x, unq_inv, dim=0) over pillars (call sites :43,:180), fp32, values of
  * any sign.  x (n, channels); index (n) int64 in [0,P); out (P, channels); argmax (P, channels) int64 =
@@ -705,7 +726,8 @@ size_t pnx_lazy_decode_bytes(void);
  *   row_of_rank_in[rank] when given), -1 where that site is inactive or outside.  Submanifold layers pass the set's own index, stride 1.
  * pnx_sp3_conv: y (n_out, cout) = relu?(sum over taps and cin of x[map[row][t]][c] * w[t][c][:] + shift (+ residual (n_out, cout))),
  *   fp32 in and out on the fp32 matrix cores, every row reduced in one fixed order (bit-identical run to run).  w_packed is
- *   (T, round_up(cin, 4), round_up(cout, 16)) fp32 = pnx_sp3_packed_weight_floats, zero-padded, BatchNorm scale folded in; cout <= 144.
+ *   (T, round_up(cin, 4), round_up(cout, 16)) fp32 = pnx_sp3_packed_weight_floats, zero-padded, BatchNorm scale folded in; cin <= 1024,
+ *   cout <= 192 (a wave holds ceil(cout / 16) accumulator tiles of 16 x 16).
  * pnx_sp3_dense: out (batch, channels*D, H, W) fp32 zero-filled, then out[b][c*D + z][y][x] = feat[row][c] (x.dense().view(B, C*D, H, W)).
  * Training (gradients of y[o] = sum_t w[:, t, :] . x[map[o][t]]):
  * pnx_sp3_conv_train: pnx_sp3_conv with another fixed summation order, for the training graph (forward and data gradient): every tap is summed

@@ -72,6 +72,11 @@ PROTOTYPES = {
     "pnx_bilinear_gather_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "pnx_bilinear_gather_backward": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, ctypes.POINTER(ctypes.c_float),
                                                     ctypes.POINTER(ctypes.c_float), _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "pnx_sp3_bilinear_gather": (ctypes.c_int, [_vp, _i64, _i32, _vp, _sz, _i32, _i32, _i32, _vp, _i32, ctypes.POINTER(ctypes.c_float),
+                                               ctypes.POINTER(ctypes.c_float), _vp, _vp, _i32, _i64, _vp, _i32, _vp]),
+    "pnx_sp3_bilinear_gather_backward_scratch_bytes": (_sz, [_i64, _i64]),
+    "pnx_sp3_bilinear_gather_backward": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, ctypes.POINTER(ctypes.c_float),
+                                                        ctypes.POINTER(ctypes.c_float), _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
     "pnx_scatter_max_workspace_bytes": (_sz, [_i64, _i64]),
     "pnx_scatter_max": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
     "pnx_scatter_max_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp]),

@@ -9,6 +9,9 @@
 //   pnx_bilinear_gather  SingleView.bilinear_interpolate (mvf_encoder.py:208-246) on a channels-last map
 //   pnx_bilinear_gather_backward  its gradient w.r.t. the map: a stable sort of the points by base cell, then one wave per map cell sums its
 //                        contributions in sorted order (no atomics: deterministic)
+//   pnx_sp3_bilinear_gather, pnx_sp3_bilinear_gather_backward  the same pair on the ROWS of an active set over (batch, 1, h, w) (sparse3d_index.h)
+//                        instead of a dense map: equal to the dense pair on the scattered map / at the active cells, at a cost that follows the
+//                        points and the rows, not the grid
 //
 // Grouping without sorting a point, like the pillar reader's rank outputs: torch.unique(dim=0) over [b, c0, c1(, c2)] rows orders the cells
 // lexicographically = by the linear key ((b*g0 + c0)*g1 + c1)(*g2 + c2); every occupied key sets one bit of a key-order bitmap, a popcount
@@ -25,6 +28,8 @@
 #include "pnx_scan.h"
 
 namespace {
+
+#include "sparse3d_index.h"  // the index of an active set: pnx_sp3_bilinear_gather looks its corners up in one
 
 struct GroupGeomDev {
   float mn[3], vs[3];
@@ -363,6 +368,45 @@ __global__ __launch_bounds__(kBlock) void k_bilinear_bounds(const uint32_t* __re
 
 constexpr int kBilChunk = 4;  // channels per lane and pass: 256 channels per walk of the cell's points
 
+// the terms cell (y, x) receives from the sorted positions [s, e), added to acc in that order: channels c0 + lane + 64 k.  The one walk both the
+// dense gradient (a wave per map cell) and the gradient of a set's rows (a wave per active row, pnx_sp3_bilinear_gather_backward) run.
+__device__ __forceinline__ void bil_grad_run(float (&acc)[kBilChunk], int s, int e, int x, int y, int c0, int lane, const float* __restrict__ g, int ldg,
+                                             int H, int W, int C, const float* __restrict__ pos, int ldp, float mn0, float mn1, float vs0, float vs1,
+                                             float inv_ds, const int32_t* __restrict__ order) {
+  for (int i0 = s; i0 < e; i0 += 64) {
+    // one point per lane: which of its corners are this cell, and their weights
+    int p = 0;
+    unsigned m = 0;
+    BilSample sm = {};
+    if (i0 + lane < e) {
+      p = order[i0 + lane];
+      sm = bil_sample(pos + (int64_t)p * ldp, mn0, mn1, vs0, vs1, inv_ds, H, W);
+      m = (sm.y0 == y && sm.x0 == x ? 1u : 0u) | (sm.y1 == y && sm.x0 == x ? 2u : 0u) | (sm.y0 == y && sm.x1 == x ? 4u : 0u) |
+          (sm.y1 == y && sm.x1 == x ? 8u : 0u);
+    }
+    unsigned long long todo = __ballot(m != 0);
+    while (todo) {
+      const int j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const int pj = __builtin_amdgcn_readlane(p, j);
+      const unsigned mj = (unsigned)__builtin_amdgcn_readlane((int)m, j);
+      const float* row = g + (int64_t)pj * ldg + c0 + lane;
+      float gv[kBilChunk];
+#pragma unroll
+      for (int k = 0; k < kBilChunk; k++) gv[k] = c0 + lane + 64 * k < C ? row[64 * k] : 0.f;
+      const float w4[4] = {sm.wa, sm.wb, sm.wc, sm.wd};
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (mj >> q & 1) {  // wave-uniform
+          const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w4[q]), j));
+#pragma unroll
+          for (int k = 0; k < kBilChunk; k++) acc[k] = __fadd_rn(acc[k], __fmul_rn(w, gv[k]));
+        }
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_bilinear_grad(const float* __restrict__ g, int ldg, int B, int H, int W, int C, const float* __restrict__ pos,
                                                           int ldp, float mn0, float mn1, float vs0, float vs1, float inv_ds,
                                                           const int32_t* __restrict__ order, const int32_t* __restrict__ start,
@@ -379,43 +423,93 @@ __global__ __launch_bounds__(kBlock) void k_bilinear_grad(const float* __restric
       for (int r = 0; r < 2; r++) {
         if (y - 1 + r < 0) continue;
         const int row0 = cell - x - (1 - r) * W;  // key of (b, y - 1 + r, 0)
-        const int s = start[row0 + max(x - 1, 0)], e = start[row0 + x + 1];
-        for (int i0 = s; i0 < e; i0 += 64) {
-          // one point per lane: which of its corners are this cell, and their weights
-          int p = 0;
-          unsigned m = 0;
-          BilSample sm = {};
-          if (i0 + lane < e) {
-            p = order[i0 + lane];
-            sm = bil_sample(pos + (int64_t)p * ldp, mn0, mn1, vs0, vs1, inv_ds, H, W);
-            m = (sm.y0 == y && sm.x0 == x ? 1u : 0u) | (sm.y1 == y && sm.x0 == x ? 2u : 0u) | (sm.y0 == y && sm.x1 == x ? 4u : 0u) |
-                (sm.y1 == y && sm.x1 == x ? 8u : 0u);
-          }
-          unsigned long long todo = __ballot(m != 0);
-          while (todo) {
-            const int j = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const int pj = __builtin_amdgcn_readlane(p, j);
-            const unsigned mj = (unsigned)__builtin_amdgcn_readlane((int)m, j);
-            const float* row = g + (int64_t)pj * ldg + c0 + lane;
-            float gv[kBilChunk];
-#pragma unroll
-            for (int k = 0; k < kBilChunk; k++) gv[k] = c0 + lane + 64 * k < C ? row[64 * k] : 0.f;
-            const float w4[4] = {sm.wa, sm.wb, sm.wc, sm.wd};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-              if (mj >> q & 1) {  // wave-uniform
-                const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w4[q]), j));
-#pragma unroll
-                for (int k = 0; k < kBilChunk; k++) acc[k] = __fadd_rn(acc[k], __fmul_rn(w, gv[k]));
-              }
-            }
-          }
-        }
+        bil_grad_run(acc, start[row0 + max(x - 1, 0)], start[row0 + x + 1], x, y, c0, lane, g, ldg, H, W, C, pos, ldp, mn0, mn1, vs0, vs1, inv_ds, order);
       }
 #pragma unroll
       for (int k = 0; k < kBilChunk; k++)
         if (c0 + lane + 64 * k < C) gi[(int64_t)cell * C + c0 + lane + 64 * k] = acc[k];
+    }
+  }
+}
+
+// ---- the same sampling and gradient on the ROWS of an active set over (batch, 1, h, w) (sparse3d_index.h) instead of a dense map: a corner is a bit
+// test and a rank; an absent corner reads 0, so the forward equals k_bilinear<float> on the map scattered from the rows and the gradient equals
+// k_bilinear_grad's read at the active cells, bit for bit (the same products, added in the same order).
+__global__ __launch_bounds__(kBlock) void k_sp3_bilinear(const float* __restrict__ rows, int64_t n_rows, Sp3Grid G, const uint32_t* __restrict__ bitmap,
+                                                         const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk, int C,
+                                                         const float* __restrict__ pos, int ldp, float mn0, float mn1, float vs0, float vs1,
+                                                         const int32_t* __restrict__ cell_coords, const int64_t* __restrict__ inv, float inv_ds, int64_t n,
+                                                         float* __restrict__ out, int ldo) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
+  for (int64_t p = wave; p < n; p += nwaves) {
+    const int b = cell_coords[inv[p] * 3];
+    const BilSample s = bil_sample(pos + p * ldp, mn0, mn1, vs0, vs1, inv_ds, G.H, G.W);
+    const bool okb = b >= 0 && b < G.B;
+    const int ys[4] = {s.y0, s.y1, s.y0, s.y1}, xs[4] = {s.x0, s.x0, s.x1, s.x1};  // corners a, b, c, d
+    const float* src[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      src[q] = nullptr;
+      if (okb) {
+        const int64_t k = sp3_key(G, b, 0, ys[q], xs[q]);
+        if ((bitmap[k >> 5] >> (k & 31)) & 1u) {
+          const int64_t r = sp3_rank(bitmap, pre, blk, k);
+          if (r < n_rows) src[q] = rows + r * C;  // an index that does not belong to these rows reads nothing
+        }
+      }
+    }
+    for (int c = lane; c < C; c += 64) {
+      float v = __fmul_rn(src[0] ? src[0][c] : 0.f, s.wa);
+      v = __fadd_rn(v, __fmul_rn(src[1] ? src[1][c] : 0.f, s.wb));
+      v = __fadd_rn(v, __fmul_rn(src[2] ? src[2][c] : 0.f, s.wc));
+      v = __fadd_rn(v, __fmul_rn(src[3] ? src[3][c] : 0.f, s.wd));
+      out[p * ldo + c] = okb ? v : 0.f;
+    }
+  }
+}
+
+// seg[4 r ..] = the two runs of sorted positions active row r = (b, y, x) receives from: [lower bound of key (b, y', max(x - 1, 0)), lower bound of
+// key (b, y', x) + 1) for y' = y - 1, y -- the entries start[] holds for that cell in the dense gradient; an empty run where y' < 0 or the row's
+// coords lie outside the map
+__global__ __launch_bounds__(kBlock) void k_sp3_bilinear_bounds(const uint32_t* __restrict__ skey, int n, const int32_t* __restrict__ coords, int64_t n_rows,
+                                                                int B, int H, int W, int32_t* __restrict__ seg) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= 4 * n_rows) return;
+  const int64_t row = e >> 2;
+  const int r = (int)(e >> 1) & 1, hi_end = (int)e & 1;
+  const int4 c = *reinterpret_cast<const int4*>(coords + 4 * row);
+  const int b = c.x, y = c.z, x = c.w;
+  int lo = 0;
+  if (b >= 0 && b < B && y >= 0 && y < H && x >= 0 && x < W && y - 1 + r >= 0) {
+    const uint32_t k = (uint32_t)((b * H + y - 1 + r) * W + (hi_end ? x + 1 : max(x - 1, 0)));
+    int hi = n;
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (skey[mid] < k) lo = mid + 1;
+      else hi = mid;
+    }
+  }
+  seg[e] = lo;
+}
+
+__global__ __launch_bounds__(kBlock) void k_sp3_bilinear_grad(const float* __restrict__ g, int ldg, const int32_t* __restrict__ coords, int64_t n_rows, int H,
+                                                              int W, int C, const float* __restrict__ pos, int ldp, float mn0, float mn1, float vs0,
+                                                              float vs1, float inv_ds, const int32_t* __restrict__ order, const int32_t* __restrict__ seg,
+                                                              float* __restrict__ grows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
+  for (int64_t row = wave; row < n_rows; row += nwaves) {
+    const int x = coords[4 * row + 3], y = coords[4 * row + 2];
+    for (int c0 = 0; c0 < C; c0 += 64 * kBilChunk) {
+      float acc[kBilChunk];
+#pragma unroll
+      for (int k = 0; k < kBilChunk; k++) acc[k] = 0.f;
+      for (int r = 0; r < 2; r++)
+        bil_grad_run(acc, seg[4 * row + 2 * r], seg[4 * row + 2 * r + 1], x, y, c0, lane, g, ldg, H, W, C, pos, ldp, mn0, mn1, vs0, vs1, inv_ds, order);
+#pragma unroll
+      for (int k = 0; k < kBilChunk; k++)
+        if (c0 + lane + 64 * k < C) grows[row * C + c0 + lane + 64 * k] = acc[k];
     }
   }
 }
@@ -433,6 +527,30 @@ BilGradWs bilgrad_carve(void* ws, int64_t n, int64_t cells) {
   w.skey = c.take<uint32_t>((size_t)n);
   w.order = c.take<int32_t>((size_t)n);
   w.start = c.take<int32_t>((size_t)cells + 1);
+  w.sort_bytes = 0;
+  if (n > 0) {
+    rocprim::counting_iterator<int32_t> iota(0);
+    (void)rocprim::radix_sort_pairs(nullptr, w.sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, iota, (int32_t*)nullptr, (size_t)n, 0u, 32u,
+                                    (hipStream_t) nullptr);
+  }
+  w.sort = c.take<char>(w.sort_bytes);
+  w.bytes = c.used() + 256;
+  return w;
+}
+// the workspace of pnx_sp3_bilinear_gather_backward: the same sort, then four segment bounds per active row instead of one per map cell
+struct Sp3BilGradWs {
+  uint32_t *key, *skey;
+  int32_t *order, *seg;
+  void* sort;
+  size_t sort_bytes, bytes;
+};
+Sp3BilGradWs sp3_bilgrad_carve(void* ws, int64_t n, int64_t n_rows) {
+  PnxCarver c(ws);
+  Sp3BilGradWs w;
+  w.key = c.take<uint32_t>((size_t)n);
+  w.skey = c.take<uint32_t>((size_t)n);
+  w.order = c.take<int32_t>((size_t)n);
+  w.seg = c.take<int32_t>((size_t)n_rows * 4);
   w.sort_bytes = 0;
   if (n > 0) {
     rocprim::counting_iterator<int32_t> iota(0);
@@ -585,6 +703,75 @@ int pnx_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, int32_t
   if (nb > 16384) nb = 16384;
   k_bilinear_grad<<<(unsigned)nb, kBlock, 0, st>>>(grad_out, grad_ld, batch, h, w, channels, pos, pos_ld, mn0, mn1, vs0, vs1, inv_ds, ws.order, ws.start,
                                                    grad_image);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+int pnx_sp3_bilinear_gather(const float* rows, int64_t n_rows, int32_t channels, const void* index, size_t index_bytes, int32_t batch, int32_t h,
+                            int32_t w, const float* pos, int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host,
+                            const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* out, int32_t out_ld,
+                            pnx_stream_t stream) {
+  PNX_REQUIRE(pos_min2_host && pos_voxel2_host && batch > 0 && h > 0 && w > 0 && channels > 0 && pos_ld >= 2 && out_ld >= channels && n >= 0 &&
+                  n_rows >= 0 && n_rows < ((int64_t)1 << 31) && (n == 0 || (pos && cell_coords && unq_inv && out)) && (n_rows == 0 || rows),
+              PNX_ERR_INVALID, "pnx_sp3_bilinear_gather: bad arguments");
+  PNX_REQUIRE(ds_rate >= 1 && (ds_rate & (ds_rate - 1)) == 0, PNX_ERR_UNSUPPORTED, "pnx_sp3_bilinear_gather: ds_rate %d is not a power of two", ds_rate);
+  const int32_t grid3[3] = {1, h, w};
+  Sp3Grid G;
+  Sp3Index ix;
+  int rc = sp3_grid(batch, grid3, &G);
+  if (rc == PNX_OK) rc = sp3_index_args(G, const_cast<void*>(index), index_bytes, &ix);
+  if (rc != PNX_OK) return rc;
+  if (n == 0) return PNX_OK;
+  int64_t nb = (n + 3) / 4;
+  if (nb > 8192) nb = 8192;
+  k_sp3_bilinear<<<(unsigned)nb, kBlock, 0, (hipStream_t)stream>>>(rows, n_rows, G, ix.bitmap, ix.pre, ix.blk, channels, pos, pos_ld, pos_min2_host[0],
+                                                                 pos_min2_host[1], pos_voxel2_host[0], pos_voxel2_host[1], cell_coords, unq_inv,
+                                                                 1.0f / (float)ds_rate, n, out, out_ld);
+  PNX_LAUNCH_CHECK();
+  return PNX_OK;
+}
+
+size_t pnx_sp3_bilinear_gather_backward_scratch_bytes(int64_t n, int64_t n_rows) {
+  if (n < 0 || n >= ((int64_t)1 << 31) - 64 || n_rows < 0 || n_rows >= ((int64_t)1 << 29)) return 0;
+  return sp3_bilgrad_carve(nullptr, n, n_rows).bytes;
+}
+
+int pnx_sp3_bilinear_gather_backward(const float* grad_out, int32_t grad_ld, const int32_t* coords, int64_t n_rows, int32_t batch, int32_t h, int32_t w,
+                                     int32_t channels, const float* pos, int32_t pos_ld, const float* pos_min2_host, const float* pos_voxel2_host,
+                                     const int32_t* cell_coords, const int64_t* unq_inv, int32_t ds_rate, int64_t n, float* grad_rows, void* workspace,
+                                     size_t workspace_bytes, pnx_stream_t stream) {
+  PNX_REQUIRE(pos_min2_host && pos_voxel2_host && batch > 0 && h > 0 && w > 0 && channels > 0 && pos_ld >= 2 && n >= 0 && n_rows >= 0 &&
+                  (n == 0 || (grad_out && pos && cell_coords && unq_inv)) && (n_rows == 0 || (grad_rows && coords && ((uintptr_t)coords & 15) == 0)),
+              PNX_ERR_INVALID, "pnx_sp3_bilinear_gather_backward: bad arguments");
+  PNX_REQUIRE(grad_ld >= channels, PNX_ERR_INVALID, "pnx_sp3_bilinear_gather_backward: grad_ld %d < %d channels", grad_ld, channels);
+  PNX_REQUIRE(ds_rate >= 1 && (ds_rate & (ds_rate - 1)) == 0, PNX_ERR_UNSUPPORTED, "pnx_sp3_bilinear_gather_backward: ds_rate %d is not a power of two",
+              ds_rate);
+  PNX_REQUIRE(bilgrad_sizes_ok(n, batch, h, w) && n_rows < ((int64_t)1 << 29), PNX_ERR_UNSUPPORTED,
+              "pnx_sp3_bilinear_gather_backward: %lld points / %lld rows / %d x %d x %d cells exceed 32-bit indices", (long long)n, (long long)n_rows, batch,
+              h, w);
+  if (n_rows == 0) return PNX_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    PNX_CHECK_HIP(hipMemsetAsync(grad_rows, 0, (size_t)n_rows * channels * sizeof(float), st));
+    return PNX_OK;
+  }
+  const Sp3BilGradWs ws = sp3_bilgrad_carve(workspace, n, n_rows);
+  PNX_CHECK_WORKSPACE(workspace, workspace_bytes, ws.bytes, "pnx_sp3_bilinear_gather_backward");
+  const int cells = batch * h * w;
+  const float inv_ds = 1.0f / (float)ds_rate;
+  const float mn0 = pos_min2_host[0], mn1 = pos_min2_host[1], vs0 = pos_voxel2_host[0], vs1 = pos_voxel2_host[1];
+  k_bilinear_keys<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, st>>>(batch, h, w, pos, pos_ld, mn0, mn1, vs0, vs1, cell_coords, unq_inv, inv_ds, n, ws.key);
+  PNX_LAUNCH_CHECK();
+  unsigned bits = 1;
+  while (bits < 32 && ((uint32_t)1 << bits) <= (uint32_t)cells) bits++;  // 2^bits > cells: the sentinel key of a point outside the batch sorts last
+  size_t sort_bytes = ws.sort_bytes;
+  rocprim::counting_iterator<int32_t> iota(0);
+  PNX_CHECK_HIP(rocprim::radix_sort_pairs(ws.sort, sort_bytes, (const uint32_t*)ws.key, ws.skey, iota, ws.order, (size_t)n, 0u, bits, st));
+  k_sp3_bilinear_bounds<<<(unsigned)((4 * n_rows + kBlock - 1) / kBlock), kBlock, 0, st>>>(ws.skey, (int)n, coords, n_rows, batch, h, w, ws.seg);
+  int64_t nb = (n_rows + 3) / 4;
+  if (nb > 16384) nb = 16384;
+  k_sp3_bilinear_grad<<<(unsigned)nb, kBlock, 0, st>>>(grad_out, grad_ld, coords, n_rows, h, w, channels, pos, pos_ld, mn0, mn1, vs0, vs1, inv_ds, ws.order,
+                                                       ws.seg, grad_rows);
   PNX_LAUNCH_CHECK();
   return PNX_OK;
 }

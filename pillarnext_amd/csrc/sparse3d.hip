@@ -37,41 +37,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct Sp3Grid {
-  int B, D, H, W;
-};
-
-struct Sp3Index {
-  uint32_t* bitmap;
-  uint32_t* pre;
-  uint32_t* blk;
-  int64_t nwords;
-  int nblk;
-  size_t bytes;
-};
-
-Sp3Index sp3_carve(void* base, const Sp3Grid& g) {
-  Sp3Index r;
-  const int64_t cells = (int64_t)g.B * g.D * g.H * g.W;
-  r.nwords = (cells + 31) >> 5;
-  r.nblk = (int)((r.nwords + PNX_SCAN_ITEMS - 1) / PNX_SCAN_ITEMS);
-  PnxCarver c(base);
-  r.bitmap = c.take<uint32_t>((size_t)r.nwords);
-  r.pre = c.take<uint32_t>((size_t)r.nwords);
-  r.blk = c.take<uint32_t>((size_t)r.nblk + 1);
-  r.bytes = c.used();
-  return r;
-}
-
-int sp3_grid(int32_t batch, const int32_t* grid3, Sp3Grid* g) {
-  PNX_REQUIRE(grid3 != nullptr, PNX_ERR_INVALID, "sparse3d: grid is NULL");
-  PNX_REQUIRE(batch >= 0 && grid3[0] >= 1 && grid3[1] >= 1 && grid3[2] >= 1, PNX_ERR_INVALID, "sparse3d: bad grid %d x (%d, %d, %d)", batch,
-              grid3[0], grid3[1], grid3[2]);
-  const int64_t cells = (int64_t)batch * grid3[0] * grid3[1] * grid3[2];
-  PNX_REQUIRE(cells < ((int64_t)1 << 36), PNX_ERR_UNSUPPORTED, "sparse3d: %lld grid cells (at most 2^36)", (long long)cells);
-  g->B = batch, g->D = grid3[0], g->H = grid3[1], g->W = grid3[2];
-  return PNX_OK;
-}
+#include "sparse3d_index.h"  // Sp3Grid, Sp3Index, sp3_carve, sp3_grid, sp3_index_args, sp3_key, sp3_rank
 
 // output extent (n + 2 pad - k) / s + 1 per axis; fills o and returns PNX_OK, or an error for a geometry without outputs
 int sp3_conv_geom(const Sp3Grid& in, const int32_t* k3, const int32_t* s3, const int32_t* p3, Sp3Grid* out) {
@@ -92,18 +58,10 @@ struct Sp3Conv {
   int k[3], s[3], p[3];
 };
 
-__device__ __forceinline__ int64_t sp3_key(const Sp3Grid& g, int b, int z, int y, int x) { return (((int64_t)b * g.D + z) * g.H + y) * g.W + x; }
-
 __device__ __forceinline__ bool sp3_row(const int32_t* __restrict__ coords, int64_t i, const Sp3Grid& g, int (&c)[4]) {
   const int4 v = *reinterpret_cast<const int4*>(coords + 4 * i);
   c[0] = v.x, c[1] = v.y, c[2] = v.z, c[3] = v.w;
   return c[0] >= 0 && c[0] < g.B && c[1] >= 0 && c[1] < g.D && c[2] >= 0 && c[2] < g.H && c[3] >= 0 && c[3] < g.W;
-}
-
-__device__ __forceinline__ uint32_t sp3_rank(const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk,
-                                             int64_t k) {
-  const int64_t w = k >> 5;
-  return blk[w >> PNX_SCAN_SHIFT] + pre[w] + (uint32_t)__popc(bitmap[w] & ((1u << (k & 31)) - 1u));
 }
 
 // rows with a coordinate outside the grid are skipped here (the module rejects them before calling)
@@ -417,11 +375,6 @@ void sp3_wgrad_nt(int nt, dim3 grid, hipStream_t st, const float* x, int64_t n_i
 #include "sparse3d_half_train.h"  // the 16-bit training form: k_sp3_wgrad_h, its split and its partials buffer
 #include "sparse3d_bn.h"          // train-mode BatchNorm + residual + ReLU over the rows: k_sp3_bn_*, their split and their partials buffer
 
-int sp3_index_args(const Sp3Grid& g, void* index, size_t index_bytes, Sp3Index* ix) {
-  *ix = sp3_carve(index, g);
-  return pnx_check_workspace(index, index_bytes, ix->bytes, "sparse3d index");
-}
-
 // bitmap already marked: word prefix (level 1 + level 2), total set bits -> count
 int sp3_scan(const Sp3Index& ix, int32_t* count, hipStream_t st) {
   if (ix.nblk > 0) k_scan_local<SCAN_POPC><<<ix.nblk, kBlock, 0, st>>>(ix.bitmap, ix.nwords, ix.pre, ix.blk);
@@ -544,8 +497,8 @@ size_t pnx_sp3_packed_weight_floats(int32_t taps, int32_t cin, int32_t cout) {
 static int sp3_conv_run(bool per_tap, const float* x, int64_t n_in, int32_t cin, const int32_t* map, int64_t n_out, int32_t taps, const float* w_packed,
                         const float* shift, const float* residual, int32_t relu, float* y, int32_t cout, pnx_stream_t stream) {
   const char* name = per_tap ? "pnx_sp3_conv_train" : "pnx_sp3_conv";
-  PNX_REQUIRE(cin >= 1 && cin <= 1024 && cout >= 1 && cout <= 144 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
-              "%s: %d -> %d channels over %d taps (cin 1..1024, cout 1..144, taps 1..27)", name, cin, cout, taps);
+  PNX_REQUIRE(cin >= 1 && cin <= 1024 && cout >= 1 && cout <= 192 && taps >= 1 && taps <= 27, PNX_ERR_UNSUPPORTED,
+              "%s: %d -> %d channels over %d taps (cin 1..1024, cout 1..192, taps 1..27)", name, cin, cout, taps);
   PNX_REQUIRE(n_in >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31), PNX_ERR_INVALID, "%s: %lld -> %lld rows", name, (long long)n_in,
               (long long)n_out);
   if (n_out == 0) return PNX_OK;
@@ -561,7 +514,10 @@ static int sp3_conv_run(bool per_tap, const float* x, int64_t n_in, int32_t cin,
     case 6: sp3_conv_launch<6>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
     case 7: sp3_conv_launch<7>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
     case 8: sp3_conv_launch<8>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
-    default: sp3_conv_launch<9>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 9: sp3_conv_launch<9>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 10: sp3_conv_launch<10>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    case 11: sp3_conv_launch<11>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
+    default: sp3_conv_launch<12>(per_tap, nb, st, x, n_in, cin, map, n_out, taps, w_packed, shift, residual, relu, y, cout); break;
   }
   PNX_LAUNCH_CHECK();
   return PNX_OK;

@@ -13,6 +13,11 @@ from .plan import Dyn, LaunchPlan
 from .switches import on
 
 
+def _params_version(module):
+    """Changes whenever a parameter or buffer of the module is replaced or written in place: the key of every cache of folded / packed weights."""
+    return tuple((p.data_ptr(), p._version) for p in list(module.parameters()) + list(module.buffers()))
+
+
 def _fold_bn(weight, bn, conv_bias=None, transposed=False):
     """Fold an eval-mode BatchNorm into the preceding conv: returns (weight', bias') in fp32."""
     w = weight.detach().float()

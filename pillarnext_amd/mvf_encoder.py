@@ -16,7 +16,10 @@ Same class names, constructor arguments and state-dict keys as the reference.  W
     positions need a gradient);
   * the per-view sparse ResNets: in eval mode the masked HIP convolution kernels of the PillarNeXt backbone (csrc/conv3x3.hip; BatchNorm folded,
     bf16, the 48 / 96 / 192 channels zero-padded to the kernels' 64 / 128 / 256: _HipViewNet), in training the masked-dense blocks of models.py
-    (spconv is absent from the image; like the backbone that part is unpinned); the two PointNets: in training the same fused node (pointnet2
+    (spconv is absent from the image; like the backbone that part is unpinned), or, after use_sparse_rows(), the sparse gather-GEMM kernels of
+    csrc/sparse3d.hip over the rows of the active cells -- a 2-D sparse convolution is the 3-D one on a grid of depth 1 -- in eval (BatchNorm
+    folded, fp32) and in training (sparse3d.SparseConvFunction + SparseBNActFunction per layer), sampled by pnx_sp3_bilinear_gather: no
+    (B, H, W, C) map exists at any stage; the two PointNets: in training the same fused node (pointnet2
     hands over its per-pillar maximum and never writes the (N, 256) activation), otherwise torch Linear (rocBLAS) + BatchNorm + ReLU.
 CUDA tensors only: there is no CPU path."""
 import numpy as np
@@ -26,9 +29,10 @@ from torch.nn import functional as F
 
 from . import ops
 from ._lib import PNX_GROUP_CYLINDER_CLAMP, PNX_GROUP_PILLAR_CLAMP
-from .fused import _fold_bn, _HipConv3x3
+from .fused import _fold_bn, _HipConv3x3, _params_version
 from .models import SparseBasicBlock, SparseConvBlock, _Seq
 from .reader import PFNLayer
+from .sparse3d import SparseBNActFunction, SparseConvFunction, SparseDenseFunction
 from .switches import on
 from .voxel_encoder import _device_points, batch_of, grid_of
 
@@ -204,8 +208,22 @@ class _HipViewNet:
         return x
 
 
-def _params_version(module):
-    return tuple((p.data_ptr(), p._version) for p in list(module.parameters()) + list(module.buffers()))
+def sparse_weight_view(conv):
+    """The (Cout, Cin, kH, kW) weight of a view's _SpConv2d as the sparse kernels read it: (Cout, 1, kH, kW, Cin), a VIEW of the parameter (no
+    copy, so autograd delivers dW in the parameter's own layout and a checkpoint written either way loads either way)."""
+    return conv.weight.permute(0, 2, 3, 1).unsqueeze(1)
+
+
+def _no_tick(phase):
+    pass
+
+
+def _conv_geom(conv):
+    """(kernel, stride, padding) of a view's 2-D convolution as the 3-D geometry over a grid of depth 1."""
+    (kh, kw), (sh, sw), (ph, pw) = conv.kernel_size, conv.stride, conv.padding
+    if conv.bias is not None or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or (ph, pw) != (kh // 2, kw // 2):
+        raise ops.PnxError("SingleView.use_sparse_rows: bias-free, undilated convolutions with padding k // 2 only")
+    return (1, int(kh), int(kw)), (1, int(sh), int(sw)), (0, int(ph), int(pw))
 
 
 class SingleView(nn.Module):
@@ -225,6 +243,7 @@ class SingleView(nn.Module):
                                           + [SparseBasicBlock(ds_num_filters[i], kernel_size[i]) for _ in range(n)]) for i, n in enumerate(layer_nums)])
         self.ds_rate = np.prod(np.array(ds_layer_strides))
         self.conv_dtype = None      # None: the blocks run as fp32 torch modules; torch.bfloat16 / float16: eval runs them on the HIP kernels (use_hip_convs)
+        self.sparse_rows = False    # True: every call use_hip_convs does not serve runs the blocks on the rows of the active cells (use_sparse_rows)
 
     def use_hip_convs(self, dtype=torch.bfloat16):
         """Inference in 16-bit activations for the view's sparse ResNet (what FusedPillarNeXt is to the PillarNeXt backbone): eval-mode forwards under
@@ -233,6 +252,95 @@ class SingleView(nn.Module):
             raise ops.PnxError("use_hip_convs: torch.bfloat16, torch.float16 or None")
         self.conv_dtype = dtype
         return self
+
+    def use_sparse_rows(self, enabled=True):
+        """The view's sparse ResNet and its sampling on the ROWS of the active cells (csrc/sparse3d.hip, fp32) instead of a dense (B, H, W, C) map,
+        in eval and in training: memory and time follow the number of occupied cells, not the grid.  Same modules, parameters and state-dict keys;
+        results equal the masked-dense path's up to fp32 summation order.  Eval under no_grad keeps use_hip_convs where that is set (16-bit);
+        every other call takes the rows.  CUDA tensors only.  Off by default; returns self."""
+        self.sparse_rows = bool(enabled)
+        return self
+
+    def _rows_folded(self):
+        """{conv: (packed weight with the eval BatchNorm's scale folded in, shift)} for pnx_sp3_conv, once per parameter version."""
+        f = self.__dict__.get("_rows_folded_cache")
+        version = _params_version(self.blocks)
+        if f is None or f[0] != version:
+            layers = {}
+            for seq in self.blocks:
+                for m in seq:
+                    for conv, bn in ((m.conv, m.norm),) if isinstance(m, SparseConvBlock) else ((m.block1.conv, m.block1.norm), (m.conv2, m.norm2)):
+                        a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)    # sparse3d._fold's algebra
+                        w = sparse_weight_view(conv).detach().float() * a.view(-1, 1, 1, 1, 1)
+                        layers[conv] = (ops.sp3_pack_weight(w), (bn.bias.detach().float() - bn.running_mean.detach().float() * a).contiguous())
+            f = self.__dict__["_rows_folded_cache"] = (version, layers)
+        return f[1]
+
+    def _rows_conv(self, x, m, conv, norm, subm, folded, residual=None):
+        """One layer on rows: relu(BatchNorm(conv(x)) [+ residual]).  folded: the eval plan; None: under autograd."""
+        if folded is not None:
+            wp, shift = folded[conv]
+            return ops.sp3_conv(x, m, wp, shift, conv.out_channels, residual=residual, relu=True)
+        y = SparseConvFunction.apply(x, sparse_weight_view(conv), m, subm, _no_tick)
+        if norm.training:
+            return SparseBNActFunction.apply(y, norm.weight, norm.bias, residual, None, norm, True, None)[0]
+        y = F.batch_norm(y, norm.running_mean, norm.running_var, norm.weight, norm.bias, False, 0.0, norm.eps)
+        return torch.relu(y if residual is None else y + residual)
+
+    def sparse_sets(self, fv, unq, batch_size, H, W, differentiable=None):
+        """`blocks` on rows: fv (P, C) fp32 at unq (P, 3) int32 [b, y, x] (distinct cells) -> per stage (coords (N, 4) int32 [b, 0, y, x] in
+        rank = [b, y, x] order, features (N, C_stage) fp32, the set's ops.Sp3Index over (1, H_stage, W_stage)).  A SparseConvBlock builds its output
+        set (the 3x3 / stride pooled input set; one host sync reads its size), a stage's SparseBasicBlocks share one submanifold map.
+        differentiable (default: training mode, or a gradient is wanted): layer by layer under autograd instead of the folded eval kernels."""
+        if not (fv.is_cuda and unq.is_cuda):
+            raise ops.PnxError("SingleView.use_sparse_rows needs CUDA (ROCm) tensors; the sparse kernels have no CPU implementation")
+        if fv.dtype != torch.float32 or fv.dim() != 2 or unq.dim() != 2 or unq.shape[1] != 3 or unq.shape[0] != fv.shape[0]:
+            raise ops.PnxError("SingleView.sparse_sets: fv (P, C) fp32 with one row per cell of unq (P, 3) [b, y, x]")
+        if differentiable is None:
+            differentiable = self.training or torch.is_grad_enabled() and (fv.requires_grad or any(p.requires_grad for p in self.blocks.parameters()))
+        B = int(batch_size)
+        u = unq.int()
+        coords = torch.stack([u[:, 0], torch.zeros_like(u[:, 0]), u[:, 1], u[:, 2]], dim=1).contiguous()
+        ix, rows, _ = ops.sp3_index_build(coords, B, (1, H, W), want_rows=True)
+        folded = None if differentiable else self._rows_folded()
+        x = fv.contiguous()
+        sets = []
+        for seq in self.blocks:
+            for j, m in enumerate(seq):
+                if j == 0 and isinstance(m, SparseConvBlock):
+                    k, s, p = _conv_geom(m.conv)
+                    if m.subm:
+                        nb = ops.sp3_neighbor_map(coords, ix, rows, k, (1, 1, 1), p)
+                    else:
+                        oix, cnt = ops.sp3_out_index(coords, B, ix.grid, k, s, p)
+                        oc = ops.sp3_index_coords(oix, int(cnt.item()))
+                        nb = ops.sp3_neighbor_map(oc, ix, rows, k, s, p)
+                        ix, coords = oix, oc
+                    rows = None      # a layer's output rows are in rank order
+                    x = self._rows_conv(x, nb, m.conv, m.norm, m.subm, folded)
+                    sub = None
+                elif isinstance(m, SparseBasicBlock) and j > 0:
+                    k, s, p = _conv_geom(m.conv2)
+                    if s != (1, 1, 1) or _conv_geom(m.block1.conv) != (k, s, p):
+                        raise ops.PnxError("SingleView.use_sparse_rows: a basic block's convolutions must be two equal stride-1 kernels")
+                    if sub is None or sub[0] != k:
+                        sub = (k, ops.sp3_neighbor_map(coords, ix, None, k, s, p))     # shared by the stage's submanifold layers
+                    y = self._rows_conv(x, sub[1], m.block1.conv, m.block1.norm, True, folded)
+                    x = self._rows_conv(y, sub[1], m.conv2, m.norm2, True, folded, residual=x)
+                else:
+                    raise ops.PnxError(f"SingleView.use_sparse_rows: unexpected module {type(m).__name__} at position {j} of a stage")
+            sets.append((coords, x, ix))
+        return sets
+
+    def _forward_rows(self, fv, pos, unq, unq_inv, batch_size, H, W):
+        coords, x, ix = self.sparse_sets(fv, unq, batch_size, H, W)[-1]
+        ds = int(self.ds_rate)
+        if torch.is_grad_enabled() and pos.requires_grad:
+            # the positions need a gradient: the torch statement on the (small, last-stage) dense map, as on the masked-dense path
+            return self.sample(SparseDenseFunction.apply(x, coords, ix.batch, ix.grid), pos, unq, unq_inv)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return ops.SparseBilinearGather.apply(x, coords, ix, pos, self.bias, self.voxel_size, unq, unq_inv, ds)
+        return ops.sp3_bilinear_gather(x, ix, pos, self.bias, self.voxel_size, unq, unq_inv, ds)
 
     def _pos_columns(self, features):
         return features[:, 0:2] if self.mode == "pillar" else features[:, 10:12]
@@ -283,6 +391,8 @@ class SingleView(nn.Module):
                 x = net(fv, unq, batch_size, H, W)
                 out = ops.bilinear_gather(x, pos, self.bias, self.voxel_size, unq, unq_inv, int(self.ds_rate))
                 return out[:, : net.cout_true].contiguous()
+        if self.sparse_rows:
+            return self._forward_rows(fv, pos, unq, unq_inv, batch_size, H, W)
         canvas = torch.zeros((batch_size, H, W, fv.shape[1]), dtype=fv.dtype, device=fv.device)
         mask = torch.zeros((batch_size, 1, H, W), dtype=fv.dtype, device=fv.device)
         u = unq.long()
@@ -332,6 +442,17 @@ class MVFFeatureNet(nn.Module):
     def use_hip_convs(self, dtype=torch.bfloat16):
         """Both views' sparse ResNets on the masked HIP convolution kernels in eval mode (SingleView.use_hip_convs)."""
         self.pillarview.use_hip_convs(dtype), self.cylinderview.use_hip_convs(dtype)
+        return self
+
+    def use_sparse_rows(self, enabled=True, views=("pillar", "cylinder")):
+        """SingleView.use_sparse_rows for the named views ("pillar", "cylinder"); a view that is not named is switched off.  The cylinder view's
+        grid is small and far denser than the pillar view's: views=("pillar",) keeps it on the masked-dense path.  Returns self."""
+        by_name = {"pillar": self.pillarview, "cylinder": self.cylinderview}
+        unknown = [v for v in views if v not in by_name]
+        if unknown:
+            raise ops.PnxError(f"use_sparse_rows: unknown views {unknown} (pillar, cylinder)")
+        for name, view in by_name.items():
+            view.use_sparse_rows(bool(enabled) and name in views)
         return self
 
     def group_views(self, points, batch_size=None):

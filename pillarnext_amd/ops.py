@@ -281,6 +281,82 @@ class BilinearGather(torch.autograd.Function):
         return gi.to(dtype), None, None, None, None, None, None
 
 
+def _sp3_bilinear_args(what, ix, pos, cell_coords, unq_inv, ds_rate):
+    if len(ix.grid) != 3 or ix.grid[0] != 1:
+        raise PnxError(f"{what}: the set must lie over a grid (1, H, W), got {ix.grid}")
+    if not (pos.dtype == torch.float32 and pos.dim() == 2 and pos.shape[1] >= 2 and pos.stride(1) == 1 and cell_coords.dtype == torch.int32
+            and unq_inv.dtype == torch.int64 and unq_inv.shape[0] == pos.shape[0]):
+        raise PnxError(f"{what}: pos fp32 rows, int32 coords, int64 unq_inv")
+    if not (pos.is_cuda and cell_coords.is_cuda and unq_inv.is_cuda):
+        raise PnxError(f"{what} needs CUDA (ROCm) tensors; there is no CPU implementation")
+    ds = int(ds_rate)
+    if ds < 1 or ds & (ds - 1):
+        raise PnxError(f"{what}: ds_rate {ds_rate} is not a power of two")
+    return ds
+
+
+def sp3_bilinear_gather(rows, ix, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate):
+    """pnx_sp3_bilinear_gather: bilinear_gather on the rows (n_rows, C) fp32 of the active set indexed by ix (an Sp3Index over grid (1, H, W)) instead
+    of a dense map -> (N, C) fp32, equal to bilinear_gather on the map scattered from the rows."""
+    _need_cuda(rows, "rows")
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] < 1:
+        raise PnxError("sp3_bilinear_gather: rows must be (n_rows, C) fp32")
+    ds = _sp3_bilinear_args("sp3_bilinear_gather", ix, pos, cell_coords, unq_inv, ds_rate)
+    n, C = pos.shape[0], rows.shape[1]
+    out = torch.empty((n, C), dtype=torch.float32, device=rows.device)
+    mn = (ctypes.c_float * 2)(float(pos_min[0]), float(pos_min[1]))
+    vs = (ctypes.c_float * 2)(float(pos_voxel[0]), float(pos_voxel[1]))
+    check(lib().pnx_sp3_bilinear_gather(ptr(rows), rows.shape[0], C, ptr(ix.buf), ix.nbytes, ix.batch, ix.grid[1], ix.grid[2], ptr(pos),
+                                        pos.stride(0) if n > 1 else 2, mn, vs, ptr(cell_coords.contiguous()), ptr(unq_inv.contiguous()), ds, n, ptr(out), C,
+                                        stream_ptr()), "pnx_sp3_bilinear_gather")
+    return out
+
+
+def sp3_bilinear_gather_backward(grad_out, coords, ix, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate):
+    """pnx_sp3_bilinear_gather_backward: grad_out (N, C) fp32 with unit column stride (a column slice is read in place), coords (n_rows, 4) int32
+    [b, 0, y, x] = the rows of the set ix indexes -> the gradient of the rows (n_rows, C) fp32, fully written: bilinear_gather_backward's map read
+    at coords, bit for bit.  Deterministic."""
+    _need_coords(coords)
+    ds = _sp3_bilinear_args("sp3_bilinear_gather_backward", ix, pos, cell_coords, unq_inv, ds_rate)
+    n = pos.shape[0]
+    if not (grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.dim() == 2 and grad_out.shape[0] == n and grad_out.shape[1] >= 1):
+        raise PnxError("sp3_bilinear_gather_backward: grad_out (N, C) fp32 CUDA rows")
+    C = grad_out.shape[1]
+    if not ((n == 0 or grad_out.stride(1) == 1 or C == 1) and (n <= 1 or grad_out.stride(0) >= C)):
+        raise PnxError("sp3_bilinear_gather_backward: grad_out needs unit column stride and a row stride >= C")
+    n_rows = coords.shape[0]
+    nbytes = lib().pnx_sp3_bilinear_gather_backward_scratch_bytes(n, n_rows)
+    if nbytes == 0:
+        raise PnxError("sp3_bilinear_gather_backward: point or row count beyond 32-bit indices")
+    out = torch.empty((n_rows, C), dtype=torch.float32, device=grad_out.device)
+    ws = _BILGRAD_WS.get(nbytes, grad_out.device)
+    mn = (ctypes.c_float * 2)(float(pos_min[0]), float(pos_min[1]))
+    vs = (ctypes.c_float * 2)(float(pos_voxel[0]), float(pos_voxel[1]))
+    check(lib().pnx_sp3_bilinear_gather_backward(ptr(grad_out), grad_out.stride(0) if n > 1 else C, ptr(coords), n_rows, ix.batch, ix.grid[1], ix.grid[2], C,
+                                                 ptr(pos), pos.stride(0) if n > 1 else 2, mn, vs, ptr(cell_coords.contiguous()), ptr(unq_inv.contiguous()),
+                                                 ds, n, ptr(out), ptr(ws), ws.numel(), stream_ptr()), "pnx_sp3_bilinear_gather_backward")
+    return out
+
+
+class SparseBilinearGather(torch.autograd.Function):
+    """sp3_bilinear_gather with a gradient for the rows (sp3_bilinear_gather_backward).  pos and the index tensors get none."""
+
+    @staticmethod
+    def forward(ctx, rows, coords, ix, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate):
+        ctx.save_for_backward(coords, pos, cell_coords, unq_inv)
+        ctx.geom = (ix, pos_min, pos_voxel, ds_rate)
+        return sp3_bilinear_gather(rows.contiguous(), ix, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        coords, pos, cell_coords, unq_inv = ctx.saved_tensors
+        ix, pos_min, pos_voxel, ds_rate = ctx.geom
+        g = grad_out
+        if g.dtype != torch.float32 or g.shape[0] > 0 and (g.stride(1) != 1 or g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+            g = g.float().contiguous()          # an expanded or transposed gradient; the column slice torch.cat's backward hands over is read in place
+        return sp3_bilinear_gather_backward(g, coords, ix, pos, pos_min, pos_voxel, cell_coords, unq_inv, ds_rate), None, None, None, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------------------------- per-point training layer (csrc/point_layer_train.hip)
 _PL_WS = Workspace()
 
@@ -1200,8 +1276,26 @@ def sp3_wgrad_workspace_bytes(n_out, taps, cin, cout):
     return n
 
 
+SP3_WGRAD_MAX_CHANNELS = 144  # the widest operand of one pnx_sp3_wgrad call
+
+
+def sp3_wgrad_blocks(channels):
+    """The column blocks [(start, size)] in which sp3_wgrad serves `channels`: one block up to 144; above, k = ceil(channels / 144) blocks of
+    round_up(ceil(channels / k), 16) columns, the last one taking what is left (192 -> 96 + 96, 176 -> 96 + 80, 150 -> 80 + 70)."""
+    c = int(channels)
+    if c < 1:
+        raise PnxError(f"sp3_wgrad: {channels} channels")
+    if c <= SP3_WGRAD_MAX_CHANNELS:
+        return [(0, c)]
+    k = -(-c // SP3_WGRAD_MAX_CHANNELS)
+    size = (-(-c // k) + 15) // 16 * 16
+    return [(s, min(size, c - s)) for s in range(0, c, size)]
+
+
 def sp3_wgrad(x, nbmap, dy):
-    """pnx_sp3_wgrad: x (N_in, Cin), nbmap (N_out, T), dy (N_out, Cout) -> dw (Cout, T, Cin) fp32."""
+    """pnx_sp3_wgrad: x (N_in, Cin), nbmap (N_out, T), dy (N_out, Cout) -> dw (Cout, T, Cin) fp32.  Cin or Cout above 144 (the entry point's range):
+    one call per pair of column blocks (sp3_wgrad_blocks) on contiguous column copies, written to dw[co block, :, ci block] -- every element of dw
+    is still one call's fixed-order sum over the rows."""
     for t, name in ((x, "x"), (nbmap, "nbmap"), (dy, "dy")):
         _need_cuda(t, name)
     if x.dtype != torch.float32 or dy.dtype != torch.float32 or nbmap.dtype != torch.int32 or x.dim() != 2 or dy.dim() != 2 or nbmap.dim() != 2:
@@ -1210,10 +1304,24 @@ def sp3_wgrad(x, nbmap, dy):
         raise PnxError("sp3_wgrad: dy and nbmap must have one row per output site, and every operand must be contiguous")
     n_out, T = nbmap.shape
     ci, co = x.shape[1], dy.shape[1]
-    nbytes = sp3_wgrad_workspace_bytes(n_out, T, ci, co)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+
+    def one(xb, dyb):
+        cib, cob = xb.shape[1], dyb.shape[1]
+        nbytes = sp3_wgrad_workspace_bytes(n_out, T, cib, cob)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+        dwb = torch.empty((cob, T, cib), dtype=torch.float32, device=x.device)
+        check(lib().pnx_sp3_wgrad(ptr(xb), xb.shape[0], cib, ptr(dyb), cob, ptr(nbmap), n_out, T, ptr(dwb), ptr(ws), nbytes, stream_ptr()), "pnx_sp3_wgrad")
+        return dwb
+
+    ci_blocks, co_blocks = sp3_wgrad_blocks(ci), sp3_wgrad_blocks(co)
+    if len(ci_blocks) == 1 and len(co_blocks) == 1:
+        return one(x, dy)
     dw = torch.empty((co, T, ci), dtype=torch.float32, device=x.device)
-    check(lib().pnx_sp3_wgrad(ptr(x), x.shape[0], ci, ptr(dy), co, ptr(nbmap), n_out, T, ptr(dw), ptr(ws), nbytes, stream_ptr()), "pnx_sp3_wgrad")
+    xs = [x if len(ci_blocks) == 1 else x[:, s:s + k].contiguous() for s, k in ci_blocks]
+    for so, ko in co_blocks:
+        dyb = dy if len(co_blocks) == 1 else dy[:, so:so + ko].contiguous()
+        for (si, ki), xb in zip(ci_blocks, xs):
+            dw[so:so + ko, :, si:si + ki] = one(xb, dyb)
     return dw
 
 

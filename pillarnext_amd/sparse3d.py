@@ -36,7 +36,7 @@ from torch import nn
 
 from . import dist_utils, ops
 from ._lib import PnxError
-from .mvf_encoder import _params_version
+from .fused import _params_version
 
 
 def _triple(v):
@@ -205,7 +205,7 @@ class SparseBNActFunction(torch.autograd.Function):
 
         forward(y, gamma, beta, residual, residual_h, norm, relu, dtype) -> (out (n, C) fp32, out_h or None)
 
-    norm (nn.BatchNorm1d or nn.SyncBatchNorm, in training mode) gives eps and momentum and has its running_mean, running_var and
+    norm (nn.BatchNorm1d, nn.SyncBatchNorm or the view nets' models.MaskedBatchNorm, in training mode) gives eps and momentum and has its running_mean, running_var and
     num_batches_tracked moved exactly as torch's training-mode BatchNorm1d moves them (unbiased variance); n <= 1 without synchronisation raises
     as torch does, n == 0 returns empty outputs and leaves the buffers alone.  The node saves y, the residual operand it read and the per-channel
     vectors -- not out: the backward recomputes the ReLU gate from them.
@@ -215,7 +215,8 @@ class SparseBNActFunction(torch.autograd.Function):
     as the 16-bit eval path (pnx_sp3_conv_h) does, so training and inference add the same residual, and keeps only them for the backward
     (the next convolution holds them anyway: no fp32 activation but y survives the forward); the fp32 `residual` only carries the graph, and
     its gradient passes the rounding straight through: dresidual = g.  Without residual_h (fp32 mode) the fp32 residual is read, as before.
-    nn.SyncBatchNorm: [sum x | sum x^2 | n] is all-reduced in fp64 once in the forward (this rank's sums re-centred from its running mean to
+    nn.SyncBatchNorm, or a models.MaskedBatchNorm whose enable_sync() was called (convert_sync_batchnorm; the group is its sync_group):
+    [sum x | sum x^2 | n] is all-reduced in fp64 once in the forward (this rank's sums re-centred from its running mean to
     0 first), [sum g | sum g xhat] once in the backward, through dist_utils.all_reduce_sum(t, norm.process_group) looked up at call time;
     dgamma and dbeta stay the local sums (DDP averages them).  A rank without rows issues both collectives all the same."""
 
@@ -225,8 +226,9 @@ class SparseBNActFunction(torch.autograd.Function):
             raise PnxError("SparseBNActFunction: the norm must track running statistics with a fixed momentum")
         y = y.contiguous()
         n, C = y.shape
-        sync = isinstance(norm, nn.SyncBatchNorm)
-        group = norm.process_group if sync else False
+        masked_sync = bool(getattr(norm, "sync", False)) and not isinstance(norm, nn.SyncBatchNorm)  # models.MaskedBatchNorm after enable_sync()
+        sync = isinstance(norm, nn.SyncBatchNorm) or masked_sync
+        group = (norm.sync_group if masked_sync else norm.process_group) if sync else False
         res = residual_h if residual_h is not None else (None if residual is None else residual.contiguous())
         ctx.relu, ctx.group, ctx.empty = bool(relu), group, n == 0 and not sync
         if ctx.empty:

@@ -12,7 +12,11 @@ medians of device-event times after warm-up, torch.cuda.max_memory_allocated abo
 runs it alone) times the reader's six per-point layers at the same geometry -- the PFN layers of both views (20 -> 24, 48 -> 48), pointnet1
 (20 -> 192) and pointnet2 (576 -> 256 + per-pillar max) -- forward + backward, the fused node of csrc/point_layer_train.hip (PNX_TRAIN_POINT_HIP=1)
 against the torch modules (=0, the parent's path), alternating in one run: median / min / max of device-event times and peak memory above the
-inputs per layer and in total, the weight-gradient difference, and the verdict the switch's default follows; it writes --points-out."""
+inputs per layer and in total, the weight-gradient difference, and the verdict the switch's default follows; it writes --points-out.
+--train --sparse-rows runs the view nets' leg instead: each view's sparse ResNet (configs/mvf18_aspp_waymo.yaml: 48 / 96 / 192 / 192, two basic blocks
+per stage) + its sampling, forward + backward from the cell features, masked dense (the (B, H, W, C) canvas through models.py's blocks) against
+SingleView.use_sparse_rows (rows of the active cells on csrc/sparse3d.hip), alternating in one run: device-event times, peak memory above the inputs,
+the rows per stage; then the sampler alone, pnx_sp3_bilinear_gather + backward against the dense pair; it writes --views-out."""
 import argparse
 import os
 import sys
@@ -85,6 +89,89 @@ def train_leg(a):
                   f"peak above the inputs {peak[leg] / 2**20:7.1f} MiB")
         print(f"{view.mode:8s} view: max |grad(node) - grad(torch)| / max |grad| = {diff:.2e}; node / torch time = {np.median(times['node']) / np.median(times['torch']):.3f}")
     print(f"both views: node {total['node']:.1f} us, torch {total['torch']:.1f} us, node / torch = {total['node'] / total['torch']:.3f}")
+
+
+def view_nets_leg(a):
+    """The two view nets in training at full size, masked dense against sparse rows."""
+    B = a.batch
+    t = torch.from_numpy(synth.make_batch("C4", B, "sweep", n=a.points)).cuda()
+    pr, vs = [-76.8, -76.8, -10.0, 76.8, 76.8, 10.0], [0.075, 0.075, 20]
+    cr, cs = [-180, -10.0, 0, 180, 10.0, 107], [0.140625, 0.2, 107]
+    torch.manual_seed(0)
+    m = MVFFeatureNet(in_channels=5, voxel_size=vs, pc_range=pr, cylinder_size=cs, cylinder_range=cr, num_filters=[48, 48], layer_nums=[2, 2, 2, 2],
+                      ds_layer_strides=[1, 2, 2, 2], ds_num_filters=[48, 96, 192, 192], kernel_size=[3, 3, 3, 3], out_channels=256).cuda().train()
+    with torch.no_grad():
+        feat, rp, rc, _ = m.group_views(t, B)
+    n = feat.shape[0]
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    say(f"# the multi-view reader's view nets in training, forward + backward from the cell features (blocks + sampling): {n} points in {B} frames, MI355X")
+    say("# rows = SingleView.use_sparse_rows (csrc/sparse3d.hip, pnx_sp3_bilinear_gather); dense = the (B, H, W, C) canvas through the masked-dense blocks, the parent's path")
+    total = {"rows": 0.0, "dense": 0.0}
+    for view, r, (H, W) in ((m.pillarview, rp, (2048, 2048)), (m.cylinderview, rc, (100, 2560))):
+        P = r["coords"].shape[0]
+        fv = torch.randn((P, 48), device="cuda", generator=gen).requires_grad_(True)
+        go = torch.randn((n, 192), device="cuda", generator=gen)
+        view.cell_features = lambda features, unq_inv, num_cells, fv=fv: fv
+        with torch.no_grad():
+            sets = view.use_sparse_rows().sparse_sets(fv.detach(), r["coords"], B, H, W, differentiable=False)
+        say(f"{view.mode:8s} view, grid {B} x {H} x {W}: {P} active cells ({100.0 * P / (B * H * W):.2f} %); rows per stage "
+            + ", ".join(f"{c.shape[0]} of {B * ix.grid[1] * ix.grid[2]}" for c, _, ix in sets))
+        del sets
+
+        def step():
+            fv.grad = None
+            view.zero_grad(set_to_none=True)
+            view(feat, r["coords"], r["unq_inv"], np.array([H, W]), B).backward(go)
+
+        times, peak, grads = {"rows": [], "dense": []}, {}, {}
+        for it in range(a.warm + a.iters):
+            for leg in ("rows", "dense"):                                          # alternating, so that both see the same machine
+                view.use_sparse_rows(leg == "rows")
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                step()
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= a.warm:
+                    times[leg].append(e0.elapsed_time(e1))
+                    peak[leg] = max(peak.get(leg, 0), torch.cuda.max_memory_allocated() - base)
+                grads[leg] = (fv.grad.detach().clone(), view.blocks[0][0].conv.weight.grad.detach().clone())
+        del view.cell_features
+        for leg in ("rows", "dense"):
+            ms = np.sort(np.asarray(times[leg]))
+            total[leg] += float(np.median(ms))
+            say(f"{view.mode:8s} view, {leg:5s}: median {np.median(ms):9.2f} ms  (min {ms[0]:9.2f}, max {ms[-1]:9.2f}, {len(ms)} runs), peak above the inputs {peak[leg] / 2**20:9.1f} MiB")
+        d = [float((a_ - b_).abs().max() / b_.abs().max()) for a_, b_ in zip(grads["rows"], grads["dense"])]
+        say(f"{view.mode:8s} view: max |d fv(rows) - d fv(dense)| / max = {d[0]:.2e}, first conv's dW {d[1]:.2e}; rows / dense time = "
+            f"{np.median(times['rows']) / np.median(times['dense']):.3f}, peak memory = {peak['rows'] / peak['dense']:.4f}")
+        # the sampler alone: the rows of the last stage against the dense map scattered from them
+        with torch.no_grad():
+            coords, x, ix = view.use_sparse_rows().sparse_sets(fv.detach(), r["coords"], B, H, W, differentiable=False)[-1]
+        pos, ds = view._pos_columns(feat), int(view.ds_rate)
+        img = torch.zeros((B, ix.grid[1], ix.grid[2], 192), device="cuda")
+        cl = coords.long()
+        img[cl[:, 0], cl[:, 2], cl[:, 3]] = x
+        img = img.permute(0, 3, 1, 2)
+        for name, fn in (("pnx_sp3_bilinear_gather          ", lambda: ops.sp3_bilinear_gather(x, ix, pos, view.bias, view.voxel_size, r["coords"], r["unq_inv"], ds)),
+                         ("pnx_bilinear_gather              ", lambda: ops.bilinear_gather(img, pos, view.bias, view.voxel_size, r["coords"], r["unq_inv"], ds)),
+                         ("pnx_sp3_bilinear_gather_backward ", lambda: ops.sp3_bilinear_gather_backward(go, coords, ix, pos, view.bias, view.voxel_size, r["coords"], r["unq_inv"], ds)),
+                         ("pnx_bilinear_gather_backward     ", lambda: ops.bilinear_gather_backward(go, tuple(img.shape), pos, view.bias, view.voxel_size, r["coords"], r["unq_inv"], ds))):
+            say(f"{view.mode:8s} view, {name} {x.shape[0]} rows / map {B} x {ix.grid[1]} x {ix.grid[2]} x 192, {n} points: {timed(fn):8.1f} us per call (wall, 20 calls)")
+        del img
+    say(f"both views: rows {total['rows']:.2f} ms, dense {total['dense']:.2f} ms, rows / dense = {total['rows'] / total['dense']:.3f}")
+    if a.views_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.views_out)), exist_ok=True)
+        with open(a.views_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def point_layers_leg(a):
@@ -197,7 +284,13 @@ def main():
     ap.add_argument("--leg", choices=["all", "sampling", "points"], default="all", help="--train: the sampling leg, the per-point layers, or both")
     ap.add_argument("--points-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mvf_point_layers_train.txt"),
                     help="--train: where the per-point layers' leg writes its report ('' = nowhere)")
+    ap.add_argument("--sparse-rows", action="store_true", help="--train: the view nets' leg, masked dense against SingleView.use_sparse_rows")
+    ap.add_argument("--views-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mvf_view_nets_sparse.txt"),
+                    help="--train --sparse-rows: where the view nets' leg writes its report ('' = nowhere)")
     a = ap.parse_args()
+    if a.train and a.sparse_rows:
+        view_nets_leg(a)
+        return
     if a.train:
         if a.leg in ("all", "sampling"):
             train_leg(a)

@@ -73,6 +73,7 @@ int main() {
       check("group_carve", [&](void* b) { return group_carve(b, n, 6, 2, &g).bytes; });
     }
     check("bilgrad_carve", [&](void* b) { return bilgrad_carve(b, n, 2 * 9 * 11).bytes; });
+    for (int64_t rows : kCounts) check("sp3_bilgrad_carve", [&](void* b) { return sp3_bilgrad_carve(b, n, rows).bytes; });
 #elif defined(UNIT_scatter)
     for (int64_t p : kCounts) check("sm_carve", [&](void* b) { return sm_carve(b, n, p).bytes; });
 #elif defined(UNIT_sparse3d)
